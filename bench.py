@@ -8,7 +8,13 @@ batch=16 per GPU, T=20, random-init UNet, fp32-grade arithmetic.  The default co
 accumulate): it meets the fp32 parity bound (|delta| < 1e-3; measured ~3e-6, tests/test_gpu_parity.py)
 at ~3x the throughput of the exact-fp32 MFMA path, which stays available as --precision f32.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--no-cpu-baseline]
+A plain run measures the headline alone: set-up, W warm-up steps, K timed steps, the JSON line.  --full adds
+everything else the line can carry: the sub-records (other precisions, batch regimes, sizes, training steps, the
+file-based val / train records), the CPU baseline with its parity check, the per-conv roofline (HIP events around
+the conv launches) and the clock / power telemetry of the timed region.  --dump-outputs DIR writes what the timed
+path returned in its last step as DIR/<name>.npy (float32 / float64), for output-for-output comparisons of two builds.
+
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full [--no-cpu-baseline]] [--dump-outputs DIR]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 """
 import argparse
@@ -359,10 +365,11 @@ def run_config(eng, dev, precision, B, S, steps, warmup, graph, noise_mode, rank
     return dt, out, prof, prof_dt
 
 
-def run_train(eng, dev, B, S, steps, warmup, rank=0, sync=None, allreduce=None, precision='f16x3', per_pass=None):
+def run_train(eng, dev, B, S, steps, warmup, rank=0, sync=None, allreduce=None, precision='f16x3', per_pass=None, last=None):
     """Time `steps` optimisation steps (BASELINE configs[4], "training step"): noise draw + img2res + q_sample + forward + L1 loss /
     (b*c*h*w) + backward + Adam, all in the engine (no ATen kernel in the timed region), Dropout(0.2) live as in .train() mode.
-    Returns seconds.  A "step" = one optimizer step over one batch of B synthetic 256x256 HR/SR pairs per GPU."""
+    Returns seconds.  A "step" = one optimizer step over one batch of B synthetic 256x256 HR/SR pairs per GPU.
+    last: a dict that receives the loss of the last timed step."""
     g = torch.Generator().manual_seed(777 + rank)
     hr = (torch.rand(B, 3, S, S, generator=g) * 2 - 1).to(dev)
     sr = (hr + 0.1 * torch.randn(B, 3, S, S, generator=g).to(dev)).clamp(-1, 1)
@@ -399,6 +406,8 @@ def run_train(eng, dev, B, S, steps, warmup, rank=0, sync=None, allreduce=None, 
     dt = time.perf_counter() - t0
     eng.set_training(False)
     assert loss == loss
+    if last is not None:
+        last['loss'] = loss
     return dt
 
 
@@ -686,6 +695,27 @@ def gather_rank_times(dt, dev):
     return max(ts), ts
 
 
+DUMP_BUDGET = 64 << 20      # bytes of .npy payload one run writes under --dump-outputs, all ranks together
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs: every array as dirname/<name>.npy, float32 (float64 stays float64).  When together they exceed `budget`
+    bytes, each is cut to a fixed sample of its flattened elements: one element per equal stride, at an offset drawn from a
+    generator seeded with 0, so that two runs with the same arguments write the same elements."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > budget:
+            flat = a.reshape(-1)
+            stride = -(-flat.size // max(1, flat.size * budget // total))
+            base = np.arange(0, flat.size, stride, dtype=np.int64)
+            width = np.minimum(stride, flat.size - base)
+            a = flat[base + (np.random.default_rng(0).random(base.size) * width).astype(np.int64)]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+
+
 def per_rank_stats(ts, units_per_rank):
     v = [units_per_rank / t for t in ts]
     return {'min': min(v), 'max': max(v), 'mean': sum(v) / len(v), 'unit': 'images/s per rank', 'ranks': len(v)}
@@ -805,6 +835,12 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--batch', type=int, default=16, help='images per GPU per step')
     ap.add_argument('--size', type=int, default=256)
+    ap.add_argument('--full', action='store_true',
+                    help='measure more than the headline: sub-records, CPU baseline + parity check, per-conv roofline, clock / power '
+                         'telemetry (a plain run does none of these; the --no-* options below thin out a --full run)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy '
+                         '(float32 / float64, at most 64 MB in all: a fixed seeded sample of a larger output)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-sub-records', action='store_true',
                     help='skip the exact_f32 / bf16_b64_graph / b1_graph legs that ride in the same JSON line at N=1')
@@ -834,6 +870,8 @@ def main():
     distributed = world > 1 or os.environ.get('FDSR_BENCH_FORCE_DIST') == '1'
     if args.gpus != world:
         raise SystemExit(f'--gpus {args.gpus} but WORLD_SIZE={world}')
+    if not args.full:     # a plain run measures the headline and nothing else
+        args.no_cpu_baseline = args.no_sub_records = args.no_profile = args.no_facade = True
 
     import torch.distributed as dist
     from fastdiffsr_amd.arch import UNetConfig, FASTDIFFSR_UNET, FASTDIFFSR_SCHEDULE_VAL
@@ -857,7 +895,7 @@ def main():
     cfg = UNetConfig(**FASTDIFFSR_UNET)
     # weights: rank 0 builds the random-init UNet, ONE RCCL broadcast replicates it
     sd = synth_state_dict(cfg, 0) if rank == 0 else None
-    weights_sha_rank0 = state_dict_sha256(sd) if rank == 0 else None
+    weights_sha_rank0 = state_dict_sha256(sd) if rank == 0 and distributed and args.full else None
     if distributed:
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         with _StdoutToStderr():
@@ -883,10 +921,20 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
+    def out_name(name):
+        return name if world == 1 else f'{name}_rank{rank}'
+
     if args.train:
         Bt = args.batch if args.batch != 16 else 32
         hook = parallel.allreduce_grads if distributed else None
-        dt = run_train(eng, dev, Bt, S, args.steps, args.warmup, rank=rank, sync=sync, allreduce=hook, precision=args.precision)
+        last = {}
+        dt = run_train(eng, dev, Bt, S, args.steps, args.warmup, rank=rank, sync=sync, allreduce=hook, precision=args.precision, last=last)
+        if args.dump_outputs:
+            # what the caller of the step gets back: the loss, and the weights after the last Adam update (every live tensor,
+            # flattened and concatenated in checkpoint order)
+            w = np.concatenate([eng.get_weight(k).reshape(-1) for k, _, live in eng.schema() if live])
+            dump_outputs(args.dump_outputs, {out_name('loss'): np.array([last['loss']], dtype=np.float64), out_name('weights'): w},
+                         DUMP_BUDGET // world)
         rank_ts = [dt]
         if distributed:
             dt, rank_ts = gather_rank_times(dt, dev)
@@ -908,9 +956,11 @@ def main():
         return
 
     # independent per-GPU batch (weak scaling): rank r samples its own B images
-    telemetry = {}
+    telemetry = {} if args.full else None
     dt, out, prof, _ = run_config(eng, dev, args.precision, B, S, args.steps, args.warmup, args.graph, args.noise,
                                   rank=rank, sync=sync, want_profile=not args.no_profile, telemetry=telemetry)
+    if args.dump_outputs:     # the SR images of the last timed step, [B,3,S,S]
+        dump_outputs(args.dump_outputs, {out_name('sr'): out.cpu().numpy()}, DUMP_BUDGET // world)
     rank_ts = [dt]
     if distributed:
         dt, rank_ts = gather_rank_times(dt, dev)
@@ -937,13 +987,14 @@ def main():
             'whole_path_tflops': ips / world * FLOPS_PER_IMAGE / 1e12,
             'whole_path': whole_path(ips / world, args.precision),
             'library': {'version': version.split(' FDSR_SRC_SHA256=')[0], 'source_sha256': version.rsplit('=', 1)[-1]},
-            # mean shader clock / package power of rank 0's GPU over the timed region (hwmon; nominal 2400 MHz): is the regime power-bound?
-            'telemetry': telemetry,
         }
+        if telemetry is not None:
+            # mean shader clock / package power of rank 0's GPU over the timed region (hwmon; nominal 2400 MHz): is the regime power-bound?
+            res['telemetry'] = telemetry
         res['library']['kernel_forms'] = {'k32': bit_names(K32, K32_BITS), 'strip': bit_names(STRIP, STRIP_BITS)}
         if args.debug_option:
             res['debug_options'] = list(args.debug_option)
-        if distributed:   # every rank loaded what rank 0 broadcast: its hash is checked against rank 0's own arrays
+        if distributed and args.full:   # every rank loaded what rank 0 broadcast: its hash is checked against rank 0's own arrays
             res['weights'] = {'sha256_rank0_source': weights_sha_rank0, 'sha256_after_broadcast': state_dict_sha256(sd),
                               'broadcast_bytes': int(sum(np.asarray(v).nbytes for v in sd.values())),
                               'broadcast_seconds_rank0': t_bcast, 'communicator_init_seconds_rank0': t_init}

@@ -123,3 +123,22 @@ def test_launcher_tears_the_job_down_when_one_rank_dies_or_the_parent_is_signall
     p.send_signal(signal.SIGTERM)
     assert p.wait(timeout=60) == 128 + signal.SIGTERM
     assert not any(alive(q) for q in pids(d2))
+
+
+def test_dump_outputs_writes_float_arrays_and_caps_them_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: arrays under the budget are written whole (float32, float64 kept); above it every array is cut to the
+    same seeded sample on every call, within the budget."""
+    import numpy as np
+    import bench
+    x = np.arange(3000, dtype=np.float16).reshape(3, 1000)
+    loss = np.array([0.25], dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / 'a'), {'x': x, 'loss': loss})
+    a = np.load(tmp_path / 'a' / 'x.npy')
+    assert a.dtype == np.float32 and a.shape == (3, 1000) and np.array_equal(a, x.astype(np.float32))
+    assert np.load(tmp_path / 'a' / 'loss.npy').dtype == np.float64
+    big = np.random.default_rng(1).standard_normal(100003).astype(np.float32)
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), {'big': big, 'loss': loss}, budget=40000)
+    b, c = np.load(tmp_path / 'b' / 'big.npy'), np.load(tmp_path / 'c' / 'big.npy')
+    assert b.dtype == np.float32 and 0 < b.nbytes <= 40000 and np.array_equal(b, c)
+    assert np.isin(b, big).all() and len(np.unique(b)) == b.size

@@ -27,7 +27,7 @@ def test_bench_rccl_path_with_one_rank():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT')}
     env.update({'FDSR_BENCH_FORCE_DIST': '1', 'HSA_ENABLE_IPC_MODE_LEGACY': '0'})
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '1', '--warmup', '1',
-                        '--no-cpu-baseline'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=540)
+                        '--full', '--no-cpu-baseline'], cwd=ROOT, env=env, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines                    # RCCL's banner must not leak onto stdout
@@ -54,9 +54,9 @@ def test_bench_rccl_path_with_one_rank():
 
 @pytest.mark.timeout(900)
 def test_bench_default_line_is_complete_and_parity_clean():
-    """The driver's command shape (N=1, all legs): one JSON line carrying the headline, every sub-record without an
+    """The full command shape (N=1, all legs): one JSON line carrying the headline, every sub-record without an
     error, the CPU baseline, and a parity check that holds AFTER the training sub-records ran (they own their engine)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1'], cwd=ROOT,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--full'], cwd=ROOT,
                        capture_output=True, text=True, timeout=840)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -77,6 +77,29 @@ def test_bench_default_line_is_complete_and_parity_clean():
     if 'psnr_delta_db' in pc:
         assert abs(pc['psnr_delta_db']) <= 0.01 and pc['max_abs_diff_image'] <= 1e-3
     assert len(res['library']['source_sha256']) == 64
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times the headline alone: one JSON line with the headline fields and none of the --full records;
+    --dump-outputs writes the SR images of the last timed step, the same on a second run with the same arguments."""
+    import numpy as np
+    sr = []
+    for d in ('a', 'b'):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '2',
+                            '--dump-outputs', str(tmp_path / d)], cwd=ROOT, capture_output=True, text=True, timeout=540)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        res = json.loads(lines[0])
+        assert res['metric'].startswith('256x256 SR images/sec') and res['unit'] == 'images/s' and res['higher_is_better'] is True
+        assert res['dtype'] == 'f16x3' and res['steps'] == 2 and res['value'] > 0
+        assert abs(res['ms_per_step'] - 1e3 * 2 / res['value']) < 1e-6 * res['ms_per_step']     # B=2 images per step
+        assert not {'sub_records', 'cpu_baseline', 'parity_check', 'roofline', 'telemetry'} & set(res)
+        assert os.listdir(tmp_path / d) == ['sr.npy']
+        sr.append(np.load(tmp_path / d / 'sr.npy'))
+    assert sr[0].dtype == np.float32 and sr[0].shape == (2, 3, 256, 256) and np.isfinite(sr[0]).all()
+    assert np.array_equal(sr[0], sr[1])
 
 
 @pytest.mark.timeout(600)

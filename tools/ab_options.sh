@@ -5,7 +5,7 @@ A="$1"; B="$2"; shift 2
 for rep in 1 2; do
   for o in "$A" "$B"; do
     args=""; for kv in $o; do args="$args --debug-option $kv"; done
-    v=$(python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-sub-records $args "$@" 2>/dev/null | python -c "import json,sys; r=json.loads(sys.stdin.readline()); print('%.2f img/s  conv frac %.4f' % (r['value'], r['roofline']['frac']))")
+    v=$(python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-sub-records $args "$@" 2>/dev/null | python -c "import json,sys; r=json.loads(sys.stdin.readline()); print('%.2f img/s  conv frac %.4f' % (r['value'], r['roofline']['frac']))")
     echo "[$o] $v"
   done
 done

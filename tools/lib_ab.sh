@@ -6,7 +6,7 @@ one() {  # lib ("" = the tree's), opts, bench args...
   lib="$1"; o="$2"; shift 2
   args=""; for kv in $o; do args="$args --debug-option $kv"; done
   if [ -n "$lib" ]; then export FDSR_LIB="$lib"; else unset FDSR_LIB; fi
-  v=$(python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-sub-records $args "$@" 2>/dev/null | python -c "import json,sys; r=json.loads(sys.stdin.readline()); print('%.2f img/s  conv frac %.4f' % (r['value'], r['roofline']['frac']))")
+  v=$(python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-sub-records $args "$@" 2>/dev/null | python -c "import json,sys; r=json.loads(sys.stdin.readline()); print('%.2f img/s  conv frac %.4f' % (r['value'], r['roofline']['frac']))")
   echo "[${lib:+variant }$o] $v"
   unset FDSR_LIB
 }

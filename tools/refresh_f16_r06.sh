@@ -2,7 +2,7 @@
 set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-H="--no-cpu-baseline --no-sub-records"
+H="--full --no-cpu-baseline --no-sub-records"
 for n in f16 bf16; do
   rm -rf $O/stats_${n}_b64
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_${n}_b64 -o s -- python3 $R/bench.py $H --precision $n --batch 64 --graph --steps 4 --warmup 1 > $O/stats_${n}_b64.log 2>&1 < /dev/null
@@ -12,5 +12,5 @@ for n in f16 bf16; do
 done
 cd $R
 bash tools/refresh_traffic_r06.sh > $O/traffic_refresh.log 2>&1
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd_f16tree.json 2> $O/bench_driver_cmd_f16tree.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd_f16tree.json 2> $O/bench_driver_cmd_f16tree.err
 echo f16-refresh-done

@@ -9,11 +9,11 @@ set -x
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06; mkdir -p $O
 cd $R
 python -c "import __graft_entry__ as g; g.build()" > $O/build.log 2>&1 < /dev/null
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err < /dev/null
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err < /dev/null
 timeout 600 python bench.py --train --precision f16x3 --steps 3 --warmup 1 > $O/bench_train_f16x3_b32.json 2>/dev/null < /dev/null
 timeout 600 python bench.py --train --precision f32 --steps 3 --warmup 1 > $O/bench_train_f32_b32.json 2>/dev/null < /dev/null
 cd /tmp && export TMPDIR=/tmp
-H="--no-cpu-baseline --no-sub-records"
+H="--full --no-cpu-baseline --no-sub-records"
 stats() {   # name, bench args...
   n=$1; shift
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$n -o s -- python3 $R/bench.py $H "$@" > $O/stats_$n.log 2>&1 < /dev/null
