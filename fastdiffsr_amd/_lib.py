@@ -25,6 +25,10 @@ class FdsrSchedule(C.Structure):
                 ('sigma', C.POINTER(C.c_float))]
 
 
+class FdsrSampleOpts(C.Structure):
+    _fields_ = [('chunk_steps', C.c_int32), ('traj_every', C.c_int32)]
+
+
 class FdsrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f'libfdsr_hip error {code}: {msg}')
@@ -70,6 +74,8 @@ SYMBOLS = {
                                     C.c_size_t, C.c_void_p]),
     'fdsr_sample': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_int]),
+    'fdsr_sample_stepwise': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.POINTER(FdsrSampleOpts)]),
     'fdsr_set_precision': (C.c_int, [C.c_void_p, C.c_int]),
     'fdsr_set_seed': (C.c_int, [C.c_void_p, C.c_uint64]),
     'fdsr_debug_tensor_elem_bytes': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p]),

@@ -1374,6 +1374,89 @@ int sample_body(fdsr_handle h, const float* cond, const float* noise, float* out
   return FDSR_OK;
 }
 
+// ---- fdsr_sample_stepwise: the same loop with its per-step inputs on the device ------------------------------------------
+void destroy_step_graph(const StepGraphEntry& g) {
+  for (hipGraphExec_t x : {g.head, g.body, g.rem})
+    if (x) (void)hipGraphExecDestroy(x);
+}
+
+void drop_step_graphs(fdsr_handle h) {
+  for (auto& g : h->step_graphs) destroy_step_graph(g);
+  h->step_graphs.clear();
+}
+
+StepRecord* step_rec(fdsr_handle h) { return reinterpret_cast<StepRecord*>(reinterpret_cast<char*>(h->d_step_ctl) + 256); }
+
+int ensure_step_state(fdsr_handle h) {
+  if (!h->d_step_ctl) {
+    HIPCHK(h, hipMalloc(&h->d_step_ctl, 256 + sizeof(StepRecord)));
+    HIPCHK(h, hipMemset(h->d_step_ctl, 0, 256 + sizeof(StepRecord)));
+    HIPCHK(h, hipMalloc(&h->d_step_row, (size_t)h->TE * sizeof(float)));
+  }
+  if (h->step_sched_valid && h->step_sched_T == h->T) return FDSR_OK;
+  if (h->d_step_sched) { (void)hipFree(h->d_step_sched); h->d_step_sched = nullptr; }
+  HIPCHK(h, hipMalloc(&h->d_step_sched, (size_t)5 * h->T * sizeof(float)));
+  std::vector<float> s;
+  s.reserve((size_t)5 * h->T);
+  for (const auto* v : {&h->s_recip, &h->s_recipm1, &h->s_c1, &h->s_c2, &h->s_sigma}) s.insert(s.end(), v->begin(), v->end());
+  HIPCHK(h, hipMemcpy(h->d_step_sched, s.data(), s.size() * sizeof(float), hipMemcpyHostToDevice));
+  h->step_sched_T = h->T;
+  h->step_sched_valid = true;
+  return FDSR_OK;
+}
+
+// everything before step 0: the packed input, the range flag, the call counter of the engine's noise, and k = 0
+int stepwise_head(fdsr_handle h, const float* cond, const float* noise, int N, int H, int W, char* ws, hipStream_t st) {
+  float* xin = reinterpret_cast<float*>(ws + h->plan.tensor_off[h->t_in]);
+  const int x_off = h->gdp ? 0 : 3, c_off = h->gdp ? 3 : 0;
+  if (h->prec == PREC_F16X3 && g_tun.sat_guard) HIPCHK(h, hipMemsetAsync(h->d_sat, 0, sizeof(int), st));
+  HIPCHK(h, launch_nchw_to_nhwc(cond, xin, N, 3, H, W, h->CP, c_off, 1, st));
+  if (noise) {
+    HIPCHK(h, launch_nchw_to_nhwc(noise, xin, N, 3, H, W, h->CP, x_off, 0, st));
+  } else {
+    HIPCHK(h, launch_rng_advance(h->d_rng, st));
+    HIPCHK(h, launch_randn_xin(h->d_rng, xin, N, H * W, h->CP, st, x_off));
+  }
+  HIPCHK(h, hipMemsetAsync(h->d_step_ctl, 0, sizeof(int), st));
+  return FDSR_OK;
+}
+
+// one reverse step k (whichever the counter holds): identical launches for every k
+int stepwise_step(fdsr_handle h, const float* noise, float* out, float* traj, int N, int H, int W, char* ws, hipStream_t st,
+                  int traj_every) {
+  StepPrologueParams sp{};
+  sp.counter = h->d_step_ctl;
+  sp.sched = h->d_step_sched;
+  sp.temb_table = h->d_temb_table;
+  sp.temb_row = h->d_step_row;
+  sp.rec = step_rec(h);
+  sp.T = h->T; sp.TE = h->TE; sp.traj_every = traj_every;
+  HIPCHK(h, launch_step_prologue(sp, st));
+  int rc = run_unet(h, N, H, W, ws, nullptr, 0.f, st, h->d_step_row);
+  if (rc) return rc;
+  PosteriorStepParams pp{};
+  pp.rec = step_rec(h);
+  pp.eps = reinterpret_cast<const float*>(ws + h->plan.tensor_off[h->t_eps]);
+  pp.xin = reinterpret_cast<float*>(ws + h->plan.tensor_off[h->t_in]);
+  pp.noise = noise;
+  pp.rng = noise ? nullptr : h->d_rng;
+  pp.traj = traj;
+  pp.out = out;
+  pp.N = N; pp.HW = H * W; pp.CP = h->CP;
+  pp.x_off = h->gdp ? 0 : 3; pp.x0_pred = h->gdp ? 1 : 0;
+  pp.plain_out = h->plain_out ? 1 : 0;
+  HIPCHK(h, launch_posterior_step(pp, st));
+  return FDSR_OK;
+}
+
+// default chunk: T itself up to 32 steps, else the largest divisor of T in [16, 32] (T = 1000 / 2000: 25), else 32 + a remainder
+int default_chunk(int T) {
+  if (T <= 32) return T;
+  for (int c = 32; c >= 16; --c)
+    if (T % c == 0) return c;
+  return 32;
+}
+
 }  // namespace fdsr_int
 
 // ---------------------------------------------------------------------------
@@ -1408,6 +1491,7 @@ int fdsr_create(const fdsr_config* cfg, fdsr_handle* out) {
 void fdsr_destroy(fdsr_handle h) {
   if (!h) return;
   for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
+  drop_step_graphs(h);
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
   if (h->d_params) (void)hipFree(h->d_params);
   if (h->d_wq) (void)hipFree(h->d_wq);
@@ -1416,6 +1500,8 @@ void fdsr_destroy(fdsr_handle h) {
   if (h->d_temb_table) (void)hipFree(h->d_temb_table);
   if (h->d_nl) (void)hipFree(h->d_nl);
   if (h->d_rng) (void)hipFree(h->d_rng);
+  for (void* q : {(void*)h->d_step_ctl, (void*)h->d_step_row, (void*)h->d_step_sched})
+    if (q) (void)hipFree(q);
   if (h->d_wtq) (void)hipFree(h->d_wtq);
   if (h->d_hamax) (void)hipFree(h->d_hamax);
   if (h->d_copy_tab) (void)hipFree(h->d_copy_tab);
@@ -1477,6 +1563,7 @@ int fdsr_load_weight(fdsr_handle h, const char* key, const float* host, const in
   h->temb_table_valid = false;
   for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);   // weights are baked by address only, but be safe
   h->graphs.clear();
+  drop_step_graphs(h);
   return FDSR_OK;
 }
 
@@ -1495,8 +1582,10 @@ int fdsr_set_schedule(fdsr_handle h, const fdsr_schedule* s) {
   cp(h->s_nl, s->noise_level); cp(h->s_recip, s->sqrt_recip); cp(h->s_recipm1, s->sqrt_recipm1);
   cp(h->s_c1, s->coef1); cp(h->s_c2, s->coef2); cp(h->s_sigma, s->sigma);
   h->temb_table_valid = false;
+  h->step_sched_valid = false;
   for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
   h->graphs.clear();
+  drop_step_graphs(h);
   return FDSR_OK;
 }
 
@@ -1572,6 +1661,88 @@ int fdsr_sample(fdsr_handle h, const float* cond_nchw, const float* noise, float
   if (h->graphs.size() >= 8) { (void)hipGraphExecDestroy(h->graphs.front().exec); h->graphs.erase(h->graphs.begin()); }
   h->graphs.push_back(ge);
   HIPCHK(h, hipGraphLaunch(ge.exec, st));
+  return FDSR_OK;
+}
+
+int fdsr_sample_stepwise(fdsr_handle h, const float* cond_nchw, const float* noise, float* out_nchw, float* traj_nchw, int batch,
+                         int height, int width, void* workspace, size_t workspace_bytes, void* hip_stream, int flags,
+                         const fdsr_sample_opts* opts) {
+  if (!h || !cond_nchw || !out_nchw) return fail(h, FDSR_E_INVALID, "null argument");
+  if (h->cfg.in_channel != 6 || h->cfg.out_channel != 3)
+    return fail(h, FDSR_E_INVALID, "conditional sampling needs in_channel=6, out_channel=3");
+  const int chunk_opt = opts ? opts->chunk_steps : 0, every = opts ? opts->traj_every : 1;
+  if (chunk_opt < 0 || every < 1) return fail(h, FDSR_E_INVALID, "fdsr_sample_opts: chunk_steps >= 0 and traj_every >= 1");
+  if (g_tun.bf16_f16x3_steps != 0)
+    return fail(h, FDSR_E_INVALID, "fdsr_sample_stepwise: the bf16_f16x3_steps probe makes the precision step-dependent; use fdsr_sample");
+  int rc = check_ready(h, true);
+  if (rc) return rc;
+  if ((rc = get_plan(h, batch, height, width))) return rc;
+  if ((rc = check_ws(h, workspace, workspace_bytes))) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  char* ws = reinterpret_cast<char*>(workspace);
+  if (h->prec != PREC_F32 && h->h_forms_stale && (rc = fdsr_sync_weight_forms(h))) return rc;
+  if ((rc = ensure_temb_table(h, st))) return rc;
+  if ((rc = ensure_step_state(h))) return rc;
+  if (!noise && (rc = ensure_rng(h))) return rc;
+  if ((flags & FDSR_SAMPLE_GRAPH) && st == nullptr)
+    return fail(h, FDSR_E_INVALID, "FDSR_SAMPLE_GRAPH needs a non-default stream (stream capture cannot run on the NULL stream)");
+  const bool use_graph = (flags & FDSR_SAMPLE_GRAPH) && !h->profiling;
+  if (use_graph && h->training && h->n_drop_slots > 0)   // a replayed chunk would repeat its dropout masks
+    return fail(h, FDSR_E_INVALID, "fdsr_sample_stepwise: FDSR_SAMPLE_GRAPH with live dropout (train mode); sample eagerly");
+  const int T = h->T;
+  if (!use_graph) {
+    if ((rc = stepwise_head(h, cond_nchw, noise, batch, height, width, ws, st))) return rc;
+    for (int k = 0; k < T; ++k) {
+      h->prof_step = (k % 4) == 0;
+      rc = stepwise_step(h, noise, out_nchw, traj_nchw, batch, height, width, ws, st, every);
+      if (rc) break;
+    }
+    h->prof_step = true;
+    return rc;
+  }
+
+  const int chunk = chunk_opt > 0 ? std::min(chunk_opt, T) : default_chunk(T);
+  if (h->step_graphs_epoch != g_tun.epoch) {   // graphs captured under other launcher options
+    drop_step_graphs(h);
+    h->step_graphs_epoch = g_tun.epoch;
+  }
+  const StepGraphEntry* hit = nullptr;
+  for (auto& g : h->step_graphs)
+    if (g.cond == cond_nchw && g.noise == noise && g.out == out_nchw && g.traj == traj_nchw && g.ws == workspace &&
+        g.temb_table == h->d_temb_table && g.sched == h->d_step_sched && g.N == batch && g.H == height && g.W == width &&
+        g.chunk == chunk && g.every == every)
+      hit = &g;
+  if (!hit) {
+    // three single-stream captures: head, `chunk` steps, T % chunk steps
+    StepGraphEntry ge{cond_nchw, noise, out_nchw, traj_nchw, workspace, h->d_temb_table, h->d_step_sched,
+                      batch, height, width, chunk, every, nullptr, nullptr, nullptr};
+    auto capture = [&](int steps, hipGraphExec_t* exec) -> int {
+      hipGraph_t graph = nullptr;
+      HIPCHK(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+      int r = steps < 0 ? stepwise_head(h, cond_nchw, noise, batch, height, width, ws, st) : FDSR_OK;
+      for (int k = 0; k < steps && !r; ++k) r = stepwise_step(h, noise, out_nchw, traj_nchw, batch, height, width, ws, st, every);
+      hipError_t e = hipStreamEndCapture(st, &graph);
+      if (r) { if (graph) (void)hipGraphDestroy(graph); return r; }
+      if (e != hipSuccess) return fail(h, FDSR_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+      e = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+      (void)hipGraphDestroy(graph);
+      if (e != hipSuccess) return fail(h, FDSR_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
+      return FDSR_OK;
+    };
+    rc = capture(-1, &ge.head);
+    if (!rc) rc = capture(chunk, &ge.body);
+    if (!rc && T % chunk) rc = capture(T % chunk, &ge.rem);
+    if (rc) { destroy_step_graph(ge); return rc; }
+    if (h->step_graphs.size() >= 8) {
+      destroy_step_graph(h->step_graphs.front());
+      h->step_graphs.erase(h->step_graphs.begin());
+    }
+    h->step_graphs.push_back(ge);
+    hit = &h->step_graphs.back();
+  }
+  HIPCHK(h, hipGraphLaunch(hit->head, st));
+  for (int c = 0; c < T / chunk; ++c) HIPCHK(h, hipGraphLaunch(hit->body, st));
+  if (hit->rem) HIPCHK(h, hipGraphLaunch(hit->rem, st));
   return FDSR_OK;
 }
 
@@ -1720,6 +1891,7 @@ int fdsr_set_precision(fdsr_handle h, int mode) {
   if (h->prec != mode) {
     for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
     h->graphs.clear();
+    drop_step_graphs(h);
   }
   h->prec = mode;
   return FDSR_OK;

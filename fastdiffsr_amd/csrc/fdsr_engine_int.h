@@ -96,6 +96,15 @@ struct GraphEntry {
   hipGraphExec_t exec;
 };
 
+// fdsr_sample_stepwise under FDSR_SAMPLE_GRAPH: the prologue, one chunk of `chunk` steps and the T % chunk remainder
+struct StepGraphEntry {
+  const void *cond, *noise, *out, *traj, *ws, *temb_table, *sched;
+  int N, H, W, chunk, every;
+  hipGraphExec_t head, body, rem;   // rem: null when chunk divides T
+};
+
+void drop_step_graphs(fdsr_handle h);   // destroys the captured fdsr_sample_stepwise graphs
+
 }  // namespace fdsr_int
 
 using namespace fdsr_int;
@@ -151,6 +160,14 @@ struct fdsr_engine {
   double prof_flops = 0, prof_bytes = 0;
   std::vector<GraphEntry> graphs;
   unsigned graphs_epoch = 0;
+  // fdsr_sample_stepwise: device-resident step state, allocated on first use (not part of the workspace)
+  int* d_step_ctl = nullptr;        // step counter, then (256 bytes on) the current StepRecord
+  float* d_step_row = nullptr;      // [TE]: the current step's noise-embedding row
+  float* d_step_sched = nullptr;    // [5][T]: device copy of the posterior scalars
+  int step_sched_T = 0;
+  bool step_sched_valid = false;
+  std::vector<StepGraphEntry> step_graphs;
+  unsigned step_graphs_epoch = 0;
   // ---- training state (fdsr_train.cpp) ----
   float* d_master = nullptr;          // every live checkpoint tensor in checkpoint layout, concatenated in schema order
   std::vector<size_t> master_off;     // per weight entry: float offset into d_master (SIZE_MAX: dead / synthetic)

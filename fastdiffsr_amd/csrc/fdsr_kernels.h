@@ -300,6 +300,38 @@ struct PosteriorParams {
 };
 hipError_t launch_posterior(const PosteriorParams& p, hipStream_t s);
 
+// Device-resident step state of fdsr_sample_stepwise: every step launches the same kernels with the same arguments, so a
+// captured chunk of steps replays for any k.  The step prologue reads the counter k, fills the record of step t = T-1-k and
+// the current noise-embedding row, then advances the counter; the posterior below reads the record instead of kernel arguments.
+struct StepRecord {
+  float c_recip, c_recipm1, coef1, coef2, sigma;
+  int rng_plane;     // k + 1
+  int noise_plane;   // k + 1, or -1 at t == 0 (no noise)
+  int traj_slot;     // index of t among {t : t % traj_every == 0} in descending order, or -1
+  int is_last;       // t == 0: write out
+};
+struct StepPrologueParams {
+  int* counter;                 // k (reset to 0 by the sampling prologue)
+  const float* sched;           // [5][T]: sqrt_recip, sqrt_recipm1, coef1, coef2, sigma
+  const float* temb_table;      // [T][TE]
+  float* temb_row;              // [TE]: row t of temb_table
+  StepRecord* rec;
+  int T, TE, traj_every;
+};
+hipError_t launch_step_prologue(const StepPrologueParams& p, hipStream_t s);
+struct PosteriorStepParams {
+  const StepRecord* rec;
+  const float* eps;
+  float* xin;
+  const float* noise;           // [planes][N,3,H,W] base, or null (engine RNG)
+  const unsigned long long* rng;   // or null (explicit noise)
+  float* traj;                  // [slots][N,3,H,W] base, or null
+  float* out;
+  int N, HW, CP;
+  int plain_out, x_off, x0_pred;
+};
+hipError_t launch_posterior_step(const PosteriorStepParams& p, hipStream_t s);
+
 // Engine-side noise (fdsr_sample with noise == NULL): counter-based Philox4x32-10 + Box-Muller, keyed by
 // (seed, call counter) and indexed by (plane, pixel): the values do not depend on the launch geometry.
 hipError_t launch_rng_advance(unsigned long long* rng, hipStream_t s);                      // ++call counter

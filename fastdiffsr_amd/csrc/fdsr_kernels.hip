@@ -961,37 +961,102 @@ hipError_t launch_randn_xin(const unsigned long long* rng, float* xin, int N, in
 // ---------------------------------------------------------------------------
 // reverse-diffusion update                                   (diffusion.py:157-190)
 // ---------------------------------------------------------------------------
+// one pixel of one step; both posterior kernels below run exactly this arithmetic
+__device__ __forceinline__ void posterior_pixel(size_t i, int HW, int CP, const float* eps, float* xin,
+                                                const float* noise, const unsigned long long* rng, int rng_plane, float* traj,
+                                                float* out, float c_recip, float c_recipm1, float coef1, float coef2, float sigma,
+                                                int plain_out, int x_off, int x0_pred) {
+  const size_t n = i / HW, pix = i % HW;
+  float* xs = xin + i * CP;
+  float z[3] = {0.f, 0.f, 0.f};
+  if (rng) randn3(rng, rng_plane, i, z);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float x = xs[x_off + c];
+    const float e = eps[i * 3 + c];
+    // two separately rounded products, then subtract (SURVEY H4): no fma contraction
+    const float a = __fmul_rn(c_recip, x);
+    const float b = __fmul_rn(c_recipm1, e);
+    float x0 = x0_pred ? e : __fsub_rn(a, b);                                 // GDP: the network output IS x_0
+    x0 = fminf(fmaxf(x0, -1.f), 1.f);                                        // clamp_(-1, 1)  :178-179
+    const float mean = __fadd_rn(__fmul_rn(coef1, x0), __fmul_rn(coef2, x));   // :161-165
+    float xn = mean;
+    const size_t o = (n * 3 + c) * HW + pix;
+    if (noise) xn = __fadd_rn(mean, __fmul_rn(noise[o], sigma));             // :189-190
+    else if (rng) xn = __fadd_rn(mean, __fmul_rn(z[c], sigma));
+    xs[x_off + c] = xn;
+    if (traj) traj[o] = xn;
+    if (out) out[o] = plain_out ? xn : fminf(fmaxf(xn, -1.f), 1.f) / 2.0f + xs[(x_off ? 0 : 3) + c];   // res2img :275-281 (SR3: the image itself)
+  }
+}
+
 __global__ void __launch_bounds__(256) posterior_kernel(const PosteriorParams p) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   const size_t total = (size_t)p.N * p.HW;
   if (i >= total) return;
-  const size_t n = i / p.HW, pix = i % p.HW;
-  float* xs = p.xin + i * p.CP;
-  float z[3] = {0.f, 0.f, 0.f};
-  if (p.rng) randn3(p.rng, p.rng_plane, i, z);
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float x = xs[p.x_off + c];
-    const float e = p.eps[i * 3 + c];
-    // two separately rounded products, then subtract (SURVEY H4): no fma contraction
-    const float a = __fmul_rn(p.c_recip, x);
-    const float b = __fmul_rn(p.c_recipm1, e);
-    float x0 = p.x0_pred ? e : __fsub_rn(a, b);                               // GDP: the network output IS x_0
-    x0 = fminf(fmaxf(x0, -1.f), 1.f);                                        // clamp_(-1, 1)  :178-179
-    const float mean = __fadd_rn(__fmul_rn(p.coef1, x0), __fmul_rn(p.coef2, x));   // :161-165
-    float xn = mean;
-    const size_t o = (n * 3 + c) * p.HW + pix;
-    if (p.noise) xn = __fadd_rn(mean, __fmul_rn(p.noise[o], p.sigma));       // :189-190
-    else if (p.rng) xn = __fadd_rn(mean, __fmul_rn(z[c], p.sigma));
-    xs[p.x_off + c] = xn;
-    if (p.traj) p.traj[o] = xn;
-    if (p.out) p.out[o] = p.plain_out ? xn : fminf(fmaxf(xn, -1.f), 1.f) / 2.0f + xs[(p.x_off ? 0 : 3) + c];   // res2img :275-281 (SR3: the image itself)
-  }
+  posterior_pixel(i, p.HW, p.CP, p.eps, p.xin, p.noise, p.rng, p.rng_plane, p.traj, p.out, p.c_recip, p.c_recipm1, p.coef1, p.coef2,
+                  p.sigma, p.plain_out, p.x_off, p.x0_pred);
 }
 
 hipError_t launch_posterior(const PosteriorParams& p, hipStream_t s) {
   const size_t total = (size_t)p.N * p.HW;
   hipLaunchKernelGGL(posterior_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// device-resident step state (fdsr_sample_stepwise)
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) step_prologue_kernel(const StepPrologueParams p) {
+  __shared__ int sk;
+  if (threadIdx.x == 0) sk = *p.counter;
+  __syncthreads();
+  // the host resets the counter before step 0 and launches exactly T steps; the clamp only keeps a misuse inside the tables
+  const int k = min(max(sk, 0), p.T - 1);
+  const int t = p.T - 1 - k;
+  const float* row = p.temb_table + (size_t)t * p.TE;
+  for (int j = threadIdx.x; j < p.TE; j += 256) p.temb_row[j] = row[j];
+  if (threadIdx.x == 0) {
+    StepRecord r;
+    r.c_recip = p.sched[t];
+    r.c_recipm1 = p.sched[p.T + t];
+    r.coef1 = p.sched[2 * p.T + t];
+    r.coef2 = p.sched[3 * p.T + t];
+    r.sigma = p.sched[4 * p.T + t];
+    r.rng_plane = k + 1;
+    r.noise_plane = t > 0 ? k + 1 : -1;
+    // slots hold t = T-1, T-2, ... that are multiples of traj_every: t's slot counts the multiples above it
+    r.traj_slot = (t % p.traj_every == 0) ? (p.T - 1) / p.traj_every - t / p.traj_every : -1;
+    r.is_last = t == 0 ? 1 : 0;
+    *p.rec = r;
+  }
+  __syncthreads();   // every read of the counter is done before it moves
+  if (threadIdx.x == 0) *p.counter = sk + 1;
+}
+
+hipError_t launch_step_prologue(const StepPrologueParams& p, hipStream_t s) {
+  if (p.T < 1 || p.TE < 1 || p.traj_every < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(step_prologue_kernel, dim3(1), dim3(256), 0, s, p);
+  return hipGetLastError();
+}
+
+__global__ void __launch_bounds__(256) posterior_step_kernel(const PosteriorStepParams p) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t total = (size_t)p.N * p.HW;
+  if (i >= total) return;
+  const StepRecord r = *p.rec;
+  const size_t img = total * 3;
+  const float* noise = (p.noise && r.noise_plane >= 0) ? p.noise + (size_t)r.noise_plane * img : nullptr;
+  const unsigned long long* rng = (!p.noise && r.noise_plane >= 0) ? p.rng : nullptr;
+  float* traj = (p.traj && r.traj_slot >= 0) ? p.traj + (size_t)r.traj_slot * img : nullptr;
+  float* out = r.is_last ? p.out : nullptr;
+  posterior_pixel(i, p.HW, p.CP, p.eps, p.xin, noise, rng, r.rng_plane, traj, out, r.c_recip, r.c_recipm1, r.coef1, r.coef2, r.sigma,
+                  p.plain_out, p.x_off, p.x0_pred);
+}
+
+hipError_t launch_posterior_step(const PosteriorStepParams& p, hipStream_t s) {
+  const size_t total = (size_t)p.N * p.HW;
+  hipLaunchKernelGGL(posterior_step_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 

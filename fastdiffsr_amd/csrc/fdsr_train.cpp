@@ -684,6 +684,7 @@ int fdsr_adam_step(fdsr_handle h, float lr, float beta1, float beta2, float eps,
   h->h_forms_stale = true;
   for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
   h->graphs.clear();
+  drop_step_graphs(h);
   return FDSR_OK;
 }
 

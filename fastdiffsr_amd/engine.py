@@ -177,12 +177,21 @@ class Engine:
             raise _lib.FdsrSaturated(rc, self.lib.fdsr_last_error(self.h).decode())
         _lib.check(self.h, rc)
 
-    def sample(self, cond, noise=None, want_traj=False, graph=False, out=None, traj=None):
+    def sample(self, cond, noise=None, want_traj=False, graph=False, out=None, traj=None, stepwise=False, traj_every=1, chunk=0):
         """noise: [T,B,3,H,W] (parity runs: the reference's draws), or None: the engine draws
-        inside the loop (Philox, see set_seed) like the reference's in-loop randn_like."""
-        return self._with_range_fallback(lambda: self._sample(cond, noise, want_traj, graph, out, traj))
+        inside the loop (Philox, see set_seed) like the reference's in-loop randn_like.
+        stepwise: fdsr_sample_stepwise (long schedules: the per-step inputs live on the device, a graph
+        replays a chunk of `chunk` steps, 0 = the library's default); the trajectory then holds the
+        traj_slots(traj_every) frames of t % traj_every == 0, t descending."""
+        return self._with_range_fallback(lambda: self._sample(cond, noise, want_traj, graph, out, traj, stepwise, traj_every, chunk))
 
-    def _sample(self, cond, noise, want_traj, graph, out, traj):
+    def traj_slots(self, traj_every=1):
+        """Frames a stepwise trajectory holds: the t in [0, T) with t % traj_every == 0."""
+        return (self.T - 1) // int(traj_every) + 1
+
+    def _sample(self, cond, noise, want_traj, graph, out, traj, stepwise=False, traj_every=1, chunk=0):
+        if not stepwise and (traj_every != 1 or chunk):
+            raise ValueError('traj_every / chunk apply to the stepwise entry point only (stepwise=True)')
         cond = self._check_input(cond, 'cond')
         B, _, H, W = cond.shape
         if noise is not None:
@@ -193,23 +202,31 @@ class Engine:
         ws = self._workspace(B, H, W, cond.device)
         if out is None:
             out = torch.empty(B, 3, H, W, device=cond.device, dtype=torch.float32)
+        n_traj = self.traj_slots(traj_every) if stepwise else self.T
         if want_traj and traj is None:
-            traj = torch.empty(self.T, B, 3, H, W, device=cond.device, dtype=torch.float32)
+            traj = torch.empty(n_traj, B, 3, H, W, device=cond.device, dtype=torch.float32)
+        if stepwise and want_traj and tuple(traj.shape) != (n_traj, B, 3, H, W):
+            raise ValueError(f'traj must be [{n_traj},{B},3,{H},{W}], got {tuple(traj.shape)}')
         cur = torch.cuda.current_stream(cond.device)
         flags = _lib.FDSR_SAMPLE_GRAPH if graph else 0
         args = (self.h, _ptr(cond), _ptr(noise), _ptr(out), _ptr(traj if want_traj else None), B, H, W, _ptr(ws), ws.numel())
+        if stepwise:
+            opts = _lib.FdsrSampleOpts(int(chunk), int(traj_every))
+            entry = lambda *a: self.lib.fdsr_sample_stepwise(*a, C.byref(opts))   # noqa: E731
+        else:
+            entry = self.lib.fdsr_sample
         if graph and cur.cuda_stream == 0:
             # stream capture cannot run on the NULL stream: replay on a stream of our own, ordered after and
             # before the caller's current stream
             if self._gstream is None or self._gstream.device != cond.device:
                 self._gstream = torch.cuda.Stream(cond.device)
             self._gstream.wait_stream(cur)
-            _lib.check(self.h, self.lib.fdsr_sample(*args, C.c_void_p(self._gstream.cuda_stream), flags))
+            _lib.check(self.h, entry(*args, C.c_void_p(self._gstream.cuda_stream), flags))
             cur.wait_stream(self._gstream)
             self._keep = (cond, noise, out, traj)
             self._saturation_check(self._gstream.cuda_stream)
         else:
-            _lib.check(self.h, self.lib.fdsr_sample(*args, C.c_void_p(cur.cuda_stream), flags))
+            _lib.check(self.h, entry(*args, C.c_void_p(cur.cuda_stream), flags))
             self._keep = (cond, noise, out, traj)
             self._saturation_check(cur.cuda_stream)
         return (out, traj) if want_traj else out

@@ -5,6 +5,7 @@ import torch
 from torch import nn
 
 from .. import diffusion as _d
+from ..long_schedule import frames_of, sample_stepwise, use_stepwise
 
 
 class GaussianDiffusion(_d.GaussianDiffusion):
@@ -25,10 +26,20 @@ class GaussianDiffusion(_d.GaussianDiffusion):
         device = self.betas.device
         x = x_in.to(device=device, dtype=torch.float32).contiguous()
         T = self.num_timesteps
-        if noise is None and getattr(self, 'rng', 'torch') != 'engine':
-            noise = torch.empty((T + 1,) + tuple(x.shape), device=device, dtype=torch.float32)
+        engine_rng = noise is None and getattr(self, 'rng', 'torch') == 'engine'
+
+        def draw(dst):
             for k in range(T + 1):                                # randn(shape) (:229), then noise_like per step (:206), all torch.randn
-                noise[k] = torch.randn(x.shape, device=device)
+                dst[k] = torch.randn(x.shape, device=device)
+        if use_stepwise(T):     # T > 50 (the reference's T = 1000): fastdiffsr_amd.long_schedule; self.graph as the flagship's
+            self.denoise_fn.sync_weights()
+            eng = self.denoise_fn.engine
+            eng.set_precision(self.precision)
+            res = sample_stepwise(self, eng, x, continous, None if engine_rng else draw, noise)   # Dropout: denoise_fn.training
+            return frames_of(x, res[1]) if continous else res[-1]
+        if noise is None and not engine_rng:
+            noise = torch.empty((T + 1,) + tuple(x.shape), device=device, dtype=torch.float32)
+            draw(noise)
         self.denoise_fn.sync_weights()
         eng = self.denoise_fn.engine
         eng.set_precision(self.precision)

@@ -3,6 +3,7 @@ HIP engine: discrete-time reverse process, the network sees the integer t, the o
 import torch
 from torch import nn
 
+from ..long_schedule import frames_of, sample_stepwise, use_stepwise
 from ..schedule import schedule_buffers, sampling_scalars
 
 
@@ -15,6 +16,15 @@ class GaussianDiffusion(nn.Module):
         self.loss_type = loss_type
         self.conditional = conditional
         self.precision = 'f16x3'
+        # sampling noise when the caller passes none: 'torch' = torch.randn in the reference's order (T+1 planes drawn up front:
+        # the memory cost of reproducing torch's stream), 'engine' = Philox inside the HIP loop (denoise_fn.engine.set_seed)
+        self.rng = 'torch'
+        # T > 50 (fastdiffsr_amd.long_schedule): the stepwise loop as captured chunks, with the flagship's meaning ('auto' from the
+        # second call of a shape on, 'on' from the first, 'off' never); schedules up to 50 steps keep their eager fdsr_sample call.
+        # Graph replays keep their per-shape buffers (with rng = 'torch' the [T+1,B,3,H,W] noise too) between calls:
+        # fastdiffsr_amd.long_schedule.release_buffers(self) frees them
+        self.graph = 'auto'
+        self._gbuf = {}
 
     def set_loss(self, device):                                   # :96-102
         if self.loss_type == 'l1':
@@ -38,10 +48,22 @@ class GaussianDiffusion(nn.Module):
         device = self.betas.device
         x = x_in.to(device=device, dtype=torch.float32).contiguous()
         T = self.num_timesteps
-        if noise is None:   # randn(shape), then one noise_like draw per step, t = 0 included (:189-196, :215)
-            noise = torch.empty((T + 1,) + tuple(x.shape), device=device, dtype=torch.float32)
+        engine_rng = noise is None and getattr(self, 'rng', 'torch') == 'engine'
+
+        def draw(dst):      # randn(shape), then one noise_like draw per step, t = 0 included (:189-196, :215)
             for k in range(T + 1):
-                noise[k] = torch.randn(x.shape, device=device)
+                dst[k] = torch.randn(x.shape, device=device)
+        if use_stepwise(T):
+            self.denoise_fn.sync_weights()
+            eng = self.denoise_fn.engine
+            eng.set_precision(self.precision)
+            res = sample_stepwise(self, eng, x, continous, None if engine_rng else draw, noise)
+            if not continous:
+                return res[-1] if res.shape[0] == 1 else res
+            return frames_of(x, res[1])
+        if noise is None and not engine_rng:
+            noise = torch.empty((T + 1,) + tuple(x.shape), device=device, dtype=torch.float32)
+            draw(noise)
         self.denoise_fn.sync_weights()
         eng = self.denoise_fn.engine
         eng.set_precision(self.precision)

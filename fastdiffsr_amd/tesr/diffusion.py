@@ -7,6 +7,7 @@ import torch
 from torch import nn
 
 from .. import diffusion as _d
+from ..long_schedule import frames_of, sample_stepwise, use_stepwise
 
 
 class CharbonnierLoss(nn.Module):                                 # tesr_modules/unet.py:956-967
@@ -58,11 +59,21 @@ class GaussianDiffusion(_d.GaussianDiffusion):
         device = self.betas.device
         x = x_in.to(device=device, dtype=torch.float32).contiguous()
         T = self.num_timesteps
-        if noise is None and getattr(self, 'rng', 'torch') != 'engine':
-            noise = torch.empty((T,) + tuple(x.shape), device=device, dtype=torch.float32)
-            noise[0] = torch.randn(x.shape, device=device)        # :196
+        engine_rng = noise is None and getattr(self, 'rng', 'torch') == 'engine'
+
+        def draw(dst):
+            dst[0] = torch.randn(x.shape, device=device)          # :196
             for k in range(1, T):
-                noise[k] = torch.randn_like(x)                    # :180, t > 0
+                dst[k] = torch.randn_like(x)                      # :180, t > 0
+        if use_stepwise(T):     # T > 50 (the reference's T = 2000): fastdiffsr_amd.long_schedule; self.graph as the flagship's
+            self.denoise_fn.sync_weights()
+            eng = self.denoise_fn.engine
+            eng.set_precision(self.precision)
+            res = sample_stepwise(self, eng, x, continous, None if engine_rng else draw, noise)
+            return frames_of(x, res[1]) if continous else res[-1]
+        if noise is None and not engine_rng:
+            noise = torch.empty((T,) + tuple(x.shape), device=device, dtype=torch.float32)
+            draw(noise)
         self.denoise_fn.sync_weights()
         eng = self.denoise_fn.engine
         eng.set_precision(self.precision)

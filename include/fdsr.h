@@ -140,6 +140,37 @@ int fdsr_sample(fdsr_handle h, const float* cond_nchw, const float* noise,
                 float* out_nchw, float* traj_nchw, int batch, int height, int width,
                 void* workspace, size_t workspace_bytes, void* hip_stream, int flags);
 
+/* Long schedules (the siblings' own T = 1000 / 2000): fdsr_sample with the per-step inputs on the device.
+ * A small step-prologue kernel before every step reads a step counter held by the handle, copies the
+ * noise-embedding row and the posterior scalars of t = T-1-k into handle-owned buffers and advances the
+ * counter; so every step launches the same kernels with the same arguments.  Same arithmetic as
+ * fdsr_sample: out and the frames it keeps are bitwise equal to fdsr_sample's.
+ *   cond_nchw, noise, out_nchw  as fdsr_sample (the noise layout is unchanged: [T+1,...] for SR3 / GDP,
+ *                              [T,...] otherwise, or NULL for the engine's own draws)
+ *   traj_nchw [S,B,3,H,W] or NULL, S = ceil(T / traj_every) = the number of t in [0, T) with
+ *                              t % traj_every == 0: x_t after those steps, t descending
+ *                              (traj_every = 1 is fdsr_sample's full trajectory; the reference's
+ *                              continous=True keeps traj_every = 1 | (T / 10))
+ *   opts                       NULL = {0, 1}; chunk_steps: steps per captured graph (0: the library's
+ *                              default, at most 32 and a divisor of T where one lies in [16, 32])
+ * flags: FDSR_SAMPLE_GRAPH captures three graphs -- the prologue (input packing, counter reset), one chunk of
+ *        chunk_steps steps and, when chunk_steps does not divide T, the remainder -- and replays the chunk
+ *        T / chunk_steps times, so the graph size is O(chunk_steps), not O(T).  The cache rules are
+ *        fdsr_sample's (key: pointers, shape and opts; at most 8 entries; dropped on a weight, schedule or
+ *        precision change).  Refused (FDSR_E_INVALID) with live dropout (fdsr_set_training) and under the
+ *        bf16_f16x3_steps debug option, whose precision depends on the step.
+ * Memory: beyond the workspace (fdsr_workspace_bytes is unchanged) the handle keeps 5*T + TE floats and
+ *        a few bytes of step state.  The step counter is handle state: calls on one handle must be ordered
+ *        on one stream, which is the handle's contract anyway. */
+typedef struct fdsr_sample_opts {
+  int32_t chunk_steps;   /* 0: library default */
+  int32_t traj_every;    /* >= 1 */
+} fdsr_sample_opts;
+int fdsr_sample_stepwise(fdsr_handle h, const float* cond_nchw, const float* noise,
+                         float* out_nchw, float* traj_nchw, int batch, int height, int width,
+                         void* workspace, size_t workspace_bytes, void* hip_stream, int flags,
+                         const fdsr_sample_opts* opts);
+
 /* Seed of the engine-side noise (resets the per-call counter): the same seed and call order give
  * the same images, whatever the batch split or launch geometry.  The reference draws from torch's
  * global generator (diffusion.py:189, :207); its stream is not reproduced, so parity is defined on
