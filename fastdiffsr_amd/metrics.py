@@ -5,10 +5,14 @@ fp32 copy `DDPM.get_current_visuals` makes, model/model.py:97-111).
 tensor2img and PSNR are pinned by goldens generated from the reference's own functions
 (tests/golden/metrics.npz).  SSIM / ERGAS follow the reference formulas (metrics.py:103-152) but the
 reference needs cv2 / skimage to run them, which this image lacks: those two are unpinned.
-LPIPS (AlexNet weights) is out of scope.
+LPIPS (AlexNet, v0.1 heads; calculate_lpips, metrics.py:154-163) runs on the device from the user's own weight files
+(class LPIPS below, csrc/fdsr_lpips.hip); it is pinned by tests/golden/lpips_alex.npz, made by the reference's own
+calculate_lpips on a synthetic backbone (synth.synth_alexnet_features) and the real v0.1 heads.
 """
 import ctypes as C
 import math
+import os
+from collections import OrderedDict
 
 import numpy as np
 import torch
@@ -203,3 +207,121 @@ def compare_ssim(X, Y, multichannel=True, win_size=7):
     S = ((2 * ux * uy + C1) * (2 * vxy + C2)) / ((ux ** 2 + uy ** 2 + C1) * (vx + vy + C2))
     pad = (win_size - 1) // 2
     return float(S[pad:-pad, pad:-pad].mean())
+
+
+# --- LPIPS (core/metrics.py:154-163 calculate_lpips: lpips.LPIPS(net='alex'), the v0.1 linear heads), on the device --------
+LPIPS_BACKBONE = OrderedDict([('features.0.weight', (64, 3, 11, 11)), ('features.0.bias', (64,)),
+                              ('features.3.weight', (192, 64, 5, 5)), ('features.3.bias', (192,)),
+                              ('features.6.weight', (384, 192, 3, 3)), ('features.6.bias', (384,)),
+                              ('features.8.weight', (256, 384, 3, 3)), ('features.8.bias', (256,)),
+                              ('features.10.weight', (256, 256, 3, 3)), ('features.10.bias', (256,))])
+LPIPS_CHANNELS = (64, 192, 384, 256, 256)
+LPIPS_LIN = OrderedDict(('lin%d.model.1.weight' % k, (1, c, 1, 1)) for k, c in enumerate(LPIPS_CHANNELS))
+LPIPS_BACKBONE_FILE = 'alexnet-owt-7be5be79.pth'     # torchvision's ImageNet AlexNet, as its hub cache names it
+
+
+def _as_state_dict(src):
+    if isinstance(src, (str, os.PathLike)):
+        return torch.load(os.fspath(src), map_location='cpu', weights_only=True)
+    return src
+
+
+def lpips_state(backbone, lin):
+    """The 15 tensors fdsr_lpips_load takes, as float32 numpy arrays in load order, from a torchvision AlexNet state dict
+    (its `classifier.*` tensors are ignored) and an `lpips` v0.1 alex.pth state dict.  Any other name, a missing tensor or a
+    wrong shape raises KeyError / ValueError: nothing is guessed."""
+    out = OrderedDict()
+    for sd, table, ignore in ((backbone, LPIPS_BACKBONE, 'classifier.'), (lin, LPIPS_LIN, None)):
+        extra = [k for k in sd if k not in table and not (ignore and k.startswith(ignore))]
+        if extra:
+            raise KeyError('unexpected LPIPS tensor(s): %s' % ', '.join(sorted(extra)))
+        for k, shape in table.items():
+            if k not in sd:
+                raise KeyError('LPIPS tensor %r is missing' % k)
+            v = sd[k]
+            a = (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float32)
+            if tuple(a.shape) != shape:
+                raise ValueError('LPIPS tensor %r has shape %s, expected %s' % (k, tuple(a.shape), shape))
+            out[k] = np.ascontiguousarray(a)
+    return out
+
+
+class LPIPS:
+    """LPIPS (AlexNet, v0.1 heads) of uint8 images on the device (include/fdsr.h: fdsr_lpips_*), the reference's
+    calculate_lpips: the [0,1] ToTensor image goes into the network as it is (no normalize=True), so the values match the
+    reference's log, not `lpips` called with normalize=True.
+
+        lp = LPIPS(backbone, lin)          # two state dicts or two .pth paths (torch.load(weights_only=True))
+        lp = LPIPS(*LPIPS.default_paths())
+        out = lp.lpips_u8(truth, test_a, test_b=None)    # [n_tests, B, 6] fp64 CUDA: (LPIPS, per-layer terms 0..4)
+    """
+
+    def __init__(self, backbone, lin, device=None):
+        tensors = lpips_state(_as_state_dict(backbone), _as_state_dict(lin))
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(None, lib.fdsr_lpips_create(C.byref(h)))
+        self._h = h
+        with torch.cuda.device(self.device):
+            for k, a in tensors.items():
+                shape = (C.c_int64 * a.ndim)(*a.shape)
+                _lib.check(None, lib.fdsr_lpips_load(h, k.encode(), C.c_void_p(a.ctypes.data), shape, a.ndim))
+        self._ws = {}
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h is not None and _lib._lib is not None:
+            _lib._lib.fdsr_lpips_destroy(h)
+            self._h = None
+
+    @staticmethod
+    def default_paths():
+        """Where a user of the reference already has the two files (lpips.LPIPS(net='alex') reads them from there); nothing is
+        ever downloaded:  $TORCH_HOME/hub/checkpoints/alexnet-owt-7be5be79.pth (TORCH_HOME defaults to ~/.cache/torch) and the
+        `lpips` package's weights/v0.1/alex.pth (located with importlib, without importing the package)."""
+        import importlib.util
+        torch_home = os.path.expanduser(os.environ.get('TORCH_HOME', os.path.join('~', '.cache', 'torch')))
+        backbone = os.path.join(torch_home, 'hub', 'checkpoints', LPIPS_BACKBONE_FILE)
+        if not os.path.isfile(backbone):
+            raise FileNotFoundError('LPIPS backbone %s not found: put torchvision\'s ImageNet AlexNet weights (%s) there, or pass '
+                                    '--lpips-backbone PATH' % (backbone, LPIPS_BACKBONE_FILE))
+        spec = importlib.util.find_spec('lpips')
+        lin = None
+        if spec is not None and spec.submodule_search_locations:
+            for d in spec.submodule_search_locations:
+                cand = os.path.join(d, 'weights', 'v0.1', 'alex.pth')
+                if os.path.isfile(cand):
+                    lin = cand
+                    break
+        if lin is None:
+            raise FileNotFoundError('LPIPS heads lpips/weights/v0.1/alex.pth not found: install the `lpips` package (it ships the '
+                                    'file) or pass --lpips-lin PATH')
+        return backbone, lin
+
+    def workspace(self, b, h, w):
+        need = C.c_size_t()
+        _lib.check(None, _lib.load().fdsr_lpips_workspace_bytes(self._h, b, h, w, C.byref(need)))
+        key = (self.device, torch.cuda.current_stream(self.device).cuda_stream)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need.value:
+            ws = self._ws[key] = torch.empty(int(need.value), dtype=torch.uint8, device=self.device)
+        return ws
+
+    def lpips_u8(self, truth, test_a, test_b=None, out=None):
+        """[B,H,W,3] uint8 CUDA images -> [n_tests, B, 6] fp64 CUDA tensor (asynchronous on the current stream)."""
+        imgs = [truth, test_a] + ([test_b] if test_b is not None else [])
+        for t in imgs:
+            if (not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 4 or t.shape != truth.shape or t.shape[-1] != 3 or
+                    t.device != truth.device):
+                raise ValueError('lpips_u8 takes [B,H,W,3] uint8 CUDA tensors of one shape')
+        imgs = [t.contiguous() for t in imgs]
+        b, h, w, _ = truth.shape
+        ws = self.workspace(b, h, w)
+        if out is None:
+            out = torch.empty(len(imgs) - 1, b, 6, dtype=torch.float64, device=truth.device)
+        st = torch.cuda.current_stream(truth.device).cuda_stream
+        ptr = [C.c_void_p(t.data_ptr()) for t in imgs] + ([None] if test_b is None else [])
+        _lib.check(None, _lib.load().fdsr_lpips_u8(self._h, ptr[0], ptr[1], ptr[2], b, h, w, C.c_void_p(out.data_ptr()),
+                                                   C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(st)))
+        return out

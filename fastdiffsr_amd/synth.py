@@ -70,3 +70,19 @@ def synth_inputs(batch: int, height: int, width: int, steps: int = 20,
     g = torch.Generator().manual_seed(noise_seed)
     noise = torch.randn(steps, batch, 3, height, width, generator=g)
     return cond, noise
+
+
+def synth_alexnet_features(seed: int = 0) -> "OrderedDict[str, np.ndarray]":
+    """A stand-in for torchvision's ImageNet AlexNet `features` (the LPIPS backbone; no real copy is committed): the ten
+    torchvision-keyed tensors, float32, drawn in key order from numpy.random.default_rng(seed) -- weights He-normal
+    (std sqrt(2 / fan_in)), biases N(0, 0.05^2).  tests/golden/lpips_alex.npz records a per-tensor checksum of them."""
+    from .metrics import LPIPS_BACKBONE
+    g = np.random.default_rng(seed)
+    out = OrderedDict()
+    for k, shape in LPIPS_BACKBONE.items():
+        if k.endswith('.bias'):
+            x = g.normal(0.0, 0.05, size=shape)
+        else:
+            x = g.normal(0.0, np.sqrt(2.0 / int(np.prod(shape[1:]))), size=shape)
+        out[k] = x.astype(np.float32)
+    return out

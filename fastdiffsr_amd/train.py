@@ -6,7 +6,8 @@ FastDiffSR/sr_mfe.py:69-251) on the HIP engine:
 
 Same config files and dataset folders; per iteration `feed_data` + `optimize_parameters` (forward, loss / (b*c*h*w),
 backward and Adam in the engine), the `<epoch, iter> l_pix` log line every `print_freq`, a validation pass every
-`val_freq` (the val schedule, then back to the train schedule, sr_mfe.py:122-244) and `I{iter}_E{epoch}_{gen,opt}.pth`
+`val_freq` (the val schedule, then back to the train schedule, sr_mfe.py:122-244; with `--lpips` or `--lpips-backbone PATH
+--lpips-lin PATH` its log lines carry bic_lpips / sr_lpips, the LPIPS object built once per run) and `I{iter}_E{epoch}_{gen,opt}.pth`
 every `save_checkpoint_freq`.  tensorboard / wandb writers are not reproduced (the scalars go to the log).
 Under torch.distributed every rank takes its slice of each batch and the gradient arena is all-reduced: the global
 batch is the config's batch_size, as with the reference's nn.DataParallel (networks.py:116-118)."""
@@ -32,8 +33,9 @@ def loader_workers(num_workers):
     return max(2, min(int(num_workers or 0) or share, share))
 
 
-def run(opt, precision='f16x3', rank=0, world=1, log=print, val_batch=1, max_val_images=None, diffusion=None, ops=None):
-    """diffusion / ops: a ready model and the device side of the loaders (val.HipOps) -- injection points of the tests."""
+def run(opt, precision='f16x3', rank=0, world=1, log=print, val_batch=1, max_val_images=None, diffusion=None, ops=None, lpips=None):
+    """diffusion / ops: a ready model and the device side of the loaders (val.HipOps) -- injection points of the tests.
+    lpips: a metrics.LPIPS for the validation passes (their log lines then carry bic_lpips / sr_lpips, sr_mfe.py:230-235)."""
     train_opt = opt['datasets']['train']
     train_set = create_dataset(train_opt, 'train')
     # every rank draws the same batches (same shuffle seed) and keeps its own slice of each
@@ -93,7 +95,8 @@ def run(opt, precision='f16x3', rank=0, world=1, log=print, val_batch=1, max_val
             if current_step % opt['train']['val_freq'] == 0:
                 res = V.run(opt, batch=val_batch, precision=precision, results=(opt.get('path') or {}).get('results'),
                             max_images=max_val_images, rank=rank, world=world, save_images=rank == 0 or world > 1, log=log,
-                            diffusion=diffusion, step=current_step, epoch=current_epoch, ops=ops)
+                            diffusion=diffusion, step=current_step, epoch=current_epoch, ops=ops,
+                            lpips=lpips)
                 history.append((current_step, {'val_psnr': res['sr_psnr']}))
                 diffusion.set_new_noise_schedule(opt['model']['beta_schedule']['train'], schedule_phase='train')   # :233-234
             if current_step % opt['train']['save_checkpoint_freq'] == 0 and rank == 0:
@@ -113,6 +116,7 @@ def main(argv=None, diffusion=None, ops=None):
     ap.add_argument('-gpu', '--gpu_ids', default=None)
     ap.add_argument('-debug', '-d', action='store_true')
     ap.add_argument('--precision', default='f16x3', choices=['f32', 'f16x3'])
+    V.add_lpips_args(ap)
     a = ap.parse_args(argv)
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
     if world > 1:
@@ -125,7 +129,7 @@ def main(argv=None, diffusion=None, ops=None):
         tl = setup_logger(None, opt['path']['log'], 'train', screen=True)
         setup_logger('val', opt['path']['log'], 'val')
         log = logging.getLogger('base').info if tl is None else tl.info
-    out = run(opt, precision=a.precision, rank=rank, world=world, log=log, diffusion=diffusion, ops=ops)
+    out = run(opt, precision=a.precision, rank=rank, world=world, log=log, diffusion=diffusion, ops=ops, lpips=V.lpips_from_args(a))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

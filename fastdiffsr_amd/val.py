@@ -4,9 +4,14 @@ FastDiffSR/sr_mfe.py:257-378) on the HIP engine:
     python -m fastdiffsr_amd.val -c config/sr_fastdiffsr_test_64_256.json [--batch 16] [--cond-from-lr]
     python -m fastdiffsr_amd.val -c config/sr_fastdiffsr_infer_x4.json --infer        # infer.py
 
+    python -m fastdiffsr_amd.val -c ... --lpips-backbone alexnet-owt-7be5be79.pth --lpips-lin lpips/weights/v0.1/alex.pth
+
 Same config files, same dataset folders, same per-image metrics and log lines (MSE / PSNR / SSIM as
-skimage.measure computes them, ERGAS as core/metrics.py:147-152; LPIPS needs AlexNet weights and is left out),
-same `{results}/{step}_{idx}_sr.tif` outputs.  Differences, all opt-in or harmless:
+skimage.measure computes them, ERGAS as core/metrics.py:147-152), same `{results}/{step}_{idx}_sr.tif` outputs.
+LPIPS (core/metrics.py:154-163, AlexNet + the v0.1 heads) is the reference's fifth metric: it needs the user's own weight
+files and runs when asked for (`--lpips` looks where the reference's users have them, metrics.LPIPS.default_paths; or
+`--lpips-backbone PATH --lpips-lin PATH`); the two log lines then carry `bic_lpips` / `sr_lpips` as the reference's do.
+Differences, all opt-in or harmless:
   * `--batch N` samples N images per loop (the reference's val loader is batch 1 and its sampler crashes for
     more); every image is still its own independent chain
   * `continous=False`: the reference asks for the 8 intermediate frames and keeps only the last
@@ -121,6 +126,10 @@ class HipOps:
     tensor2img_batch = staticmethod(M.tensor2img_batch)   # core/metrics.py:16-42 on the device
     metric_sums = staticmethod(M.image_metric_sums)       # sr_mfe.py:313-345's per-pixel work on the device
 
+    def lpips(self, model, truth_u8, test_a_u8, test_b_u8):
+        """core/metrics.py:154-163 for both test images against one truth -> [2, B, 6] fp64 on the device (metrics.LPIPS)."""
+        return model.lpips_u8(truth_u8, test_a_u8, test_b_u8)
+
     def lr_to_sr(self, lr_u8, h, w):
         return lr_to_sr(lr_u8, h, w)
 
@@ -203,7 +212,7 @@ class _Loader:
 
 def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_images=None, rank=0, world=1,
         save_images=True, log=print, infer=False, diffusion=None, step=None, epoch=None, workers=None, rng=None, graph=None,
-        host_metrics=False, ops=None):
+        host_metrics=False, ops=None, lpips=None):
     """infer=True is the reference's infer.py (:62-110): the same loop, `{step}_{idx}_sr.png` outputs, timing, no metrics.
     diffusion: an existing model (the validation pass inside the training loop, sr_mfe.py:122-244); else one is created.
 
@@ -214,7 +223,9 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
     with metrics.compare_* instead (what the tests hold the device kernels against).
     rng: 'torch' (default; the reference's draws, reproducible under torch.manual_seed) or 'engine' (Philox inside the loop);
     graph: 'auto' | 'on' | 'off' -- replay the 20-step loop as a captured hipGraph (None: the model's default, 'auto').
-    ops: the device side (HipOps; see there)."""
+    ops: the device side (HipOps; see there).
+    lpips: a metrics.LPIPS, or None (the default: no LPIPS, the log lines and `res` exactly as without the feature).  With it
+    every image also gets bic_lpips / sr_lpips from the device (host_metrics included: there is no host LPIPS)."""
     import queue
     import sys
     import threading
@@ -242,7 +253,9 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
     if ops is None:
         ops = HipOps(diffusion.device)
     rres = int(val_opt['r_resolution'])
-    per_image = {}                     # index -> 8 numbers (bic mse/psnr/ssim/ergas, sr mse/psnr/ssim/ergas); summed in index order
+    use_lpips = lpips is not None and not infer
+    n_metric = 10 if use_lpips else 8
+    per_image = {}                     # index -> 8 numbers (bic mse/psnr/ssim/ergas, sr mse/psnr/ssim/ergas[, bic_lpips, sr_lpips]); summed in index order
     t_sample = 0.0
     # loader / writer threads of THIS rank: its share of the cores the job may use (affinity, cgroup quota, ranks on the host)
     n_workers = workers if workers else host_threads_per_rank(cap=8, floor=2)
@@ -261,7 +274,7 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
             if job is None:
                 return
             try:
-                ev, idxs, sr_host, sums_host, hr_host, inf_host, _ = job
+                ev, idxs, sr_host, sums_host, hr_host, inf_host, lp_host, _ = job
                 ev.synchronize()
                 sr_np = sr_host.numpy()
                 for j, index in enumerate(idxs):
@@ -282,6 +295,9 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
                         b_ = M.metrics_from_sums(sm[0, j], sr_np[j].shape, scale)
                         s_ = M.metrics_from_sums(sm[1, j], sr_np[j].shape, scale)
                         per_image[index] = [b_['mse'], b_['psnr'], b_['ssim'], b_['ergas'], s_['mse'], s_['psnr'], s_['ssim'], s_['ergas']]
+                    if lp_host is not None:
+                        lp = lp_host.numpy()
+                        per_image[index] += [float(lp[0, j, 0]), float(lp[1, j, 0])]     # sr_mfe.py:324, :345
             except Exception as e:       # surfaced by run() after the loop
                 errors.append(e)
             finally:
@@ -338,7 +354,7 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
             if slot_free[slot] is not None:
                 slot_free[slot].wait()           # the finisher is done with this slot's previous contents
             sr_host = ops.land('sr', slot, sr_u8)
-            sums_host = hr_host = inf_host = None
+            sums_host = hr_host = inf_host = lp_host = None
             if not infer:
                 hr_u8 = ops.tensor2img_batch(diffusion.data['HR'])
                 inf_u8 = ops.tensor2img_batch(diffusion.data['SR'])                   # the bicubic image ('INF')
@@ -349,9 +365,11 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
                     ops.metric_sums(inf_u8, hr_u8, out=sums[0])
                     ops.metric_sums(sr_u8, hr_u8, out=sums[1])
                     sums_host = ops.land('sums', slot, sums)
+                if use_lpips:
+                    lp_host = ops.land('lpips', slot, ops.lpips(lpips, hr_u8, inf_u8, sr_u8))
             done = threading.Event()
             slot_free[slot] = done
-            jobs.put((ops.mark(), idxs, sr_host, sums_host, hr_host, inf_host, done))
+            jobs.put((ops.mark(), idxs, sr_host, sums_host, hr_host, inf_host, lp_host, done))
             clock['post'] += time.perf_counter() - tp
     finally:
         tt = time.perf_counter()
@@ -366,30 +384,52 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
         clock['tail'] = time.perf_counter() - tt
     if errors:
         raise errors[0]
-    sums = np.zeros(9, dtype=np.float64)       # bic mse/psnr/ssim/ergas, sr mse/psnr/ssim/ergas, count
+    sums = np.zeros(n_metric + 1, dtype=np.float64)    # bic mse/psnr/ssim/ergas, sr mse/psnr/ssim/ergas[, bic/sr lpips], count
     for index in sorted(per_image):
         if per_image[index] is not None:
-            sums[:8] += np.array(per_image[index])
-        sums[8] += 1.0
+            sums[:n_metric] += np.array(per_image[index])
+        sums[n_metric] += 1.0
     if world > 1:
         import torch.distributed as dist
         t = torch.from_numpy(sums).cuda() if dist.get_backend() == 'nccl' else torch.from_numpy(sums)
         dist.all_reduce(t)
         sums = t.cpu().numpy()
-    n = max(sums[8], 1.0)
-    avg = sums[:8] / n
-    res = dict(images=int(sums[8]), bic_mse=avg[0], bic_psnr=avg[1], bic_ssim=avg[2], bic_ergas=avg[3],
+    n = max(sums[n_metric], 1.0)
+    avg = sums[:n_metric] / n
+    res = dict(images=int(sums[n_metric]), bic_mse=avg[0], bic_psnr=avg[1], bic_ssim=avg[2], bic_ergas=avg[3],
                sr_mse=avg[4], sr_psnr=avg[5], sr_ssim=avg[6], sr_ergas=avg[7],
                sample_seconds_this_rank=t_sample, result_path=result_path,
                host_seconds=dict(clock, total=time.perf_counter() - t_run0, workers=n_workers))
+    if use_lpips:
+        res.update(bic_lpips=avg[8], sr_lpips=avg[9])
     if rank == 0 and infer:
-        log('inference: {} images, {:.4f} s per image on this rank (batch {})'.format(int(sums[8]), t_sample / max(hi - lo, 1), batch))
+        log('inference: {} images, {:.4f} s per image on this rank (batch {})'.format(int(sums[n_metric]), t_sample / max(hi - lo, 1), batch))
     elif rank == 0:
+        # sr_mfe.py:375-378 (and :230-235): LPIPS last on each line
         log('<epoch:{:3d}, iter:{:8,d}> bic_mse: {:.5e}, bic_psnr: {:.5e}, bic_ssim: {:.5e}, bic_ergas: {:.5e}'.format(
-            current_epoch, current_step, *avg[:4]))
+            current_epoch, current_step, *avg[:4]) + (', bic_lpips: {:.5e}'.format(avg[8]) if use_lpips else ''))
         log('<epoch:{:3d}, iter:{:8,d}> sr_mse: {:.5e}, sr_psnr: {:.5e}, sr_ssim: {:.5e}, sr_ergas: {:.5e}'.format(
-            current_epoch, current_step, *avg[4:8]))
+            current_epoch, current_step, *avg[4:8]) + (', sr_lpips: {:.5e}'.format(avg[9]) if use_lpips else ''))
     return res
+
+
+def add_lpips_args(ap):
+    ap.add_argument('--lpips', action='store_true',
+                    help="also score LPIPS (the reference's calculate_lpips) with the weight files where the reference's users have "
+                         "them: $TORCH_HOME/hub/checkpoints/alexnet-owt-7be5be79.pth and the lpips package's weights/v0.1/alex.pth")
+    ap.add_argument('--lpips-backbone', default=None, metavar='PATH', help="torchvision's AlexNet state dict (implies --lpips)")
+    ap.add_argument('--lpips-lin', default=None, metavar='PATH', help="lpips' v0.1 alex.pth heads (implies --lpips)")
+
+
+def lpips_from_args(a):
+    """The metrics.LPIPS the flags ask for, or None.  Built once per run (a training run's val passes share it)."""
+    if not (a.lpips or a.lpips_backbone or a.lpips_lin):
+        return None
+    backbone, lin = a.lpips_backbone, a.lpips_lin
+    if backbone is None or lin is None:
+        d_backbone, d_lin = M.LPIPS.default_paths()
+        backbone, lin = backbone or d_backbone, lin or d_lin
+    return M.LPIPS(backbone, lin)
 
 
 def main(argv=None, diffusion=None, ops=None):
@@ -413,6 +453,7 @@ def main(argv=None, diffusion=None, ops=None):
     ap.add_argument('--graph', default=None, choices=['auto', 'on', 'off'],
                     help='replay the T-step loop as a captured hipGraph (default auto: from the second call of a shape on)')
     ap.add_argument('--host-metrics', action='store_true', help='score on the host (numpy) instead of the device kernels')
+    add_lpips_args(ap)
     a = ap.parse_args(argv)
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
     if world > 1:
@@ -428,9 +469,11 @@ def main(argv=None, diffusion=None, ops=None):
         log = lambda msg: (print(msg), val_logger.info(msg))     # noqa: E731
         if a.results is None:
             a.results = opt['path'].get('results')
+    lpips = None if a.infer else lpips_from_args(a)
     res = run(opt, batch=a.batch, cond_from_lr=a.cond_from_lr, precision=a.precision, results=a.results,
               max_images=a.max_images, rank=rank, world=world, save_images=not a.no_save, infer=a.infer, log=log,
-              workers=a.workers, rng=a.rng, graph=a.graph, host_metrics=a.host_metrics, diffusion=diffusion, ops=ops)
+              workers=a.workers, rng=a.rng, graph=a.graph, host_metrics=a.host_metrics, diffusion=diffusion, ops=ops,
+              lpips=lpips)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

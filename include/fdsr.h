@@ -224,6 +224,29 @@ int fdsr_image_metrics_u8(fdsr_handle h, const uint8_t* test_nhwc, const uint8_t
                           int width, int channels, int flags, double* out_dev, void* workspace, size_t workspace_bytes,
                           void* hip_stream);
 
+/* -- LPIPS, the fifth val metric (core/metrics.py:154-163 calculate_lpips: lpips.LPIPS(net='alex'), v0.1 heads) ----
+ * An object of its own, independent of fdsr_handle: the torchvision AlexNet `features` convolutions and the five linear
+ * heads, in fp32 on the device.  fdsr_lpips_load takes exactly these host fp32 tensors, in the checkpoint layouts:
+ *   features.{0,3,6,8,10}.weight  [64,3,11,11] [192,64,5,5] [384,192,3,3] [256,384,3,3] [256,256,3,3]
+ *   features.{0,3,6,8,10}.bias    [64] [192] [384] [256] [256]
+ *   lin{0..4}.model.1.weight      [1,C,1,1], C = 64, 192, 384, 256, 256
+ * Any other name or shape: FDSR_E_KEY.  Loading is a host-synchronous copy.
+ * fdsr_lpips_u8 scores test_a (and test_b unless NULL) against truth, all [B,H,W,3] uint8 device images, as the reference
+ * does: ToTensor() in [0,1] (NOT mapped to [-1,1]), ScalingLayer, AlexNet relu1..relu5, channel-normalised squared
+ * differences weighted by the heads, spatial means.  The truth features are computed once for both tests.
+ *   out_dev [n_tests][B][6] fp64 device: (LPIPS, then the five per-layer terms, retPerLayer).
+ * Exact-fp32 MFMA convolutions, fp64 distances, fixed-order reductions: reruns are bitwise identical, an image's value does
+ * not depend on B or its position in the batch, identical images give exactly 0.  H, W >= 32 (FDSR_E_INVALID below);
+ * FDSR_E_STATE if any of the 15 tensors is missing; FDSR_E_WORKSPACE if the workspace (sized for two tests, 256-byte
+ * aligned) is too small.  Stream-ordered, no implicit synchronisation.  Messages: fdsr_last_error(NULL). */
+typedef struct fdsr_lpips_obj* fdsr_lpips;
+int fdsr_lpips_create(fdsr_lpips* out);
+int fdsr_lpips_load(fdsr_lpips l, const char* name, const float* host_f32, const int64_t* shape, int ndim);
+int fdsr_lpips_workspace_bytes(fdsr_lpips l, int batch, int height, int width, size_t* bytes);
+int fdsr_lpips_u8(fdsr_lpips l, const uint8_t* truth_nhwc, const uint8_t* test_a_nhwc, const uint8_t* test_b_nhwc_or_null,
+                  int batch, int height, int width, double* out_dev, void* workspace, size_t workspace_bytes, void* hip_stream);
+void fdsr_lpips_destroy(fdsr_lpips l);
+
 /* -- input-pipeline helper ------------------------------------ */
 /* The dataset's tensor transform on the device (data/util.py:66-75 transform_augment: ToTensor() = uint8 / 255 as fp32,
  * HWC -> CHW, then img * (hi - lo) + lo; LRHR_dataset.py:113-119 passes min_max = (-1, 1)): the loader threads hand over
