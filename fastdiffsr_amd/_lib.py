@@ -95,6 +95,12 @@ SYMBOLS = {
     'fdsr_lpips_u8': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_void_p]),
     'fdsr_lpips_destroy': (None, [C.c_void_p]),
+    'fdsr_fid_create': (C.c_int, [C.POINTER(C.c_void_p)]),
+    'fdsr_fid_load': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    'fdsr_fid_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    'fdsr_fid_features_u8': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
+    'fdsr_fid_destroy': (None, [C.c_void_p]),
     'fdsr_set_debug': (C.c_int, [C.c_void_p, C.c_int]),
     'fdsr_debug_option': (C.c_int, [C.c_char_p, C.c_longlong]),
     'fdsr_check_saturation': (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -325,3 +325,209 @@ class LPIPS:
         _lib.check(None, _lib.load().fdsr_lpips_u8(self._h, ptr[0], ptr[1], ptr[2], b, h, w, C.c_void_p(out.data_ptr()),
                                                    C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(st)))
         return out
+
+
+# --- FID (FastDiffSR/FID.py: pytorch_fid.fid_score.calculate_fid_given_paths(..., dims=2048)), features on the device -------
+def _fid_layers():
+    """The 94 BasicConv2d of pytorch_fid's InceptionV3 up to pool3 (use_fid_inception=True), in state-dict order:
+    (name, cin, cout, kh, kw, stride, pad_h, pad_w).  csrc/fdsr_fid.hip walks the same table."""
+    out = []
+
+    def c(name, cin, cout, k, s=1, p=(0, 0)):
+        out.append((name, cin, cout, k[0], k[1], s, p[0], p[1]))
+    c('Conv2d_1a_3x3', 3, 32, (3, 3), 2)
+    c('Conv2d_2a_3x3', 32, 32, (3, 3))
+    c('Conv2d_2b_3x3', 32, 64, (3, 3), 1, (1, 1))
+    c('Conv2d_3b_1x1', 64, 80, (1, 1))
+    c('Conv2d_4a_3x3', 80, 192, (3, 3))
+    for m, cin, pf in (('Mixed_5b', 192, 32), ('Mixed_5c', 256, 64), ('Mixed_5d', 288, 64)):      # FIDInceptionA
+        c(m + '.branch1x1', cin, 64, (1, 1))
+        c(m + '.branch5x5_1', cin, 48, (1, 1))
+        c(m + '.branch5x5_2', 48, 64, (5, 5), 1, (2, 2))
+        c(m + '.branch3x3dbl_1', cin, 64, (1, 1))
+        c(m + '.branch3x3dbl_2', 64, 96, (3, 3), 1, (1, 1))
+        c(m + '.branch3x3dbl_3', 96, 96, (3, 3), 1, (1, 1))
+        c(m + '.branch_pool', cin, pf, (1, 1))
+    c('Mixed_6a.branch3x3', 288, 384, (3, 3), 2)                                                  # InceptionB
+    c('Mixed_6a.branch3x3dbl_1', 288, 64, (1, 1))
+    c('Mixed_6a.branch3x3dbl_2', 64, 96, (3, 3), 1, (1, 1))
+    c('Mixed_6a.branch3x3dbl_3', 96, 96, (3, 3), 2)
+    for m, c7 in (('Mixed_6b', 128), ('Mixed_6c', 160), ('Mixed_6d', 160), ('Mixed_6e', 192)):     # FIDInceptionC
+        c(m + '.branch1x1', 768, 192, (1, 1))
+        c(m + '.branch7x7_1', 768, c7, (1, 1))
+        c(m + '.branch7x7_2', c7, c7, (1, 7), 1, (0, 3))
+        c(m + '.branch7x7_3', c7, 192, (7, 1), 1, (3, 0))
+        c(m + '.branch7x7dbl_1', 768, c7, (1, 1))
+        c(m + '.branch7x7dbl_2', c7, c7, (7, 1), 1, (3, 0))
+        c(m + '.branch7x7dbl_3', c7, c7, (1, 7), 1, (0, 3))
+        c(m + '.branch7x7dbl_4', c7, c7, (7, 1), 1, (3, 0))
+        c(m + '.branch7x7dbl_5', c7, 192, (1, 7), 1, (0, 3))
+        c(m + '.branch_pool', 768, 192, (1, 1))
+    c('Mixed_7a.branch3x3_1', 768, 192, (1, 1))                                                   # InceptionD
+    c('Mixed_7a.branch3x3_2', 192, 320, (3, 3), 2)
+    c('Mixed_7a.branch7x7x3_1', 768, 192, (1, 1))
+    c('Mixed_7a.branch7x7x3_2', 192, 192, (1, 7), 1, (0, 3))
+    c('Mixed_7a.branch7x7x3_3', 192, 192, (7, 1), 1, (3, 0))
+    c('Mixed_7a.branch7x7x3_4', 192, 192, (3, 3), 2)
+    for m, cin in (('Mixed_7b', 1280), ('Mixed_7c', 2048)):                                       # FIDInceptionE_1 / _2
+        c(m + '.branch1x1', cin, 320, (1, 1))
+        c(m + '.branch3x3_1', cin, 384, (1, 1))
+        c(m + '.branch3x3_2a', 384, 384, (1, 3), 1, (0, 1))
+        c(m + '.branch3x3_2b', 384, 384, (3, 1), 1, (1, 0))
+        c(m + '.branch3x3dbl_1', cin, 448, (1, 1))
+        c(m + '.branch3x3dbl_2', 448, 384, (3, 3), 1, (1, 1))
+        c(m + '.branch3x3dbl_3a', 384, 384, (1, 3), 1, (0, 1))
+        c(m + '.branch3x3dbl_3b', 384, 384, (3, 1), 1, (1, 0))
+        c(m + '.branch_pool', cin, 192, (1, 1))
+    return out
+
+
+FID_LAYERS = _fid_layers()
+FID_TENSORS = OrderedDict()           # the 470 tensors fdsr_fid_load takes, in load order
+for _n, _ci, _co, _kh, _kw, _s, _ph, _pw in FID_LAYERS:
+    FID_TENSORS[_n + '.conv.weight'] = (_co, _ci, _kh, _kw)
+    for _b in ('weight', 'bias', 'running_mean', 'running_var'):
+        FID_TENSORS[_n + '.bn.' + _b] = (_co,)
+del _n, _ci, _co, _kh, _kw, _s, _ph, _pw, _b
+# include/fdsr.h's module table: (name, output side, output channels) at the fixed 299 x 299 input
+FID_MODULES = [('Conv2d_1a_3x3', 149, 32), ('Conv2d_2a_3x3', 147, 32), ('Conv2d_2b_3x3', 147, 64), ('MaxPool_1', 73, 64),
+               ('Conv2d_3b_1x1', 73, 80), ('Conv2d_4a_3x3', 71, 192), ('MaxPool_2', 35, 192), ('Mixed_5b', 35, 256),
+               ('Mixed_5c', 35, 288), ('Mixed_5d', 35, 288), ('Mixed_6a', 17, 768), ('Mixed_6b', 17, 768), ('Mixed_6c', 17, 768),
+               ('Mixed_6d', 17, 768), ('Mixed_6e', 17, 768), ('Mixed_7a', 8, 1280), ('Mixed_7b', 8, 2048), ('Mixed_7c', 8, 2048)]
+FID_DIMS = 2048
+FID_WEIGHTS_FILE = 'pt_inception-2015-12-05-6726825d.pth'     # pytorch_fid's FID Inception weights, as its hub cache names it
+
+
+def fid_state(sd):
+    """The 470 tensors fdsr_fid_load takes, as float32 numpy arrays in load order, from the FID Inception state dict
+    (pt_inception-2015-12-05-6726825d.pth, torchvision names).  `fc.*` and `*.num_batches_tracked` are ignored; any other
+    name, a missing tensor or a wrong shape raises KeyError / ValueError naming it: nothing is guessed."""
+    extra = [k for k in sd if k not in FID_TENSORS and not k.startswith('fc.') and not k.endswith('.num_batches_tracked')]
+    if extra:
+        raise KeyError('unexpected FID Inception tensor(s): %s' % ', '.join(sorted(extra)))
+    out = OrderedDict()
+    for k, shape in FID_TENSORS.items():
+        if k not in sd:
+            raise KeyError('FID Inception tensor %r is missing' % k)
+        v = sd[k]
+        a = (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float32)
+        if tuple(a.shape) != shape:
+            raise ValueError('FID Inception tensor %r has shape %s, expected %s' % (k, tuple(a.shape), shape))
+        out[k] = np.ascontiguousarray(a)
+    return out
+
+
+class FID:
+    """pytorch_fid's pool3 features (InceptionV3, dims=2048) of uint8 images on the device (include/fdsr.h: fdsr_fid_*).
+
+        fid = FID(state_dict_or_path)              # pt_inception-2015-12-05-6726825d.pth (torch.load(weights_only=True))
+        fid = FID(FID.default_path())
+        f = fid.features_u8(imgs)                  # [B,H,W,3] uint8 CUDA -> [B,2048] fp32 CUDA
+        frechet_distance(*activation_statistics(f1), *activation_statistics(f2))
+
+    Any H, W: every image is resized to 299 x 299 first.  Features are per image (bitwise independent of the batch), so B is
+    cut into chunks whose workspace stays within MAX_WORKSPACE bytes."""
+
+    MAX_WORKSPACE = 2 << 30
+
+    def __init__(self, weights, device=None):
+        tensors = fid_state(_as_state_dict(weights))
+        self.device = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
+        lib = _lib.load()
+        h = C.c_void_p()
+        _lib.check(None, lib.fdsr_fid_create(C.byref(h)))
+        self._h = h
+        with torch.cuda.device(self.device):
+            for k, a in tensors.items():
+                shape = (C.c_int64 * a.ndim)(*a.shape)
+                _lib.check(None, lib.fdsr_fid_load(h, k.encode(), C.c_void_p(a.ctypes.data), shape, a.ndim))
+        self._ws = {}
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h is not None and _lib._lib is not None:
+            _lib._lib.fdsr_fid_destroy(h)
+            self._h = None
+
+    @staticmethod
+    def default_path():
+        """Where pytorch_fid caches the weights for the reference's users: torch.hub.get_dir()/checkpoints/<FID_WEIGHTS_FILE>.
+        Nothing is ever downloaded."""
+        p = os.path.join(torch.hub.get_dir(), 'checkpoints', FID_WEIGHTS_FILE)
+        if not os.path.isfile(p):
+            raise FileNotFoundError('FID Inception weights %s not found: put pytorch_fid\'s %s there, or pass --fid-weights PATH'
+                                    % (p, FID_WEIGHTS_FILE))
+        return p
+
+    def _workspace_bytes(self, b, h, w):
+        need = C.c_size_t()
+        _lib.check(None, _lib.load().fdsr_fid_workspace_bytes(self._h, b, h, w, C.byref(need)))
+        return int(need.value)
+
+    def chunk(self, h, w):
+        """Images per device call: the most whose workspace fits MAX_WORKSPACE (at least 1)."""
+        one = self._workspace_bytes(1, h, w)
+        per = max(self._workspace_bytes(2, h, w) - one, 1)
+        return max(1, 1 + (self.MAX_WORKSPACE - one) // per)
+
+    def workspace(self, b, h, w):
+        need = self._workspace_bytes(b, h, w)
+        key = (self.device, torch.cuda.current_stream(self.device).cuda_stream)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def features_u8(self, imgs, module=-1):
+        """[B,H,W,3] uint8 CUDA images -> [B,2048] fp32 CUDA pool3 features (asynchronous on the current stream).
+        module = k: the raw NHWC output of module k of FID_MODULES, [B,S,S,C]; module = -2: the normalised 299 x 299 input."""
+        if not imgs.is_cuda or imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[-1] != 3:
+            raise ValueError('features_u8 takes [B,H,W,3] uint8 CUDA images')
+        imgs = imgs.contiguous()
+        b, h, w, _ = imgs.shape
+        if module == -1:
+            shape = (FID_DIMS,)
+        elif module == -2:
+            shape = (299, 299, 3)
+        else:
+            _, s, c = FID_MODULES[module]
+            shape = (s, s, c)
+        out = torch.empty((b,) + shape, dtype=torch.float32, device=imgs.device)
+        if b == 0:
+            return out
+        n = min(b, self.chunk(h, w))
+        ws = self.workspace(n, h, w)
+        st = torch.cuda.current_stream(imgs.device).cuda_stream
+        for i in range(0, b, n):
+            m = min(n, b - i)
+            _lib.check(None, _lib.load().fdsr_fid_features_u8(self._h, C.c_void_p(imgs[i].data_ptr()), m, h, w, module,
+                                                              C.c_void_p(out[i].data_ptr()), C.c_void_p(ws.data_ptr()),
+                                                              ws.numel(), C.c_void_p(st)))
+        return out
+
+
+def activation_statistics(feats):
+    """pytorch_fid's calculate_activation_statistics on [N, D] features, in fp64: (mu = mean, sigma = np.cov(rowvar=False))."""
+    a = (feats.detach().cpu().numpy() if isinstance(feats, torch.Tensor) else np.asarray(feats)).astype(np.float64)
+    return np.mean(a, axis=0), np.cov(a, rowvar=False)
+
+
+def frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
+    """pytorch_fid's calculate_frechet_distance: |mu1 - mu2|^2 + tr s1 + tr s2 - 2 tr sqrtm(s1 s2), scipy.linalg.sqrtm in fp64;
+    a non-finite root is retried with eps * I added to both covariances; a diagonal imaginary part above 1e-3 raises ValueError,
+    a smaller one is dropped."""
+    from scipy import linalg
+    mu1, mu2 = np.atleast_1d(np.asarray(mu1, dtype=np.float64)), np.atleast_1d(np.asarray(mu2, dtype=np.float64))
+    sigma1, sigma2 = np.atleast_2d(np.asarray(sigma1, dtype=np.float64)), np.atleast_2d(np.asarray(sigma2, dtype=np.float64))
+    if mu1.shape != mu2.shape or sigma1.shape != sigma2.shape:
+        raise ValueError('frechet_distance: the two statistics have different dimensions')
+    diff = mu1 - mu2
+    covmean = linalg.sqrtm(sigma1.dot(sigma2))
+    if not np.isfinite(covmean).all():
+        offset = np.eye(sigma1.shape[0]) * eps
+        covmean = linalg.sqrtm((sigma1 + offset).dot(sigma2 + offset))
+    if np.iscomplexobj(covmean):
+        if not np.allclose(np.diagonal(covmean).imag, 0, atol=1e-3):
+            raise ValueError('frechet_distance: imaginary component %g' % np.max(np.abs(covmean.imag)))
+        covmean = covmean.real
+    return float(diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(covmean))

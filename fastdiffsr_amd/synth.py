@@ -86,3 +86,26 @@ def synth_alexnet_features(seed: int = 0) -> "OrderedDict[str, np.ndarray]":
             x = g.normal(0.0, np.sqrt(2.0 / int(np.prod(shape[1:]))), size=shape)
         out[k] = x.astype(np.float32)
     return out
+
+
+def synth_inception_fid(seed: int = 0) -> "OrderedDict[str, np.ndarray]":
+    """A stand-in for pytorch_fid's FID Inception weights (pt_inception-2015-12-05-6726825d.pth; no real copy is committed):
+    the 470 tensors of metrics.FID_TENSORS, float32, drawn in key order from numpy.random.default_rng(seed) -- conv weights
+    He-normal (std sqrt(2 / fan_in)), BN gamma N(1, 0.05^2), beta N(0, 0.05^2), running mean 0 and var 1 -- so that every
+    block's activations stay O(1) (tests/test_fid_host.py checks it)."""
+    from .metrics import FID_TENSORS
+    g = np.random.default_rng(seed)
+    out = OrderedDict()
+    for k, shape in FID_TENSORS.items():
+        if k.endswith('.conv.weight'):
+            x = g.normal(0.0, np.sqrt(2.0 / int(np.prod(shape[1:]))), size=shape)
+        elif k.endswith('.bn.weight'):
+            x = g.normal(1.0, 0.05, size=shape)
+        elif k.endswith('.bn.bias'):
+            x = g.normal(0.0, 0.05, size=shape)
+        elif k.endswith('.bn.running_mean'):
+            x = np.zeros(shape)
+        else:
+            x = np.ones(shape)
+        out[k] = x.astype(np.float32)
+    return out

@@ -7,7 +7,8 @@ FastDiffSR/sr_mfe.py:69-251) on the HIP engine:
 Same config files and dataset folders; per iteration `feed_data` + `optimize_parameters` (forward, loss / (b*c*h*w),
 backward and Adam in the engine), the `<epoch, iter> l_pix` log line every `print_freq`, a validation pass every
 `val_freq` (the val schedule, then back to the train schedule, sr_mfe.py:122-244; with `--lpips` or `--lpips-backbone PATH
---lpips-lin PATH` its log lines carry bic_lpips / sr_lpips, the LPIPS object built once per run) and `I{iter}_E{epoch}_{gen,opt}.pth`
+--lpips-lin PATH` its log lines carry bic_lpips / sr_lpips, the LPIPS object built once per run; with `--fid` or
+`--fid-weights PATH` bic_fid / sr_fid, the HR / bicubic statistics of the fixed val set computed by the first pass only) and `I{iter}_E{epoch}_{gen,opt}.pth`
 every `save_checkpoint_freq`.  tensorboard / wandb writers are not reproduced (the scalars go to the log).
 Under torch.distributed every rank takes its slice of each batch and the gradient arena is all-reduced: the global
 batch is the config's batch_size, as with the reference's nn.DataParallel (networks.py:116-118)."""
@@ -33,9 +34,12 @@ def loader_workers(num_workers):
     return max(2, min(int(num_workers or 0) or share, share))
 
 
-def run(opt, precision='f16x3', rank=0, world=1, log=print, val_batch=1, max_val_images=None, diffusion=None, ops=None, lpips=None):
+def run(opt, precision='f16x3', rank=0, world=1, log=print, val_batch=1, max_val_images=None, diffusion=None, ops=None, lpips=None,
+        fid=None):
     """diffusion / ops: a ready model and the device side of the loaders (val.HipOps) -- injection points of the tests.
-    lpips: a metrics.LPIPS for the validation passes (their log lines then carry bic_lpips / sr_lpips, sr_mfe.py:230-235)."""
+    lpips: a metrics.LPIPS for the validation passes (their log lines then carry bic_lpips / sr_lpips, sr_mfe.py:230-235).
+    fid: a metrics.FID for the validation passes (bic_fid / sr_fid; the HR / bicubic statistics are kept between passes)."""
+    fid_cache = {}
     train_opt = opt['datasets']['train']
     train_set = create_dataset(train_opt, 'train')
     # every rank draws the same batches (same shuffle seed) and keeps its own slice of each
@@ -96,7 +100,7 @@ def run(opt, precision='f16x3', rank=0, world=1, log=print, val_batch=1, max_val
                 res = V.run(opt, batch=val_batch, precision=precision, results=(opt.get('path') or {}).get('results'),
                             max_images=max_val_images, rank=rank, world=world, save_images=rank == 0 or world > 1, log=log,
                             diffusion=diffusion, step=current_step, epoch=current_epoch, ops=ops,
-                            lpips=lpips)
+                            lpips=lpips, fid=fid, fid_cache=fid_cache)
                 history.append((current_step, {'val_psnr': res['sr_psnr']}))
                 diffusion.set_new_noise_schedule(opt['model']['beta_schedule']['train'], schedule_phase='train')   # :233-234
             if current_step % opt['train']['save_checkpoint_freq'] == 0 and rank == 0:
@@ -117,6 +121,7 @@ def main(argv=None, diffusion=None, ops=None):
     ap.add_argument('-debug', '-d', action='store_true')
     ap.add_argument('--precision', default='f16x3', choices=['f32', 'f16x3'])
     V.add_lpips_args(ap)
+    V.add_fid_args(ap)
     a = ap.parse_args(argv)
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
     if world > 1:
@@ -129,7 +134,8 @@ def main(argv=None, diffusion=None, ops=None):
         tl = setup_logger(None, opt['path']['log'], 'train', screen=True)
         setup_logger('val', opt['path']['log'], 'val')
         log = logging.getLogger('base').info if tl is None else tl.info
-    out = run(opt, precision=a.precision, rank=rank, world=world, log=log, diffusion=diffusion, ops=ops, lpips=V.lpips_from_args(a))
+    out = run(opt, precision=a.precision, rank=rank, world=world, log=log, diffusion=diffusion, ops=ops, lpips=V.lpips_from_args(a),
+              fid=V.fid_from_args(a))
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

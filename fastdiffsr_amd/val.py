@@ -5,12 +5,15 @@ FastDiffSR/sr_mfe.py:257-378) on the HIP engine:
     python -m fastdiffsr_amd.val -c config/sr_fastdiffsr_infer_x4.json --infer        # infer.py
 
     python -m fastdiffsr_amd.val -c ... --lpips-backbone alexnet-owt-7be5be79.pth --lpips-lin lpips/weights/v0.1/alex.pth
+    python -m fastdiffsr_amd.val -c ... --fid-weights pt_inception-2015-12-05-6726825d.pth
 
 Same config files, same dataset folders, same per-image metrics and log lines (MSE / PSNR / SSIM as
 skimage.measure computes them, ERGAS as core/metrics.py:147-152), same `{results}/{step}_{idx}_sr.tif` outputs.
 LPIPS (core/metrics.py:154-163, AlexNet + the v0.1 heads) is the reference's fifth metric: it needs the user's own weight
 files and runs when asked for (`--lpips` looks where the reference's users have them, metrics.LPIPS.default_paths; or
 `--lpips-backbone PATH --lpips-lin PATH`); the two log lines then carry `bic_lpips` / `sr_lpips` as the reference's do.
+FID (FID.py, pytorch_fid's Inception pool3, dims=2048) is scored over the whole val set when asked for (`--fid` reads the
+weights from pytorch_fid's hub cache, metrics.FID.default_path; `--fid-weights PATH`): `bic_fid` / `sr_fid` follow on the lines.
 Differences, all opt-in or harmless:
   * `--batch N` samples N images per loop (the reference's val loader is batch 1 and its sampler crashes for
     more); every image is still its own independent chain
@@ -130,6 +133,11 @@ class HipOps:
         """core/metrics.py:154-163 for both test images against one truth -> [2, B, 6] fp64 on the device (metrics.LPIPS)."""
         return model.lpips_u8(truth_u8, test_a_u8, test_b_u8)
 
+    def fid_features(self, model, imgs_u8):
+        """FID.py's pool3 features of each [B,H,W,3] uint8 batch in `imgs_u8`, stacked -> [len(imgs_u8) * B, 2048] fp32 on the
+        device (metrics.FID)"""
+        return model.features_u8(torch.cat(imgs_u8) if len(imgs_u8) > 1 else imgs_u8[0])
+
     def lr_to_sr(self, lr_u8, h, w):
         return lr_to_sr(lr_u8, h, w)
 
@@ -212,7 +220,7 @@ class _Loader:
 
 def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_images=None, rank=0, world=1,
         save_images=True, log=print, infer=False, diffusion=None, step=None, epoch=None, workers=None, rng=None, graph=None,
-        host_metrics=False, ops=None, lpips=None):
+        host_metrics=False, ops=None, lpips=None, fid=None, fid_cache=None):
     """infer=True is the reference's infer.py (:62-110): the same loop, `{step}_{idx}_sr.png` outputs, timing, no metrics.
     diffusion: an existing model (the validation pass inside the training loop, sr_mfe.py:122-244); else one is created.
 
@@ -225,7 +233,12 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
     graph: 'auto' | 'on' | 'off' -- replay the 20-step loop as a captured hipGraph (None: the model's default, 'auto').
     ops: the device side (HipOps; see there).
     lpips: a metrics.LPIPS, or None (the default: no LPIPS, the log lines and `res` exactly as without the feature).  With it
-    every image also gets bic_lpips / sr_lpips from the device (host_metrics included: there is no host LPIPS)."""
+    every image also gets bic_lpips / sr_lpips from the device (host_metrics included: there is no host LPIPS).
+    fid: a metrics.FID, or None (no FID).  With it the pool3 features of the HR, bicubic and SR uint8 images (the ones the
+    metrics score and the .tif files hold) are kept per image index, gathered to rank 0 in index order, and bic_fid = FID(INF,
+    HR), sr_fid = FID(SR, HR) are computed there in fp64 (FID.py's order: generated set first) and broadcast.
+    fid_cache: a dict the caller keeps between passes over the same val set (the training loop): the HR / INF statistics and
+    bic_fid are computed by the first pass and reused, later passes compute SR features only."""
     import queue
     import sys
     import threading
@@ -255,6 +268,12 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
     rres = int(val_opt['r_resolution'])
     use_lpips = lpips is not None and not infer
     n_metric = 10 if use_lpips else 8
+    use_fid = fid is not None and not infer
+    fid_ref = fid_cache if fid_cache is not None else {}
+    if fid_ref.get('images') not in (None, n_total):
+        fid_ref.clear()                # another val set: its statistics do not apply
+    fid_sets = 1 if 'hr' in fid_ref else 3          # (HR, INF, SR) or, with the reference statistics cached, SR only
+    per_fid = {}                       # index -> [fid_sets, D] fp32 features
     per_image = {}                     # index -> 8 numbers (bic mse/psnr/ssim/ergas, sr mse/psnr/ssim/ergas[, bic_lpips, sr_lpips]); summed in index order
     t_sample = 0.0
     # loader / writer threads of THIS rank: its share of the cores the job may use (affinity, cgroup quota, ranks on the host)
@@ -274,9 +293,13 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
             if job is None:
                 return
             try:
-                ev, idxs, sr_host, sums_host, hr_host, inf_host, lp_host, _ = job
+                ev, idxs, sr_host, sums_host, hr_host, inf_host, lp_host, fd_host, _ = job
                 ev.synchronize()
                 sr_np = sr_host.numpy()
+                if fd_host is not None:
+                    fd = fd_host.numpy().reshape(fid_sets, len(idxs), -1)
+                    for j, index in enumerate(idxs):
+                        per_fid[index] = fd[:, j].copy()
                 for j, index in enumerate(idxs):
                     idx = index + 1                                                   # sr_mfe.py:274 counts from 1
                     if save_images:
@@ -354,7 +377,7 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
             if slot_free[slot] is not None:
                 slot_free[slot].wait()           # the finisher is done with this slot's previous contents
             sr_host = ops.land('sr', slot, sr_u8)
-            sums_host = hr_host = inf_host = lp_host = None
+            sums_host = hr_host = inf_host = lp_host = fd_host = None
             if not infer:
                 hr_u8 = ops.tensor2img_batch(diffusion.data['HR'])
                 inf_u8 = ops.tensor2img_batch(diffusion.data['SR'])                   # the bicubic image ('INF')
@@ -367,9 +390,11 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
                     sums_host = ops.land('sums', slot, sums)
                 if use_lpips:
                     lp_host = ops.land('lpips', slot, ops.lpips(lpips, hr_u8, inf_u8, sr_u8))
+                if use_fid:
+                    fd_host = ops.land('fid', slot, ops.fid_features(fid, (hr_u8, inf_u8, sr_u8) if fid_sets == 3 else (sr_u8,)))
             done = threading.Event()
             slot_free[slot] = done
-            jobs.put((ops.mark(), idxs, sr_host, sums_host, hr_host, inf_host, lp_host, done))
+            jobs.put((ops.mark(), idxs, sr_host, sums_host, hr_host, inf_host, lp_host, fd_host, done))
             clock['post'] += time.perf_counter() - tp
     finally:
         tt = time.perf_counter()
@@ -402,15 +427,63 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
                host_seconds=dict(clock, total=time.perf_counter() - t_run0, workers=n_workers))
     if use_lpips:
         res.update(bic_lpips=avg[8], sr_lpips=avg[9])
+    if use_fid:
+        tf = time.perf_counter()
+        res.update(_fid_scores(per_fid, fid_ref, n_total, fid_sets, rank, world))
+        res['host_seconds']['fid_statistics'] = time.perf_counter() - tf      # gather + fp64 statistics + sqrtm (rank 0)
+    tail_b = (', bic_lpips: {:.5e}'.format(avg[8]) if use_lpips else '') + (', bic_fid: {:.5e}'.format(res['bic_fid']) if use_fid else '')
+    tail_s = (', sr_lpips: {:.5e}'.format(avg[9]) if use_lpips else '') + (', sr_fid: {:.5e}'.format(res['sr_fid']) if use_fid else '')
     if rank == 0 and infer:
         log('inference: {} images, {:.4f} s per image on this rank (batch {})'.format(int(sums[n_metric]), t_sample / max(hi - lo, 1), batch))
     elif rank == 0:
-        # sr_mfe.py:375-378 (and :230-235): LPIPS last on each line
+        # sr_mfe.py:375-378 (and :230-235): LPIPS last on each line, then FID (FID.py) when asked for
         log('<epoch:{:3d}, iter:{:8,d}> bic_mse: {:.5e}, bic_psnr: {:.5e}, bic_ssim: {:.5e}, bic_ergas: {:.5e}'.format(
-            current_epoch, current_step, *avg[:4]) + (', bic_lpips: {:.5e}'.format(avg[8]) if use_lpips else ''))
+            current_epoch, current_step, *avg[:4]) + tail_b)
         log('<epoch:{:3d}, iter:{:8,d}> sr_mse: {:.5e}, sr_psnr: {:.5e}, sr_ssim: {:.5e}, sr_ergas: {:.5e}'.format(
-            current_epoch, current_step, *avg[4:8]) + (', sr_lpips: {:.5e}'.format(avg[9]) if use_lpips else ''))
+            current_epoch, current_step, *avg[4:8]) + tail_s)
     return res
+
+
+def _fid_scores(per_fid, fid_ref, n_total, fid_sets, rank, world):
+    """bic_fid / sr_fid of one pass: this rank's per-image features are gathered to rank 0, put in index order (so the value does
+    not depend on the rank count or the batch), turned into fp64 statistics there and the two distances broadcast."""
+    local = {i: per_fid[i] for i in sorted(per_fid)}
+    if world > 1:
+        import torch.distributed as dist
+        parts = [None] * world if rank == 0 else None
+        dist.gather_object(local, parts, dst=0)
+        if rank == 0:
+            for p in parts[1:]:
+                local.update(p)
+    out = [None]
+    if rank == 0:
+        feats = np.stack([local[i] for i in sorted(local)])          # [N, fid_sets, D], index order
+        if fid_sets == 3:
+            fid_ref.clear()
+            fid_ref.update(images=n_total, hr=M.activation_statistics(feats[:, 0]))
+            fid_ref['bic_fid'] = M.frechet_distance(*M.activation_statistics(feats[:, 1]), *fid_ref['hr'])
+        sr = M.activation_statistics(feats[:, -1])
+        out = [dict(bic_fid=fid_ref['bic_fid'], sr_fid=M.frechet_distance(*sr, *fid_ref['hr']))]
+    if world > 1:
+        import torch.distributed as dist
+        dist.broadcast_object_list(out, src=0)
+        if rank != 0 and fid_sets == 3:
+            fid_ref.update(images=n_total, hr=None, bic_fid=out[0]['bic_fid'])    # later passes: SR features only, as on rank 0
+    return out[0]
+
+
+def add_fid_args(ap):
+    ap.add_argument('--fid', action='store_true',
+                    help="also score FID (FastDiffSR/FID.py: pytorch_fid, dims=2048) of the bicubic and SR images against HR, with "
+                         "the weights where pytorch_fid caches them: torch.hub.get_dir()/checkpoints/pt_inception-2015-12-05-6726825d.pth")
+    ap.add_argument('--fid-weights', default=None, metavar='PATH', help="pytorch_fid's FID Inception state dict (implies --fid)")
+
+
+def fid_from_args(a):
+    """The metrics.FID the flags ask for, or None.  Built once per run (a training run's val passes share it)."""
+    if not (a.fid or a.fid_weights):
+        return None
+    return M.FID(a.fid_weights or M.FID.default_path())
 
 
 def add_lpips_args(ap):
@@ -454,6 +527,7 @@ def main(argv=None, diffusion=None, ops=None):
                     help='replay the T-step loop as a captured hipGraph (default auto: from the second call of a shape on)')
     ap.add_argument('--host-metrics', action='store_true', help='score on the host (numpy) instead of the device kernels')
     add_lpips_args(ap)
+    add_fid_args(ap)
     a = ap.parse_args(argv)
     rank, world = int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1))
     if world > 1:
@@ -470,10 +544,11 @@ def main(argv=None, diffusion=None, ops=None):
         if a.results is None:
             a.results = opt['path'].get('results')
     lpips = None if a.infer else lpips_from_args(a)
+    fid = None if a.infer else fid_from_args(a)
     res = run(opt, batch=a.batch, cond_from_lr=a.cond_from_lr, precision=a.precision, results=a.results,
               max_images=a.max_images, rank=rank, world=world, save_images=not a.no_save, infer=a.infer, log=log,
               workers=a.workers, rng=a.rng, graph=a.graph, host_metrics=a.host_metrics, diffusion=diffusion, ops=ops,
-              lpips=lpips)
+              lpips=lpips, fid=fid)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

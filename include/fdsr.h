@@ -247,6 +247,38 @@ int fdsr_lpips_u8(fdsr_lpips l, const uint8_t* truth_nhwc, const uint8_t* test_a
                   int batch, int height, int width, double* out_dev, void* workspace, size_t workspace_bytes, void* hip_stream);
 void fdsr_lpips_destroy(fdsr_lpips l);
 
+/* -- FID features (FastDiffSR/FID.py: pytorch_fid.fid_score.calculate_fid_given_paths, dims=2048) -----------------
+ * An object of its own: pytorch_fid's InceptionV3(output_blocks=[3], resize_input=True, normalize_input=True,
+ * use_fid_inception=True) in fp32 on the device.  fdsr_fid_load takes the checkpoint's own tensors
+ * (pt_inception-2015-12-05-6726825d.pth, torchvision names), host fp32:
+ *   <module>.conv.weight [Cout,Cin,KH,KW]   <module>.bn.{weight,bias,running_mean,running_var} [Cout]
+ * for the 94 BasicConv2d of the pool3 path (470 tensors; metrics.FID_TENSORS lists them).  fc.* and AuxLogits.* are not
+ * taken: any other name or shape is FDSR_E_KEY.  When the last of a layer's five tensors arrives the library folds the
+ * BN into the convolution in fp64 (w' = w g / sqrt(var + 1e-3), b' = beta - mean g / sqrt(var + 1e-3)) and rounds to fp32.
+ * fdsr_fid_features_u8: [B,H,W,3] uint8 device images (any H, W >= 1: every size is resized to 299 x 299 as pytorch_fid
+ * does, u8 / 255 -> bilinear -> 2x - 1) ->
+ *   module = -1   out_dev [B][2048] fp32: the pool3 features
+ *   module = k    out_dev: the raw NHWC fp32 output of module k, [B][S][S][C]:
+ *                  k  module         S    C      k  module      S    C      k  module      S    C
+ *                  0  Conv2d_1a_3x3  149   32    6  MaxPool_2   35  192   12  Mixed_6c   17  768
+ *                  1  Conv2d_2a_3x3  147   32    7  Mixed_5b    35  256   13  Mixed_6d   17  768
+ *                  2  Conv2d_2b_3x3  147   64    8  Mixed_5c    35  288   14  Mixed_6e   17  768
+ *                  3  MaxPool_1       73   64    9  Mixed_5d    35  288   15  Mixed_7a    8 1280
+ *                  4  Conv2d_3b_1x1   73   80   10  Mixed_6a    17  768   16  Mixed_7b    8 2048
+ *                  5  Conv2d_4a_3x3   71  192   11  Mixed_6b    17  768   17  Mixed_7c    8 2048
+ *   module = -2   out_dev [B][299][299][3]: the normalised network input (the resize stage)
+ * Exact-fp32 MFMA convolutions (no split-K, no atomics), fixed-order pools: reruns are bitwise identical, an image's output
+ * does not depend on B or on its position in the batch.  FDSR_E_INVALID for B < 1, H < 1, W < 1 or a module outside
+ * [-2, 17]; FDSR_E_STATE if any of the 470 tensors is missing; FDSR_E_WORKSPACE if the workspace (256-byte aligned) is too
+ * small.  Stream-ordered, no implicit synchronisation.  Messages: fdsr_last_error(NULL). */
+typedef struct fdsr_fid_obj* fdsr_fid;
+int fdsr_fid_create(fdsr_fid* out);
+int fdsr_fid_load(fdsr_fid f, const char* name, const float* host_f32, const int64_t* shape, int ndim);
+int fdsr_fid_workspace_bytes(fdsr_fid f, int batch, int height, int width, size_t* bytes);
+int fdsr_fid_features_u8(fdsr_fid f, const uint8_t* img_nhwc, int batch, int height, int width, int module, float* out_dev,
+                         void* workspace, size_t workspace_bytes, void* hip_stream);
+void fdsr_fid_destroy(fdsr_fid f);
+
 /* -- input-pipeline helper ------------------------------------ */
 /* The dataset's tensor transform on the device (data/util.py:66-75 transform_augment: ToTensor() = uint8 / 255 as fp32,
  * HWC -> CHW, then img * (hi - lo) + lo; LRHR_dataset.py:113-119 passes min_max = (-1, 1)): the loader threads hand over
