@@ -125,7 +125,7 @@ struct Tunables {
   int gn_consumer = 1;      // small grids: GroupNorm scale / shift formed in the consumer conv's prologue from the producers' fixed-point group sums (no gn_finalize launch)
   int bf16_f16x3_steps = 0; // PROBE (EXPERIMENTS R6): bf16 sampling runs the first n (n > 0) or the last -n (n < 0) reverse steps of the loop on the f16x3 kernels
   int sat_guard = 1;        // f16x3: sticky device flag when a RAW conv input exceeds the f16 range
-  int drop_image_offset = 0;   // tests: the batch is images [offset, offset + N) of a larger one (its dropout masks follow)
+  int drop_image_offset = 0;   // tests: the batch is images [offset, offset + N) of a larger one (its dropout masks and the training step's self-drawn noise follow)
   unsigned epoch = 0;
 };
 extern Tunables g_tun;
@@ -335,8 +335,10 @@ hipError_t launch_posterior_step(const PosteriorStepParams& p, hipStream_t s);
 // Engine-side noise (fdsr_sample with noise == NULL): counter-based Philox4x32-10 + Box-Muller, keyed by
 // (seed, call counter) and indexed by (plane, pixel): the values do not depend on the launch geometry.
 hipError_t launch_rng_advance(unsigned long long* rng, hipStream_t s);                      // ++call counter
-// plane `plane` of the noise the engine would use, as [N,3,H,W] fp32 (tests) ...
-hipError_t launch_randn_plane(const unsigned long long* rng, float* dst_nchw, int N, int HW, int plane, hipStream_t s);
+// plane `plane` of the noise the engine would use, as [N,3,H,W] fp32 (tests; the training step's self-drawn target) ...
+// first_image: the N images are [first_image, first_image + N) of a larger batch and draw those images' pixels
+hipError_t launch_randn_plane(const unsigned long long* rng, float* dst_nchw, int N, int HW, int plane, hipStream_t s,
+                              size_t first_image = 0);
 // ... and x_T = plane 0 written straight into channels 3..5 of the packed UNet input
 hipError_t launch_randn_xin(const unsigned long long* rng, float* xin, int N, int HW, int CP, hipStream_t s, int c_off = 3);
 

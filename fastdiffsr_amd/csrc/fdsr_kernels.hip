@@ -883,7 +883,8 @@ __device__ __forceinline__ void randn3(const unsigned long long* rng, int plane,
     k0 += 0x9E3779B9u;
     k1 += 0xBB67AE85u;
   }
-  // 24-bit uniforms in (0,1); Box-Muller on two pairs (the fourth normal is not used)
+  // 24-bit uniforms in (0,1] (above 2^23 the sum rounds to even: 0xFFFFFF gives 1, radius 0; the smallest, 2^-25, gives |z| <= 5.887);
+  // Box-Muller on two pairs (the fourth normal is not used)
   const float u0 = ((float)(c0 >> 8) + 0.5f) * 5.9604644775390625e-8f, u1 = ((float)(c1 >> 8) + 0.5f) * 5.9604644775390625e-8f;
   const float u2 = ((float)(c2 >> 8) + 0.5f) * 5.9604644775390625e-8f, u3 = ((float)(c3 >> 8) + 0.5f) * 5.9604644775390625e-8f;
   const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
@@ -933,11 +934,11 @@ hipError_t launch_dropout_mask(unsigned char* mask, size_t n, unsigned long long
 }
 
 __global__ void __launch_bounds__(256) randn_plane_kernel(const unsigned long long* __restrict__ rng, float* __restrict__ dst, int HW,
-                                                          int CP, int c_off, int plane, size_t total) {
+                                                          int CP, int c_off, int plane, size_t total, size_t pix0) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   float z[3];
-  randn3(rng, plane, i, z);
+  randn3(rng, plane, i + pix0, z);   // counter = pixel of the FULL batch (pix0: the first pixel of a shard of a larger batch)
   if (CP) {   // NHWC, channels c_off..c_off+2 of the packed input
 #pragma unroll
     for (int c = 0; c < 3; ++c) dst[i * CP + c_off + c] = z[c];
@@ -947,14 +948,16 @@ __global__ void __launch_bounds__(256) randn_plane_kernel(const unsigned long lo
     for (int c = 0; c < 3; ++c) dst[(n * 3 + c) * HW + pix] = z[c];
   }
 }
-hipError_t launch_randn_plane(const unsigned long long* rng, float* dst, int N, int HW, int plane, hipStream_t s) {
+hipError_t launch_randn_plane(const unsigned long long* rng, float* dst, int N, int HW, int plane, hipStream_t s, size_t first_image) {
   const size_t total = (size_t)N * HW;
-  hipLaunchKernelGGL(randn_plane_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rng, dst, HW, 0, 0, plane, total);
+  hipLaunchKernelGGL(randn_plane_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rng, dst, HW, 0, 0, plane, total,
+                     first_image * HW);
   return hipGetLastError();
 }
 hipError_t launch_randn_xin(const unsigned long long* rng, float* xin, int N, int HW, int CP, hipStream_t s, int c_off) {
   const size_t total = (size_t)N * HW;
-  hipLaunchKernelGGL(randn_plane_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rng, xin, HW, CP, c_off, 0, total);
+  hipLaunchKernelGGL(randn_plane_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rng, xin, HW, CP, c_off, 0, total,
+                     (size_t)0);
   return hipGetLastError();
 }
 

@@ -401,7 +401,9 @@ int train_grads_impl(fdsr_handle h, const float* x_nchw, const float* hr_nchw, c
       if ((rc = ensure_rng(h))) return rc;
       float* nz = reinterpret_cast<float*>(ws + tp.off_noise);
       HIPCHK(h, launch_rng_advance(h->d_rng, st));
-      HIPCHK(h, launch_randn_plane(h->d_rng, nz, N, H * W, 0, st));
+      // a shard of a larger batch draws its own images' pixels, as its dropout masks do (else every data-parallel rank under one
+      // seed would train on the same noise)
+      HIPCHK(h, launch_randn_plane(h->d_rng, nz, N, H * W, 0, st, (size_t)g_tun.drop_image_offset));
       target_nchw = nz;
     }
     HIPCHK(h, launch_qsample_pack(hr_nchw, sr_nchw, noise_level, target_nchw, xin, N, H * W, h->CP, st));

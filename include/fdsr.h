@@ -129,7 +129,7 @@ int fdsr_unet_forward(fdsr_handle h, const float* x_nchw, const float* noise_lev
  *                              the `randn_like` of step t = T-k (:189), k=1..T-1;
  *                              or NULL: the engine draws the same planes itself inside the
  *                              loop (Philox4x32-10 + Box-Muller keyed by fdsr_set_seed and a
- *                              per-call counter) -- the throughput mode; parity runs pass noise
+ *                              per-call counter, see fdsr_set_seed) -- the throughput mode; parity runs pass noise
  *   out_nchw  [B,3,H,W]        res2img(x_0, cond) (:214, :275-281) == ret_img[-1]
  *   traj_nchw [T,B,3,H,W] or NULL: x_t after every step (t = T-1..0), for
  *                              continous=True frames and parity tests.
@@ -175,6 +175,22 @@ int fdsr_sample_stepwise(fdsr_handle h, const float* cond_nchw, const float* noi
  * the same images, whatever the batch split or launch geometry.  The reference draws from torch's
  * global generator (diffusion.py:189, :207); its stream is not reproduced, so parity is defined on
  * explicit noise only. */
+/* The generator is Philox4x32-10 (Salmon et al., SC'11); 32-bit counter words (c0, c1, c2, c3) and key words (k0, k1):
+ *   sampler noise, plane p      counter (i lo, i hi, p, calls lo)          key (seed lo, seed hi ^ calls hi)     i = n*H*W + pixel
+ *   self-drawn training target  the same with p = 0 (fdsr_train_grads_pairs, noise == NULL)
+ *   dropout keep bytes          counter (quad lo, quad hi, slot, step)     key (seed lo ^ 0x44524F50, seed hi)   quad = NHWC element / 4
+ * `calls` is zeroed by fdsr_set_seed; every fdsr_sample / fdsr_sample_stepwise that draws its own noise (a replayed graph too: the
+ * counter lives on the device) and every training step that draws its own target adds one BEFORE drawing; fdsr_randn reads it.
+ * Plane 0 is x_T, plane k + 1 the noise of step k.  `slot` is the index of the residual block in network order, `step` the count of
+ * training-mode forwards since fdsr_set_seed / fdsr_set_dropout_seed (the first is 1); word e of quad q decides element 4q + e:
+ * keep = word >= min(floor(p * 2^32), 2^32 - 1) with p the fp32 fdsr_config.dropout.
+ * Normals: the uniform of an output word w is ((float)(w >> 8) + 0.5f) * 2^-24 in fp32, which lies in (0, 1] (the sum rounds to even
+ * above 2^23: w >> 8 == 0xFFFFFF gives exactly 1, w >> 8 == 0 gives 2^-25); z0 = r0 cos(2 pi u1), z1 = r0 sin(2 pi u1),
+ * z2 = r1 cos(2 pi u3), r0 = sqrt(-2 ln u0), r1 = sqrt(-2 ln u2) with logf / sqrtf / sincospif: finite everywhere, |z| <= 5.887,
+ * within 7.7e-7 (measured; test bar 7.1e-6) of the fp64 evaluation on the same uniforms.
+ * Both streams count positions of the GLOBAL batch: i and quad start at a shard's first image when the caller states it (debug option
+ * "drop_image_offset"), for the dropout masks and for the self-drawn training target -- data-parallel ranks under one seed then draw
+ * the slices of the single-process draw; without it every rank draws images [0, N).  fdsr_randn never applies the offset. */
 int fdsr_set_seed(fdsr_handle h, uint64_t seed);
 /* Plane `plane` ([B,3,H,W] fp32, device) of the noise drawn under the current call counter
  * (plane 0 = x_T, plane k = step t = T-k).  For tests of the generator. */
@@ -341,7 +357,8 @@ enum fdsr_strip_bits {
  * workgroup slot in that form, 64-cycle units per K chunk; default 0), "gn_consumer" (0|1: small grids form GroupNorm scale / shift in the consumer conv's prologue from the producers' fixed-point
  * channel-pair sums instead of a gn_finalize launch; default 1), "sat_guard" (0|1), "bf16_f16x3_steps" (probe: bf16 sampling runs the first n, or for n < 0 the last -n, reverse steps on the f16x3 kernels; default 0),
  * "tail" (0|1: the input / output convs of the 16-bit modes on their own bandwidth-shaped kernels),
- * "drop_image_offset" (the batch is images [k, k+N) of a larger one: its dropout masks are those images' masks).
+ * "drop_image_offset" (the batch is images [k, k+N) of a larger one: its dropout masks are those images' masks, and a training step that
+ * draws its own target noise draws those images' pixels).
  * Every setting computes the same function within the tested bounds; they exist so that tests can force each kernel
  * form and same-box A/B runs can price them.  Returns FDSR_E_INVALID for an unknown name.  Not for production use. */
 int fdsr_debug_option(const char* name, long long value);
@@ -409,7 +426,8 @@ int fdsr_train_grads(fdsr_handle h, const float* x_nchw, const float* noise_leve
 /* The same step from the training pair itself: img2res (diffusion.py:283-289), q_sample (:233-241) and cat([SR, x_noisy]) (:257-263)
  * run in the kernel that writes the packed network input (the arithmetic of the tensor torch forms op by op: separately rounded products and sums).  hr / sr / noise:
  * [B,3,H,W] NCHW fp32 device pointers, gamma: [B] (the continuous sqrt(alpha_bar) per sample, :246-256).  noise == NULL: the
- * engine draws N(0,1) itself (Philox, fdsr_set_seed) and uses it as the target. */
+ * engine draws N(0,1) itself and uses it as the target: plane 0 under the call counter after its increment (fdsr_set_seed), what
+ * fdsr_randn(.., plane 0) reports after the step; a shard at "drop_image_offset" k draws images [k, k+N) of that plane. */
 int fdsr_train_grads_pairs(fdsr_handle h, const float* hr_nchw, const float* sr_nchw, const float* gamma, const float* noise_nchw,
                            int loss_l2, float loss_scale, float* loss_host, int batch, int height, int width, void* workspace,
                            size_t workspace_bytes, void* hip_stream);
