@@ -29,6 +29,16 @@ class FdsrSampleOpts(C.Structure):
     _fields_ = [('chunk_steps', C.c_int32), ('traj_every', C.c_int32)]
 
 
+FDSR_NAFNET_MAX_LEVELS = 8
+FDSR_NAFNET_ODE = 2
+
+
+class FdsrNafnetConfig(C.Structure):
+    _fields_ = [('img_channel', C.c_int32), ('width', C.c_int32), ('n_levels', C.c_int32),
+                ('enc_blk_nums', C.c_int32 * FDSR_NAFNET_MAX_LEVELS), ('middle_blk_num', C.c_int32),
+                ('dec_blk_nums', C.c_int32 * FDSR_NAFNET_MAX_LEVELS)]
+
+
 class FdsrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f'libfdsr_hip error {code}: {msg}')
@@ -101,6 +111,22 @@ SYMBOLS = {
     'fdsr_fid_features_u8': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_size_t, C.c_void_p]),
     'fdsr_fid_destroy': (None, [C.c_void_p]),
+    'fdsr_nafnet_create': (C.c_int, [C.POINTER(FdsrNafnetConfig), C.POINTER(C.c_void_p)]),
+    'fdsr_nafnet_num_weights': (C.c_int, [C.c_void_p]),
+    'fdsr_nafnet_weight_info': (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),
+    'fdsr_nafnet_load_weight': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    'fdsr_nafnet_weights_complete': (C.c_int, [C.c_void_p]),
+    'fdsr_nafnet_set_sde': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float]),
+    'fdsr_nafnet_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    'fdsr_nafnet_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                      C.c_size_t, C.c_void_p]),
+    'fdsr_nafnet_sample': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'fdsr_nafnet_debug_tensor': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_size_t, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'fdsr_nafnet_randn': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_void_p]),
+    'fdsr_upscale_bicubic_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'fdsr_nafnet_destroy': (None, [C.c_void_p]),
     'fdsr_set_debug': (C.c_int, [C.c_void_p, C.c_int]),
     'fdsr_debug_option': (C.c_int, [C.c_char_p, C.c_longlong]),
     'fdsr_check_saturation': (C.c_int, [C.c_void_p, C.c_void_p]),

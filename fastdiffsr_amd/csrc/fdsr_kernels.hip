@@ -19,6 +19,7 @@
 // update, layout changes at the boundary) is HBM-bound streaming code.
 #include "fdsr_kernels.h"
 #include "fdsr_act_io.h"
+#include "fdsr_philox.h"
 
 #include <string>
 
@@ -866,37 +867,6 @@ hipError_t launch_nhwc_to_nchw(const float* src, float* dst, int N, int C, int H
 // ---------------------------------------------------------------------------
 // engine-side N(0,1): Philox4x32-10 (Salmon et al., SC'11) + Box-Muller
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigned& c2, unsigned& c3, unsigned k0, unsigned k1) {
-  const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-  const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-  const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-  c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-}
-// three standard normals for pixel `i` of noise plane `plane` under {seed, calls}
-__device__ __forceinline__ void randn3(const unsigned long long* rng, int plane, size_t i, float out[3]) {
-  const unsigned long long seed = rng[0], calls = rng[1];
-  unsigned c0 = (unsigned)i, c1 = (unsigned)(i >> 32), c2 = (unsigned)plane, c3 = (unsigned)calls;
-  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32) ^ (unsigned)(calls >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c0, c1, c2, c3, k0, k1);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  // 24-bit uniforms in (0,1] (above 2^23 the sum rounds to even: 0xFFFFFF gives 1, radius 0; the smallest, 2^-25, gives |z| <= 5.887);
-  // Box-Muller on two pairs (the fourth normal is not used)
-  const float u0 = ((float)(c0 >> 8) + 0.5f) * 5.9604644775390625e-8f, u1 = ((float)(c1 >> 8) + 0.5f) * 5.9604644775390625e-8f;
-  const float u2 = ((float)(c2 >> 8) + 0.5f) * 5.9604644775390625e-8f, u3 = ((float)(c3 >> 8) + 0.5f) * 5.9604644775390625e-8f;
-  const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
-  float s0, cs0, s1, cs1;
-  sincospif(2.0f * u1, &s0, &cs0);
-  sincospif(2.0f * u3, &s1, &cs1);
-  out[0] = r0 * cs0;
-  out[1] = r0 * s0;
-  out[2] = r1 * cs1;
-  (void)s1;
-}
-
 __global__ void rng_advance_kernel(unsigned long long* rng) {
   if (threadIdx.x == 0 && blockIdx.x == 0) rng[1] += 1ull;
 }

@@ -1,0 +1,229 @@
+"""ConditionalNAFNet on the HIP engine (include/fdsr.h: fdsr_nafnet_*): an nn.Module that owns the reference's parameters
+under the reference's names -- `latest_G.pth` loads with load_state_dict(strict=True) -- and whose forward runs the device
+kernels.  Sampling only: there is no backward pass, and no PyTorch fallback."""
+import ctypes as C
+
+import torch
+import torch.nn as nn
+
+from .. import _lib
+from .arch import NAFNetConfig, param_schema, tap_names
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
+
+
+class ConditionalNAFNet(nn.Module):
+    def __init__(self, img_channel=3, width=16, middle_blk_num=1, enc_blk_nums=(), dec_blk_nums=(), upscale=1):
+        super().__init__()
+        self.upscale = upscale
+        self.cfg = NAFNetConfig(img_channel, width, middle_blk_num, list(enc_blk_nums), list(dec_blk_nums))
+        self.padder_size = self.cfg.padder_size
+        self.schema = param_schema(self.cfg)
+        # flat registration under dotted names is not allowed by nn.Module, so the tensors live in a ParameterDict-like
+        # table of their own and state_dict / load_state_dict speak the reference's keys (see _save_to_state_dict)
+        self._names = list(self.schema)
+        for i, (k, shape) in enumerate(self.schema.items()):
+            self.register_parameter('p%d' % i, nn.Parameter(torch.zeros(shape), requires_grad=False))
+        self._h = None
+        self._uploaded = None      # (device, versions) of the last upload
+        self._ws = {}
+
+    # ---- the reference's keys ----
+    def _save_to_state_dict(self, destination, prefix, keep_vars):
+        for i, k in enumerate(self._names):
+            p = getattr(self, 'p%d' % i)
+            destination[prefix + k] = p if keep_vars else p.detach()
+
+    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
+        for i, k in enumerate(self._names):
+            key = prefix + k
+            if key not in state_dict:
+                if strict:
+                    missing_keys.append(key)
+                continue
+            src, p = state_dict[key], getattr(self, 'p%d' % i)
+            if tuple(src.shape) != tuple(p.shape):
+                error_msgs.append('size mismatch for %s: copying a param with shape %s from checkpoint, the shape in current '
+                                  'model is %s.' % (key, tuple(src.shape), tuple(p.shape)))
+                continue
+            with torch.no_grad():
+                p.copy_(src)
+        if strict:
+            known = {prefix + k for k in self._names}
+            unexpected_keys += [k for k in state_dict if k.startswith(prefix) and k not in known]
+
+    def named_reference_parameters(self):
+        return [(k, getattr(self, 'p%d' % i)) for i, k in enumerate(self._names)]
+
+    # ---- the engine ----
+    def _handle(self):
+        if self._h is None:
+            lib = _lib.load()
+            c = _lib.FdsrNafnetConfig()
+            c.img_channel, c.width, c.middle_blk_num = self.cfg.img_channel, self.cfg.width, self.cfg.middle_blk_num
+            c.n_levels = len(self.cfg.enc_blk_nums)
+            if c.n_levels > _lib.FDSR_NAFNET_MAX_LEVELS:
+                raise ValueError('at most %d levels' % _lib.FDSR_NAFNET_MAX_LEVELS)
+            for i, (e, d) in enumerate(zip(self.cfg.enc_blk_nums, self.cfg.dec_blk_nums)):
+                c.enc_blk_nums[i], c.dec_blk_nums[i] = e, d
+            h = C.c_void_p()
+            _lib.check(None, lib.fdsr_nafnet_create(C.byref(c), C.byref(h)))
+            self._h = h
+        return self._h
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h is not None and _lib._lib is not None:
+            _lib._lib.fdsr_nafnet_destroy(h)
+            self._h = None
+
+    def engine_schema(self):
+        """[(key, shape)] as the library lists them (fdsr_nafnet_weight_info)."""
+        lib, h = _lib.load(), self._handle()
+        out = []
+        for i in range(lib.fdsr_nafnet_num_weights(h)):
+            key, shape, nd = C.create_string_buffer(256), (C.c_int64 * 4)(), C.c_int()
+            _lib.check(None, lib.fdsr_nafnet_weight_info(h, i, key, 256, shape, C.byref(nd)))
+            out.append((key.value.decode(), tuple(shape[:nd.value])))
+        return out
+
+    def sync_weights(self, device):
+        """Upload the parameters when they changed since the last upload (tensor versions, as unet.py does)."""
+        params = [p for _, p in self.named_reference_parameters()]
+        stamp = (str(device), tuple((p.data_ptr(), p._version) for p in params))
+        if stamp == self._uploaded:
+            return
+        lib, h = _lib.load(), self._handle()
+        with torch.cuda.device(device):
+            for k, p in zip(self._names, params):
+                a = p.detach().to('cpu', torch.float32).contiguous()
+                shape = (C.c_int64 * a.dim())(*a.shape)
+                _lib.check(None, lib.fdsr_nafnet_load_weight(h, k.encode(), _ptr(a), shape, a.dim()))
+        self._uploaded = stamp
+
+    def workspace(self, b, h, w, device):
+        need = C.c_size_t()
+        _lib.check(None, _lib.load().fdsr_nafnet_workspace_bytes(self._handle(), b, h, w, C.byref(need)))
+        key = (str(device), torch.cuda.current_stream(device).cuda_stream)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need.value:
+            ws = self._ws[key] = torch.empty(need.value, dtype=torch.uint8, device=device)
+        return ws
+
+    @staticmethod
+    def _check_pair(x, cond):
+        if not (x.is_cuda and cond.is_cuda and x.dim() == 4 and x.shape[1] == 3 and x.shape == cond.shape):
+            raise ValueError('ConditionalNAFNet takes two [B,3,H,W] tensors on the GPU (there is no CPU path)')
+        return x.float().contiguous(), cond.float().contiguous()
+
+    def _times(self, time, b, device):
+        if isinstance(time, (int, float)):
+            time = torch.tensor([time])
+        t = torch.as_tensor(time).to(device=device, dtype=torch.float32).reshape(-1)
+        if t.numel() == 1:
+            t = t.expand(b)
+        if t.numel() != b:
+            raise ValueError('time must be a scalar or one value per image')
+        return t.contiguous()
+
+    def forward(self, inp, cond, time):
+        if torch.is_grad_enabled() and any(p.requires_grad for _, p in self.named_reference_parameters()):
+            raise NotImplementedError('EDiffSR training is not implemented on this engine (sampling only)')
+        x, cond = self._check_pair(inp, cond)
+        b, _, h, w = x.shape
+        self.sync_weights(x.device)
+        with torch.cuda.device(x.device):
+            t = self._times(time, b, x.device)
+            out = torch.empty_like(x)
+            ws = self.workspace(b, h, w, x.device)
+            st = torch.cuda.current_stream(x.device).cuda_stream
+            _lib.check(None, _lib.load().fdsr_nafnet_forward(self._handle(), _ptr(x), _ptr(cond), _ptr(t), _ptr(out), b, h, w,
+                                                             _ptr(ws), ws.numel(), C.c_void_p(st)))
+        return out
+
+    def debug_tensor(self, name, inp, cond, time):
+        """The named tap of one forward (arch.tap_names), NCHW at the tap's padded size."""
+        x, cond = self._check_pair(inp, cond)
+        b, _, h, w = x.shape
+        self.sync_weights(x.device)
+        pad = self.padder_size
+        hp, wp = -(-h // pad) * pad, -(-w // pad) * pad
+        with torch.cuda.device(x.device):
+            t = self._times(time, b, x.device)
+            cap = b * hp * wp * self.cfg.width
+            out = torch.empty(cap, dtype=torch.float32, device=x.device)
+            dims = (C.c_int * 3)()
+            ws = self.workspace(b, h, w, x.device)
+            st = torch.cuda.current_stream(x.device).cuda_stream
+            _lib.check(None, _lib.load().fdsr_nafnet_debug_tensor(self._handle(), name.encode(), _ptr(x), _ptr(cond), _ptr(t), b, h, w,
+                                                                  _ptr(out), cap, dims, _ptr(ws), ws.numel(), C.c_void_p(st)))
+        th, tw, tc = dims[0], dims[1], dims[2]
+        return out[:b * th * tw * tc].view(b, th, tw, tc).permute(0, 3, 1, 2).contiguous()
+
+    def set_sde(self, thetas, sigmas, sigma_bars, dt, device):
+        T = thetas.numel() - 1
+        arr = [a.detach().to('cpu', torch.float32).contiguous() for a in (thetas, sigmas, sigma_bars)]
+        f = C.POINTER(C.c_float)
+        with torch.cuda.device(device):
+            _lib.check(None, _lib.load().fdsr_nafnet_set_sde(self._handle(), T, *[C.cast(a.data_ptr(), f) for a in arr], float(dt)))
+
+    def sample(self, state, cond, noise=None, seed=0, first_image=0, graph=False, ode=False, trajectory=False):
+        """IRSDE.reverse_sde / reverse_ode in one engine call (set_sde first).  noise [T,B,3,H,W] or None (engine draws)."""
+        x, cond = self._check_pair(state, cond)
+        b, _, h, w = x.shape
+        self.sync_weights(x.device)
+        flags = (_lib.FDSR_SAMPLE_GRAPH if graph else 0) | (_lib.FDSR_NAFNET_ODE if ode else 0)
+        with torch.cuda.device(x.device):
+            if noise is not None:
+                noise = noise.to(x.device, torch.float32).contiguous()
+                if noise.dim() != 5 or tuple(noise.shape[1:]) != tuple(x.shape):
+                    raise ValueError('noise must be [T,B,3,H,W]')
+            out = torch.empty_like(x)
+            traj = torch.empty((self._T(),) + tuple(x.shape), dtype=torch.float32, device=x.device) if trajectory else None
+            ws = self.workspace(b, h, w, x.device)
+            stream = torch.cuda.current_stream(x.device)
+            if graph and stream.cuda_stream == 0:
+                if not hasattr(self, '_graph_stream'):
+                    self._graph_stream = torch.cuda.Stream(x.device)
+                side = self._graph_stream
+                side.wait_stream(stream)
+                with torch.cuda.stream(side):
+                    ws = self.workspace(b, h, w, x.device)
+                    self._sample_call(x, cond, noise, seed, first_image, flags, out, traj, b, h, w, ws, side.cuda_stream)
+                stream.wait_stream(side)
+            else:
+                self._sample_call(x, cond, noise, seed, first_image, flags, out, traj, b, h, w, ws, stream.cuda_stream)
+        return (out, traj) if trajectory else out
+
+    def _T(self):
+        if getattr(self, '_sde_T', None) is None:
+            raise RuntimeError('set an IRSDE first (IRSDE.set_model)')
+        return self._sde_T
+
+    def _sample_call(self, x, cond, noise, seed, first_image, flags, out, traj, b, h, w, ws, st):
+        _lib.check(None, _lib.load().fdsr_nafnet_sample(self._handle(), _ptr(x), _ptr(cond), _ptr(noise), int(seed), int(first_image), flags,
+                                                        _ptr(out), _ptr(traj), b, h, w, _ptr(ws), ws.numel(), C.c_void_p(st)))
+
+    def randn(self, b, h, w, plane, seed, first_image=0, device=None):
+        """Plane `plane` of the engine's own noise stream (include/fdsr.h), [B,3,H,W]."""
+        device = device or next(self.parameters()).device
+        out = torch.empty((b, 3, h, w), dtype=torch.float32, device=device)
+        with torch.cuda.device(device):
+            st = torch.cuda.current_stream(device).cuda_stream
+            _lib.check(None, _lib.load().fdsr_nafnet_randn(_ptr(out), b, h, w, plane, int(seed), int(first_image), C.c_void_p(st)))
+        return out
+
+
+def upscale(x, scale):
+    """util.upscale on the device: F.interpolate(x, scale_factor=scale, mode='bicubic') for fp32 NCHW CUDA tensors."""
+    if not x.is_cuda or x.dim() != 4:
+        raise ValueError('upscale takes a [B,C,H,W] tensor on the GPU')
+    x = x.float().contiguous()
+    b, c, h, w = x.shape
+    out = torch.empty((b, c, h * scale, w * scale), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(None, _lib.load().fdsr_upscale_bicubic_f32(_ptr(x), _ptr(out), b, c, h, w, int(scale), C.c_void_p(st)))
+    return out

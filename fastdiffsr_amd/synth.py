@@ -109,3 +109,26 @@ def synth_inception_fid(seed: int = 0) -> "OrderedDict[str, np.ndarray]":
             x = np.ones(shape)
         out[k] = x.astype(np.float32)
     return out
+
+
+def synth_nafnet(seed: int = 0, width: int = 16, enc_blk_nums=(2, 1, 1, 1), middle_blk_num: int = 1, dec_blk_nums=(1, 1, 1, 1),
+                 img_channel: int = 3) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights for EDiffSR's ConditionalNAFNet, keyed and ordered as ediffsr.arch.param_schema.  The reference
+    initialises every beta / gamma to ZERO, which makes every NAFBlock the identity; here beta, gamma ~ 0.3 N(0,1), biases
+    0.05 N(0,1), LayerNorm g = 1 + 0.1 N(0,1), conv / linear weights N(0, 1/(3 fan_in)) (the variance of torch's default
+    kaiming_uniform(a=sqrt(5)) init) -- every tensor from its own key."""
+    from .ediffsr.arch import NAFNetConfig, param_schema as naf_schema
+    cfg = NAFNetConfig(img_channel, width, middle_blk_num, list(enc_blk_nums), list(dec_blk_nums))
+    out = OrderedDict()
+    for k, shape in naf_schema(cfg).items():
+        x = _rng('nafnet:' + k, seed).standard_normal(size=shape, dtype=np.float64)
+        if k.endswith(('.beta', '.gamma')):
+            x *= 0.3
+        elif k.endswith('.bias'):
+            x *= 0.05
+        elif k.endswith('.g'):
+            x = 1.0 + 0.1 * x
+        else:
+            x *= np.sqrt(1.0 / (3 * int(np.prod(shape[1:]))))
+        out[k] = x.astype(np.float32)
+    return out

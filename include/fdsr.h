@@ -295,7 +295,79 @@ int fdsr_fid_features_u8(fdsr_fid f, const uint8_t* img_nhwc, int batch, int hei
                          void* workspace, size_t workspace_bytes, void* hip_stream);
 void fdsr_fid_destroy(fdsr_fid f);
 
-/* -- input-pipeline helper ------------------------------------ */
+/* -- EDiffSR: ConditionalNAFNet noise predictor + IR-SDE reverse process (EDiffSR/codes: DenoisingNAFNet_arch.py,
+ * module_util.py, utils/sde_utils.py) --------------------------------------------------------------------------------
+ * An object of its own, independent of fdsr_handle.  fp32 activations (NHWC inside), every 1x1 / 2x2 / 3x3 convolution a GEMM
+ * on v_mfma_f32_32x32x2_f32 (exact fp32, a k-ordered chain per output, no split-K), LayerNorm over channels with eps 1e-5,
+ * fixed-order pools: reruns are bitwise identical and an image's result depends neither on B nor on its position in the batch.
+ * Weights: host fp32 tensors under the reference's state_dict keys and shapes (fdsr_nafnet_weight_info lists them in
+ * state_dict order; fastdiffsr_amd/ediffsr/arch.py is the Python twin).  Unknown key or wrong shape: FDSR_E_KEY.
+ * Inputs are [B,3,H,W] fp32 NCHW device tensors of any H, W >= 1: the network pads right / bottom with zeros to a multiple of
+ * 2^n_levels and crops its output (check_image_size).
+ *   fdsr_nafnet_forward   out = model(x, cond, time): the noise prediction; time_dev [B] fp32 device, one value per image
+ *                         (the reference's scalar time is that value repeated).
+ *   fdsr_nafnet_set_sde   IRSDE's tables as the reference holds them: thetas / sigmas / sigma_bars [T+1] host fp32 (index 0 unused
+ *                         by the loop), dt; sqrt(dt) is formed as (float)sqrt((double)dt), math.sqrt's value.
+ *   fdsr_nafnet_sample    IRSDE.reverse_sde (reverse_ode under FDSR_NAFNET_ODE) with mu = cond, t = T .. 1:
+ *                           score = -model(x, cond, t) / sigma_bar[t]
+ *                           x <- x - (theta[t] (cond - x) - sigma[t]^2 score) dt - sigma[t] (eps sqrt(dt))         (SDE)
+ *                           x <- x - (theta[t] (cond - x) - 0.5 sigma[t]^2 score) dt                                (ODE)
+ *                         every operation rounded to fp32 in the order written (no contraction).
+ *                           state [B,3,H,W]  x_T (IRSDE.noise_state of the upscaled LQ image);  out [B,3,H,W]  x_0
+ *                           noise [T,B,3,H,W], plane k = the eps of step t = T - k; or NULL: drawn per step with the library's
+ *                             Philox4x32-10 normals (see fdsr_set_seed for the generator): counter (i lo, i hi, k, 0),
+ *                             key (seed lo, seed hi), i = (first_image + n)*H*W + pixel -- positions of a GLOBAL image index, so a
+ *                             run split into batches draws what the unsplit run draws when each call states its first image.
+ *                             fdsr_nafnet_randn writes plane k of that stream.  Ignored under FDSR_NAFNET_ODE.
+ *                           traj [T,B,3,H,W] or NULL: x after every step (plane k = after step t = T - k)
+ *                         flags: FDSR_SAMPLE_GRAPH captures ONE step (a linear graph on hip_stream, which must be a created
+ *                           stream) whose per-step values -- the time-embedding rows, theta / sigma / sigma_bar, the noise plane --
+ *                           are read from device tables through a device-side step counter, and replays it T times.  Eager runs
+ *                           launch the same kernels with the same arguments: the results are bitwise equal.  One graph is cached per
+ *                           object (key: pointers, shape, flags); loading a weight or a schedule drops it.
+ *   fdsr_nafnet_debug_tensor  runs the forward up to the named tap and copies it out as NHWC [B][h][w][c] (dims3 = {h, w, c}; the
+ *                         padded size at the tap's level): "intro", "enhance" (x + enhance(x)), "encoders.<i>.<j>", "downs.<i>",
+ *                         "middle_blks.<j>", "ups.<i>" (after + enc_skip), "decoders.<i>.<j>", "ending" (before the crop).
+ *                         Unknown name: FDSR_E_KEY; capacity_floats too small: FDSR_E_INVALID.
+ *   fdsr_upscale_bicubic_f32  util.upscale: F.interpolate(scale_factor=scale, mode='bicubic', align_corners=False) on fp32 NCHW
+ *                         (A = -0.75, source index (d + 0.5) / scale - 0.5, taps clamped to the image), evaluated in fp64 and
+ *                         rounded once.  dst [B,C,h*scale,w*scale].
+ * FDSR_E_STATE: a weight is missing, or fdsr_nafnet_sample before fdsr_nafnet_set_sde.  FDSR_E_WORKSPACE: workspace (256-byte
+ * aligned) too small.  Stream-ordered, no implicit synchronisation (loading weights / tables is host-synchronous).  Calls on one
+ * object must be ordered on one stream.  Messages: fdsr_last_error(NULL). */
+#define FDSR_NAFNET_MAX_LEVELS 8
+#define FDSR_NAFNET_ODE 2
+typedef struct fdsr_nafnet_config {
+  int32_t img_channel;                            /* 3 */
+  int32_t width;                                  /* a multiple of 16 */
+  int32_t n_levels;                               /* len(enc_blk_nums) == len(dec_blk_nums), 1..FDSR_NAFNET_MAX_LEVELS */
+  int32_t enc_blk_nums[FDSR_NAFNET_MAX_LEVELS];
+  int32_t middle_blk_num;
+  int32_t dec_blk_nums[FDSR_NAFNET_MAX_LEVELS];
+} fdsr_nafnet_config;
+typedef struct fdsr_nafnet_obj* fdsr_nafnet;
+int fdsr_nafnet_create(const fdsr_nafnet_config* cfg, fdsr_nafnet* out);
+int fdsr_nafnet_num_weights(fdsr_nafnet n);
+int fdsr_nafnet_weight_info(fdsr_nafnet n, int index, char* key, int key_capacity, int64_t* shape4, int* ndim);
+int fdsr_nafnet_load_weight(fdsr_nafnet n, const char* key, const float* host_f32, const int64_t* shape, int ndim);
+int fdsr_nafnet_weights_complete(fdsr_nafnet n);   /* 1: every tensor is loaded, 0: not yet */
+int fdsr_nafnet_set_sde(fdsr_nafnet n, int T, const float* thetas, const float* sigmas, const float* sigma_bars, float dt);
+int fdsr_nafnet_workspace_bytes(fdsr_nafnet n, int batch, int height, int width, size_t* bytes);
+int fdsr_nafnet_forward(fdsr_nafnet n, const float* x_nchw, const float* cond_nchw, const float* time_dev, float* out_nchw, int batch,
+                        int height, int width, void* workspace, size_t workspace_bytes, void* hip_stream);
+int fdsr_nafnet_sample(fdsr_nafnet n, const float* state_nchw, const float* cond_nchw, const float* noise, uint64_t seed,
+                       int64_t first_image, int flags, float* out_nchw, float* traj, int batch, int height, int width,
+                       void* workspace, size_t workspace_bytes, void* hip_stream);
+int fdsr_nafnet_debug_tensor(fdsr_nafnet n, const char* name, const float* x_nchw, const float* cond_nchw, const float* time_dev,
+                             int batch, int height, int width, float* out_nhwc, size_t capacity_floats, int* dims3, void* workspace,
+                             size_t workspace_bytes, void* hip_stream);
+int fdsr_nafnet_randn(float* dst_nchw, int batch, int height, int width, int plane, uint64_t seed, int64_t first_image,
+                      void* hip_stream);
+int fdsr_upscale_bicubic_f32(const float* src_nchw, float* dst_nchw, int batch, int channels, int height, int width, int scale,
+                             void* hip_stream);
+void fdsr_nafnet_destroy(fdsr_nafnet n);
+
+/* -- input-pipeline helper------------------------------------ */
 /* The dataset's tensor transform on the device (data/util.py:66-75 transform_augment: ToTensor() = uint8 / 255 as fp32,
  * HWC -> CHW, then img * (hi - lo) + lo; LRHR_dataset.py:113-119 passes min_max = (-1, 1)): the loader threads hand over
  * the decoded uint8 batch, one byte per sample crosses PCIe.  src [B,H,W,C] uint8 device, dst [B,C,H,W] fp32 device,

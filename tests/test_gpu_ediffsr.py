@@ -1,0 +1,262 @@
+"""EDiffSR on the device against tests/ediffsr_restatement.py (itself pinned to the reference's modules by
+tests/golden/ediffsr.npz).  The bar everywhere is the rule of test_gpu_fid.py: 4 x the restatement's own fp32-vs-fp64
+spread, never looser than 1e-4 max|ref|; every measured value is printed before it is judged."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import ediffsr_restatement as R
+import philox_reference as P
+
+pytestmark = pytest.mark.gpu
+
+TEST_SETTING = dict(width=16, enc_blk_nums=[2, 1, 1, 1], middle_blk_num=1, dec_blk_nums=[1, 1, 1, 1])
+SHIPPED_SETTING = dict(width=64, enc_blk_nums=[14, 1, 1, 1], middle_blk_num=1, dec_blk_nums=[1, 1, 1, 1])
+DEV = 'cuda'
+
+
+def _inputs(seed, b, h, w):
+    g = torch.Generator().manual_seed(seed)
+    cond = torch.rand(b, 3, h, w, generator=g)
+    return cond + torch.randn(b, 3, h, w, generator=g) * (50 / 255), cond
+
+
+def _bound(r64, r32):
+    spread = float((r32.double() - r64).abs().max())
+    return min(4 * spread, 1e-4 * float(r64.abs().max())), spread
+
+
+def _judge(name, dev, r64, r32, scale=None):
+    bound, spread = _bound(r64, r32)
+    d = float((dev.double().cpu() - r64).abs().max())
+    print('%-16s max|dev - f64| %.3g  f32-f64 spread %.3g  bound %.3g  max|ref| %.3g' % (name, d, spread, bound, float(r64.abs().max())))
+    return d <= bound, name
+
+
+def _model(setting, seed=0):
+    from fastdiffsr_amd.ediffsr import ConditionalNAFNet
+    from fastdiffsr_amd.synth import synth_nafnet
+    sd = {k: torch.from_numpy(v) for k, v in synth_nafnet(seed, **setting).items()}
+    m = ConditionalNAFNet(**setting)
+    m.load_state_dict(sd, strict=True)
+    return m.to(DEV).eval(), sd
+
+
+@pytest.fixture(scope='module')
+def net():
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    return _model(TEST_SETTING)
+
+
+@pytest.mark.parametrize('hw', [(36, 44), (32, 32)])
+def test_layerwise_and_forward(net, hw):
+    from fastdiffsr_amd.ediffsr.arch import tap_names
+    m, sd = net
+    x, cond = _inputs(21, 2, *hw)
+    t32, t64 = {}, {}
+    with torch.no_grad():
+        y32 = R.forward(sd, x, cond, 37, t32)
+        y64 = R.forward(R.cast_sd(sd, torch.float64), x.double(), cond.double(), 37, t64)
+    fails = []
+    for name in tap_names(m.cfg):
+        ok, _ = _judge(name, m.debug_tensor(name, x.to(DEV), cond.to(DEV), 37), t64[name], t32[name])
+        if not ok:
+            fails.append(name)
+    ok, _ = _judge('output', m(x.to(DEV), cond.to(DEV), 37), y64, y32)
+    assert ok and not fails, fails
+
+
+def test_forward_per_image_float_times(net):
+    m, sd = net
+    x, cond = _inputs(22, 3, 36, 44)
+    t = torch.tensor([3.25, 58.5, 99.0])
+    with torch.no_grad():
+        y32 = R.forward(sd, x, cond, t)
+        y64 = R.forward(R.cast_sd(sd, torch.float64), x.double(), cond.double(), t)
+    ok, _ = _judge('float times', m(x.to(DEV), cond.to(DEV), t.to(DEV)), y64, y32)
+    assert ok
+    one = m(x[1:2].to(DEV), cond[1:2].to(DEV), 58.5)
+    assert torch.equal(one, m(x.to(DEV), cond.to(DEV), t.to(DEV))[1:2])
+
+
+def test_forward_shipped_setting():
+    m, sd = _model(SHIPPED_SETTING)
+    x, cond = _inputs(23, 2, 32, 32)
+    with torch.no_grad():
+        y32 = R.forward(sd, x, cond, 50)
+        y64 = R.forward(R.cast_sd(sd, torch.float64), x.double(), cond.double(), 50)
+    ok, _ = _judge('shipped output', m(x.to(DEV), cond.to(DEV), 50), y64, y32)
+    assert ok
+
+
+def _loop(m, sd, T, eps, hw, ode=False, seed=31):
+    """device trajectory, fp32 and fp64 restatement trajectories of one loop with explicit noise"""
+    from fastdiffsr_amd.ediffsr.sde import IRSDE
+    s = IRSDE(max_sigma=50, T=T, schedule='cosine', eps=eps, device='cpu')
+    s.set_model(m)
+    state, cond = _inputs(seed, 1, *hw)
+    noise = torch.randn(T, 1, 3, *hw, generator=torch.Generator().manual_seed(seed + 1))
+    tr32, tr64 = [], []
+    with torch.no_grad():
+        R.reverse_loop(sd, R.cast_tables(s, torch.float32), state, cond, noise, ode, tr32)
+        R.reverse_loop(R.cast_sd(sd, torch.float64), R.cast_tables(s, torch.float64), state.double(), cond.double(), noise.double(), ode, tr64)
+    s.set_mu(cond.to(DEV))
+    if ode:
+        out, traj = s.reverse_ode(state.to(DEV), trajectory=True)
+    else:
+        out, traj = s.reverse_sde(state.to(DEV), noise=noise.to(DEV), trajectory=True)
+    assert torch.equal(out, traj[-1])
+    return traj.cpu(), torch.stack(tr32), torch.stack(tr64)
+
+
+def test_loop_mild_schedule(net):
+    """IRSDE(T=10, eps=0.5): every step of the trajectory against the restatement, the 4 x spread / 1e-4 rule per step."""
+    m, sd = net
+    traj, t32, t64 = _loop(m, sd, 10, 0.5, (36, 44))
+    assert torch.isfinite(traj).all()
+    oks = [_judge('step %d' % k, traj[k], t64[k], t32[k])[0] for k in range(10)]
+    assert all(oks)
+
+
+def test_loop_ode(net):
+    m, sd = net
+    traj, t32, t64 = _loop(m, sd, 10, 0.5, (32, 32), ode=True)
+    oks = [_judge('ode step %d' % k, traj[k], t64[k], t32[k])[0] for k in range(10)]
+    assert all(oks)
+
+
+def test_loop_reference_schedule(net):
+    """T 100, eps 0.005 (the shipped options).  The reverse IR-SDE amplifies any deviation from mu by up to 1 / eps = 200 unless
+    the score cancels it, and synthetic weights do not: the state grows, and so does every rounding difference.  The loop is
+    therefore judged RELATIVE TO max|x| of the fp64 trajectory: max over the steps of |dev - f64| <= min(4 x spread, 1e-4 max|x|),
+    spread = max over the steps of |f32 - f64| of the restatement, and the state must stay finite and below 1e3.
+    Measured with synth_nafnet(0) at 32x32 (CPU restatement): max|x| 347, f32-f64 spread 2.4e-4 (6.8e-7 of max|x|); the device's
+    own distance is printed by the test.  (With conv weights of variance 1 / fan_in instead of synth_nafnet's 1 / (3 fan_in) the
+    same loop reaches max|x| 1.7e6, spread 0.56, device 0.42: the relative picture is the same.)"""
+    m, sd = net
+    traj, t32, t64 = _loop(m, sd, 100, 0.005, (32, 32))
+    assert torch.isfinite(traj).all()
+    peak = float(t64.abs().max())
+    spread = float((t32.double() - t64).abs().max())
+    d = float((traj.double() - t64).abs().max())
+    print('T=100: max|x| %.4g  f32-f64 spread %.3g (%.3g of max|x|)  max|dev - f64| %.3g  final-state dev %.3g' %
+          (peak, spread, spread / peak, d, float((traj[-1].double() - t64[-1]).abs().max())))
+    assert peak < 1e3
+    assert d <= min(4 * spread, 1e-4 * peak)
+
+
+def test_properties_bitwise(net):
+    from fastdiffsr_amd.ediffsr.sde import IRSDE
+    m, sd = net
+    T, hw = 6, (36, 44)
+    s = IRSDE(max_sigma=50, T=T, schedule='cosine', eps=0.5, device='cpu')
+    s.set_model(m)
+    state, cond = _inputs(41, 5, *hw)
+    noise = torch.randn(T, 5, 3, *hw, generator=torch.Generator().manual_seed(42))
+    state, cond, noise = state.to(DEV), cond.to(DEV), noise.to(DEV)
+    a, ta = m.sample(state, cond, noise=noise, trajectory=True)
+    b, tb = m.sample(state, cond, noise=noise, trajectory=True)
+    assert torch.equal(a, b) and torch.equal(ta, tb), 'rerun'
+    g, tg = m.sample(state, cond, noise=noise, trajectory=True, graph=True)
+    assert torch.equal(a, g) and torch.equal(ta, tg), 'graph == eager'
+    g2 = m.sample(state, cond, noise=noise, graph=True)
+    assert torch.equal(a, g2), 'graph replay'
+    one = m.sample(state[3:4], cond[3:4], noise=noise[:, 3:4].contiguous())
+    assert torch.equal(one, a[3:4]), 'B = 1 vs index 3 of B = 5'
+    # the engine's own draws: plane k of the documented stream, and a run on them equals a run on the same planes passed in
+    seed = 0x5EED
+    planes = torch.stack([m.randn(5, *hw, k, seed, device=DEV) for k in range(T)])
+    for k in (0, T - 1):
+        ref = P.randn_plane(seed, 0, k, 5, *hw)
+        d = float(np.abs(planes[k].cpu().numpy().astype(np.float64) - ref).max())
+        print('plane %d: max|device - philox_reference| %.3g' % (k, d))
+        assert d <= 7.1e-6      # the bar of tests/test_gpu_rng_reference.py: 4 x the fp32 restatement's gap to fp64
+    drawn = m.sample(state, cond, noise=None, seed=seed)
+    assert torch.equal(drawn, m.sample(state, cond, noise=planes)), 'noise = NULL under a seed == the documented planes'
+    assert torch.equal(drawn, m.sample(state, cond, noise=None, seed=seed, graph=True))
+    part = m.sample(state[3:5], cond[3:5], noise=None, seed=seed, first_image=3)
+    assert torch.equal(part, drawn[3:5]), 'stream positions are per global image index'
+    assert not torch.equal(drawn, m.sample(state, cond, noise=None, seed=seed + 1))
+
+
+@pytest.mark.parametrize('scale,hw', [(4, (9, 7)), (8, (5, 11)), (4, (64, 64))])
+def test_upscale_bicubic(scale, hw):
+    from fastdiffsr_amd.ediffsr.model import upscale
+    lq = torch.rand(2, 3, *hw, generator=torch.Generator().manual_seed(51))
+    r32 = torch.nn.functional.interpolate(lq, scale_factor=scale, mode='bicubic')
+    r64 = torch.nn.functional.interpolate(lq.double(), scale_factor=scale, mode='bicubic')
+    spread = float((r32.double() - r64).abs().max())
+    bound = max(4 * spread, 2.0 ** -22)
+    d = float((upscale(lq.to(DEV), scale).double().cpu() - r64).abs().max())
+    print('x%d %s: max|dev - f64| %.3g  torch f32-f64 spread %.3g  bound %.3g' % (scale, hw, d, spread, bound))
+    assert d <= bound
+
+
+def test_upscale_matches_the_golden():
+    from fastdiffsr_amd.ediffsr.model import upscale
+    with np.load(os.path.join(os.path.dirname(__file__), 'golden', 'ediffsr.npz')) as f:
+        src, ref = torch.from_numpy(f['up_src']), f['up_x4']
+    d = float(np.abs(upscale(src.to(DEV), 4).cpu().numpy() - ref).max())
+    print('golden upscale: %.3g' % d)
+    assert d <= 2.0 ** -21
+
+
+def _write_pairs(root, n=8):
+    from PIL import Image
+    g = np.random.default_rng(61)
+    os.makedirs(os.path.join(root, 'hr'))
+    os.makedirs(os.path.join(root, 'lr'))
+    for i in range(n):
+        hr = (np.clip(g.normal(0.5, 0.2, (256, 256, 3)), 0, 1) * 255).astype(np.uint8)
+        hr[:, :, 0] //= 2                                  # unequal channels: a BGR / RGB mix-up would show
+        Image.fromarray(hr).save(os.path.join(root, 'hr', '%02d.png' % i))
+        Image.fromarray(hr.reshape(64, 4, 64, 4, 3).mean(axis=(1, 3)).astype(np.uint8)).save(os.path.join(root, 'lr', '%02d.png' % i))
+
+
+def test_cli_end_to_end(tmp_path):
+    """Eight synthetic 64^2 -> 256^2 pairs, the test-setting network saved as latest_G.pth, T 10 / eps 0.5 options.  The stream
+    positions are per global image index (include/fdsr.h), so --batch 4 gives --batch 1's per-image numbers under --rng engine."""
+    import yaml
+    from PIL import Image
+    from fastdiffsr_amd import metrics as M
+    from fastdiffsr_amd.ediffsr import test as cli
+    from fastdiffsr_amd.ediffsr.model import upscale
+    from fastdiffsr_amd.ediffsr.sde import IRSDE
+    from fastdiffsr_amd.synth import synth_nafnet
+    root = str(tmp_path)
+    _write_pairs(root)
+    sd = {k: torch.from_numpy(v) for k, v in synth_nafnet(0, **TEST_SETTING).items()}
+    torch.save(sd, os.path.join(root, 'latest_G.pth'))
+    opt = {'name': 'Test-x4', 'suffix': None, 'sde': {'max_sigma': 50, 'T': 10, 'schedule': 'cosine', 'eps': 0.5},
+           'degradation': {'scale': 4}, 'path': {'pretrain_model_G': os.path.join(root, 'latest_G.pth')},
+           'datasets': {'test1': {'name': 'synth', 'mode': 'LQGT', 'dataroot_GT': os.path.join(root, 'hr'), 'dataroot_LQ': os.path.join(root, 'lr')}},
+           'network_G': {'which_model_G': 'ConditionalNAFNet', 'setting': TEST_SETTING}}
+    with open(os.path.join(root, 'opt.yml'), 'w') as f:
+        yaml.safe_dump(opt, f)
+    r1 = cli.main(['-opt', os.path.join(root, 'opt.yml'), '--rng', 'engine', '--seed', '7', '--results', os.path.join(root, 'b1')])['synth']
+    r4 = cli.main(['-opt', os.path.join(root, 'opt.yml'), '--rng', 'engine', '--seed', '7', '--batch', '4', '--graph',
+                   '--results', os.path.join(root, 'b4')])['synth']
+    assert len(r1['per_image']) == 8
+    for a, b in zip(r1['per_image'], r4['per_image']):
+        assert {k: v for k, v in a.items() if k != 'lpips'} == {k: v for k, v in b.items() if k != 'lpips'}, (a, b)   # lpips: nan (not asked for)
+    # the numbers are the reference formulas on the saved PNGs
+    for row in r1['per_image']:
+        sr = np.asarray(Image.open(os.path.join(root, 'b1', 'synth', row['name'])))
+        hr = np.asarray(Image.open(os.path.join(root, 'hr', row['name'])))
+        assert row['psnr'] == pytest.approx(M.calculate_psnr(sr, hr), rel=1e-12)
+        assert row['ergas'] == pytest.approx(M.calculate_ergas(sr, hr, scale=4), rel=1e-9)
+        assert row['ssim'] == pytest.approx(M.calculate_ssim(sr, hr), abs=1e-9)
+    assert r1['psnr'] == pytest.approx(np.mean([r['psnr'] for r in r1['per_image']]))
+    # the saved PNG of image 5 is tensor2img of the facade's own reverse_sde for the same seed and stream position
+    m, _ = _model(TEST_SETTING)
+    s = IRSDE(max_sigma=50, T=10, schedule='cosine', eps=0.5, device=DEV, rng='engine', seed=7)
+    s.set_model(m)
+    lq = torch.from_numpy(np.array(Image.open(os.path.join(root, 'lr', '05.png')))).to(DEV)[None]
+    mu = upscale(M.u8_to_tensor(lq, min_max=(0, 1)), 4)
+    s.set_mu(mu)
+    s.first_image = 5
+    x = s.reverse_sde(mu + m.randn(1, 256, 256, 10, 7, first_image=5, device=DEV) * s.max_sigma)
+    png = np.asarray(Image.open(os.path.join(root, 'b1', 'synth', '05.png')))
+    assert np.array_equal(M.tensor2img_batch(x, min_max=(0, 1))[0].cpu().numpy(), png)
