@@ -250,12 +250,15 @@ def test_memory_is_bounded_at_256():
     assert rise < one
 
 
+@pytest.mark.parametrize('n_timestep', [12, 60])
 @pytest.mark.parametrize('variant', ['ddpm', 'tesr', 'gdp'])
-def test_validation_after_a_training_step(variant):
-    """train.py's flow at T > 50: an optimisation step (dropout live: it leaves the engine in train mode), netG.eval(), then two
-    val samples with graph = 'auto' -- the second replays the chunked graph.  Both run, the engine's dropout is off (as after the
-    reference's netG.eval()), and they equal each other and an eager call bitwise."""
-    sched = dict(LONG[variant], n_timestep=60)
+def test_validation_after_a_training_step(variant, n_timestep):
+    """train.py's flow on both sampling paths (T = 12: fdsr_sample, T = 60: stepwise): an optimisation step (dropout live: it leaves
+    the engine in train mode), netG.eval(), then two val samples with graph = 'auto' -- at T > 50 the second replays the chunked
+    graph.  Both run, and they equal each other and an eager call bitwise.  The engine's dropout is off (as after the reference's
+    netG.eval()): the same dropout seed would give all three calls the same masks, so a fourth call after switching the engine's
+    train mode off by hand is what shows it -- it equals the first."""
+    sched = dict(LONG[variant], n_timestep=n_timestep)
     netG, cfg, sd, cond, noise = _new_facade(variant, sched)
     assert cfg.dropout > 0
     dev = torch.device('cuda')
@@ -273,3 +276,6 @@ def test_validation_after_a_training_step(variant):
     c = netG.p_sample_loop(x, continous=True, noise=nz)
     assert torch.isfinite(a).all()
     assert torch.equal(a, b) and torch.equal(a, c)
+    netG.denoise_fn.engine.set_training(False)
+    d = netG.p_sample_loop(x, continous=True, noise=nz)
+    assert torch.equal(a, d)
