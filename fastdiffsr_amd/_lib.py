@@ -31,6 +31,7 @@ class FdsrSampleOpts(C.Structure):
 
 FDSR_NAFNET_MAX_LEVELS = 8
 FDSR_NAFNET_ODE = 2
+FDSR_NAFNET_LOSS_WEIGHTED = 256
 
 
 class FdsrNafnetConfig(C.Structure):
@@ -126,6 +127,16 @@ SYMBOLS = {
                                            C.c_size_t, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_void_p]),
     'fdsr_nafnet_randn': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_void_p]),
     'fdsr_upscale_bicubic_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'fdsr_nafnet_set_thetas_cumsum': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
+    'fdsr_nafnet_train_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    'fdsr_nafnet_train_grads': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int,
+                                          C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'fdsr_nafnet_grad_buffer': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    'fdsr_nafnet_read_grad': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p]),
+    'fdsr_nafnet_optim_step': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    'fdsr_nafnet_read_weight': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]),
+    'fdsr_nafnet_optim_get_state': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    'fdsr_nafnet_optim_set_state': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64]),
     'fdsr_nafnet_destroy': (None, [C.c_void_p]),
     'fdsr_set_debug': (C.c_int, [C.c_void_p, C.c_int]),
     'fdsr_debug_option': (C.c_int, [C.c_char_p, C.c_longlong]),

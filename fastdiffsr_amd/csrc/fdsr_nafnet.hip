@@ -47,6 +47,7 @@ struct GemmArgs {
   const float* w;      // [Kpad][CoutPad], k = (ky * KW + kx) * Cin + ci
   const float* bias;   // [CoutPad] (zeros for a bias-free conv)
   float* out;
+  float* out2;         // EPI_GATE, training: the pair before the gate, [M][Cout] in channel order (or null)
   const float* stats;  // PRO_LN: [M][2] (mean, rstd) per pixel
   const float* pmul;   // PRO_MUL / PRO_LN: per-image vector over k, a = a * pmul[k]      (image n at pmul + n * pstride)
   const float* padd;   // PRO_LN: a = (a - mean) rstd pmul[k] + padd[k]
@@ -178,7 +179,13 @@ __global__ void __launch_bounds__(NT) naf_gemm_kernel(GemmArgs p) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const int om = mw + (i & 3) + 8 * (i >> 2);
-      if (om < M) p.out[(size_t)om * p.ostride + cg] = (acc[0][i] + b0) * (acc[1][i] + b1);
+      if (om >= M) continue;
+      const float u0 = acc[0][i] + b0, u1 = acc[1][i] + b1;
+      p.out[(size_t)om * p.ostride + cg] = u0 * u1;
+      if (p.out2) {
+        p.out2[(size_t)om * p.Cout + cg] = u0;
+        p.out2[(size_t)om * p.Cout + half + cg] = u1;
+      }
     }
     return;
   }
@@ -585,7 +592,9 @@ struct fdsr_nafnet_obj {
   int L = 0, wd = 0, R = 0;
   std::vector<WT> wts;
   std::map<std::string, int> key2w;
-  std::vector<GemmL> gemms;
+  std::vector<GemmL> gemms, tgemms;   // tgemms[i]: the input gradient of gemms[i] as a convolution of its own
+  std::vector<size_t> poff;           // tensor i's first element in the flat master / gradient / optimizer-state buffers
+  size_t P = 0, off_zero = 0;
   std::vector<BlockL> blocks;
   std::vector<std::vector<int>> enc, dec;
   std::vector<int> mid, ups, downs;   // ups / downs: GemmL indices
@@ -596,6 +605,13 @@ struct fdsr_nafnet_obj {
   size_t arena_floats = 0;
   float* d_arena = nullptr;
   bool dirty = true;
+  // training (fdsr_nafnet_train.h): flat fp32 buffers in the reference's layout, tensors in state_dict order
+  float *d_master = nullptr, *d_grad = nullptr, *d_m = nullptr, *d_v = nullptr, *d_cum = nullptr;
+  int *d_map = nullptr, *d_rowmap = nullptr;
+  bool master_valid = false;   // d_master holds the weights the arena was packed from
+  bool host_stale = false;     // an optimizer step moved the weights on: the host copies are behind d_master
+  long long opt_step = 0;
+  int cum_T = 0;
   // IR-SDE
   int T = 0;
   std::vector<float> thetas, sigmas, sbars;
@@ -725,7 +741,106 @@ void build_schema(fdsr_nafnet n) {
   n->off_rowsb = take(off, n->R);
   n->off_rowsadd = take(off, n->R);
   n->off_rowsmul = take(off, n->R);
+  // training: the transposed convolutions (cin == 0: no input gradient is needed -- intro reads data) and a zero bias for them
+  int zmax = 64;
+  for (const GemmL& g : n->gemms) {
+    GemmL t;
+    if (g.ks == 3) { t.cin = g.cout; t.cout = g.cin; t.ks = 3; t.s = 1; t.p = 1; }
+    else if (g.ks == 2) { t.cin = g.cout; t.cout = 4 * g.cin; }
+    else if (g.b < 0) { t.cin = g.cout / 4; t.cout = g.cin; t.ks = 2; t.s = 2; }
+    else { t.cin = g.cout; t.cout = g.cin; }
+    if (&g == &n->gemms[n->g_intro]) t.cin = 0;
+    if (t.cin) {
+      t.woff = take(off, (size_t)t.Kpad() * t.CoutPad());
+      zmax = std::max(zmax, t.CoutPad());
+    }
+    n->tgemms.push_back(t);
+  }
+  n->off_zero = take(off, zmax);
+  for (GemmL& t : n->tgemms) t.boff = n->off_zero;
   n->arena_floats = off;
+  size_t po = 0;
+  for (const WT& wt : n->wts) { n->poff.push_back(po); po += numel(wt.shape); }
+  n->P = po;
+}
+
+// Every device form of the weights, written through a sink: FloatSink copies values from the host tensors (the upload), IndexSink
+// records for every arena element the flat index of the master value it holds (-1: a constant), which is what the training
+// step's device-side re-pack gathers through.
+struct FloatSink {
+  fdsr_nafnet n;
+  std::vector<float>& a;
+  void set(size_t ai, int wi, size_t ei) { a[ai] = n->wts[wi].host[ei]; }
+  void cst(size_t ai, float v) { a[ai] = v; }
+};
+struct IndexSink {
+  fdsr_nafnet n;
+  std::vector<int>& a;
+  void set(size_t ai, int wi, size_t ei) { a[ai] = (int)(n->poff[wi] + ei); }
+  void cst(size_t, float) {}
+};
+
+template <class S>
+void pack_forms(fdsr_nafnet n, S& s) {
+  auto len = [&](int wi) { return numel(n->wts[wi].shape); };
+  for (const GemmL& g : n->gemms) {
+    const int Cp = g.CoutPad(), half = g.cout / 2;
+    auto col = [&](int co) { return g.gate ? (co < half ? 64 * (co / 32) + co % 32 : 64 * ((co - half) / 32) + 32 + (co - half) % 32) : co; };
+    for (int co = 0; co < g.cout; ++co) {
+      const int pc = col(co);
+      if (g.b >= 0) s.set(g.boff + pc, g.b, co);
+      for (int ci = 0; ci < g.cin; ++ci)
+        for (int ky = 0; ky < g.ks; ++ky)
+          for (int kx = 0; kx < g.ks; ++kx)
+            s.set(g.woff + ((size_t)(ky * g.ks + kx) * g.cin + ci) * Cp + pc, g.w, (((size_t)co * g.cin + ci) * g.ks + ky) * g.ks + kx);
+    }
+  }
+  const int K2 = 2 * n->wd, R = n->R;
+  for (const BlockL& b : n->blocks) {
+    const int c = b.c;
+    for (int i = 0; i < c; ++i) { s.set(b.off_beta + i, b.beta, i); s.set(b.off_gamma + i, b.gamma, i); s.set(b.off_scab + i, b.scab, i); }
+    for (int ch = 0; ch < 2 * c; ++ch) {
+      for (int k = 0; k < 9; ++k) s.set(b.off_dww + (size_t)k * 2 * c + ch, b.dww, (size_t)ch * 9 + k);
+      s.set(b.off_dwb + ch, b.dwb, ch);
+    }
+    for (size_t i = 0; i < (size_t)c * c; ++i) s.set(b.off_scaw + i, b.scaw, i);
+    // rows: [shift_att | scale_att | shift_ffn | scale_ffn], c each
+    for (int r = 0; r < 4 * c; ++r) {
+      const int gr = b.row_off + r, chunk = r / c, ch = r % c;
+      for (int j = 0; j < K2; ++j) s.set(n->off_rowsw + (size_t)j * R + gr, b.mlpw, (size_t)r * K2 + j);
+      s.set(n->off_rowsb + gr, b.mlpb, r);
+      s.cst(n->off_rowsadd + gr, (chunk & 1) ? 1.f : 0.f);
+      if (chunk == 1) s.set(n->off_rowsmul + gr, b.g1, ch);
+      else if (chunk == 3) s.set(n->off_rowsmul + gr, b.g2, ch);
+      else s.cst(n->off_rowsmul + gr, 1.f);
+    }
+  }
+  // SinusoidalPosEmb: exp(arange(half) * -(log(10000) / (half - 1))) in fp32
+  const int half = n->wd / 2;
+  const float step = (float)(-(std::log(10000.0) / (half - 1)));
+  for (int j = 0; j < half; ++j) s.cst(n->off_freq + j, expf((float)j * step));
+  auto cp = [&](int wi, size_t off) { for (size_t i = 0; i < len(wi); ++i) s.set(off + i, wi, i); };
+  cp(n->t1w, n->off_t1w); cp(n->t1b, n->off_t1b); cp(n->t2w, n->off_t2w); cp(n->t2b, n->off_t2b);
+  cp(n->ca1w, n->off_ca1w); cp(n->ca1b, n->off_ca1b); cp(n->ca2w, n->off_ca2w); cp(n->ca2b, n->off_ca2b);
+  // the input-gradient packs (training): the same GEMM kernel reads them as the weights of the transposed convolution
+  for (size_t gi = 0; gi < n->gemms.size(); ++gi) {
+    const GemmL& g = n->gemms[gi];
+    const GemmL& t = n->tgemms[gi];
+    if (t.cin == 0) continue;
+    const int Cp = t.CoutPad();
+    for (int co = 0; co < g.cout; ++co)
+      for (int ci = 0; ci < g.cin; ++ci)
+        for (int ky = 0; ky < g.ks; ++ky)
+          for (int kx = 0; kx < g.ks; ++kx) {
+            const size_t src = (((size_t)co * g.cin + ci) * g.ks + ky) * g.ks + kx;
+            size_t k, col;
+            if (g.ks == 3) { k = (size_t)((2 - ky) * 3 + (2 - kx)) * g.cout + co; col = ci; }           // flipped taps
+            else if (g.ks == 2) { k = co; col = (size_t)ci * 4 + ky * 2 + kx; }                         // downs: 1x1 + PixelShuffle scatter
+            else if (g.b < 0) { k = (size_t)(co & 3) * (g.cout / 4) + (co >> 2); col = ci; }            // ups: 2x2 stride 2 over the shuffled gradient
+            else { k = co; col = ci; }
+            s.set(t.woff + k * Cp + col, g.w, src);
+          }
+  }
 }
 
 // every device form from the host copies, one upload
@@ -734,51 +849,24 @@ int finalize(fdsr_nafnet n) {
   for (const WT& w : n->wts)
     if (!w.loaded) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet: tensor '%s' is missing", w.key.c_str());
   std::vector<float> a(n->arena_floats, 0.f);
-  auto H = [&](int i) -> const std::vector<float>& { return n->wts[i].host; };
-  for (const GemmL& g : n->gemms) {
-    const std::vector<float>& w = H(g.w);
-    const int Cp = g.CoutPad(), half = g.cout / 2;
-    auto col = [&](int co) { return g.gate ? (co < half ? 64 * (co / 32) + co % 32 : 64 * ((co - half) / 32) + 32 + (co - half) % 32) : co; };
-    for (int co = 0; co < g.cout; ++co) {
-      const int pc = col(co);
-      if (g.b >= 0) a[g.boff + pc] = H(g.b)[co];
-      for (int ci = 0; ci < g.cin; ++ci)
-        for (int ky = 0; ky < g.ks; ++ky)
-          for (int kx = 0; kx < g.ks; ++kx)
-            a[g.woff + ((size_t)(ky * g.ks + kx) * g.cin + ci) * Cp + pc] = w[(((size_t)co * g.cin + ci) * g.ks + ky) * g.ks + kx];
-    }
-  }
-  const int K2 = 2 * n->wd, R = n->R;
-  for (const BlockL& b : n->blocks) {
-    const int c = b.c;
-    std::copy(H(b.beta).begin(), H(b.beta).end(), a.begin() + b.off_beta);
-    std::copy(H(b.gamma).begin(), H(b.gamma).end(), a.begin() + b.off_gamma);
-    for (int ch = 0; ch < 2 * c; ++ch)
-      for (int k = 0; k < 9; ++k) a[b.off_dww + (size_t)k * 2 * c + ch] = H(b.dww)[(size_t)ch * 9 + k];
-    std::copy(H(b.dwb).begin(), H(b.dwb).end(), a.begin() + b.off_dwb);
-    std::copy(H(b.scaw).begin(), H(b.scaw).end(), a.begin() + b.off_scaw);
-    std::copy(H(b.scab).begin(), H(b.scab).end(), a.begin() + b.off_scab);
-    // rows: [shift_att | scale_att | shift_ffn | scale_ffn], c each
-    for (int r = 0; r < 4 * c; ++r) {
-      const int gr = b.row_off + r, chunk = r / c, ch = r % c;
-      for (int j = 0; j < K2; ++j) a[n->off_rowsw + (size_t)j * R + gr] = H(b.mlpw)[(size_t)r * K2 + j];
-      a[n->off_rowsb + gr] = H(b.mlpb)[r];
-      a[n->off_rowsadd + gr] = (chunk & 1) ? 1.f : 0.f;
-      a[n->off_rowsmul + gr] = chunk == 1 ? H(b.g1)[ch] : chunk == 3 ? H(b.g2)[ch] : 1.f;
-    }
-  }
-  // SinusoidalPosEmb: exp(arange(half) * -(log(10000) / (half - 1))) in fp32
-  const int half = n->wd / 2;
-  const float step = (float)(-(std::log(10000.0) / (half - 1)));
-  for (int j = 0; j < half; ++j) a[n->off_freq + j] = expf((float)j * step);
-  auto cp = [&](int wi, size_t off) { std::copy(H(wi).begin(), H(wi).end(), a.begin() + off); };
-  cp(n->t1w, n->off_t1w); cp(n->t1b, n->off_t1b); cp(n->t2w, n->off_t2w); cp(n->t2b, n->off_t2b);
-  cp(n->ca1w, n->off_ca1w); cp(n->ca1b, n->off_ca1b); cp(n->ca2w, n->off_ca2w); cp(n->ca2b, n->off_ca2b);
+  FloatSink sink{n, a};
+  pack_forms(n, sink);
   if (!n->d_arena) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_arena), a.size() * sizeof(float)));
   HIPCHK(nullptr, hipDeviceSynchronize());   // nothing in flight reads the old forms
   HIPCHK(nullptr, hipMemcpy(n->d_arena, a.data(), a.size() * sizeof(float), hipMemcpyHostToDevice));
   n->dirty = false;
   n->table_valid = false;
+  n->master_valid = false;
+  return FDSR_OK;
+}
+
+// the host copies follow the device master again (a weight is about to be loaded over trained ones)
+int host_from_master(fdsr_nafnet n) {
+  if (!n->host_stale) return FDSR_OK;
+  HIPCHK(nullptr, hipDeviceSynchronize());
+  for (size_t i = 0; i < n->wts.size(); ++i)
+    HIPCHK(nullptr, hipMemcpy(n->wts[i].host.data(), n->d_master + n->poff[i], n->wts[i].host.size() * sizeof(float), hipMemcpyDeviceToHost));
+  n->host_stale = false;
   return FDSR_OK;
 }
 
@@ -828,6 +916,7 @@ struct Run {
   const float* tap_ptr = nullptr;
   int tap_h = 0, tap_w = 0, tap_c = 0;
   int err = FDSR_OK;
+  float* stats = nullptr;   // training: this LayerNorm's own slot instead of pl.stats
 
   float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
   const float* P(size_t off) const { return n->d_arena + off; }
@@ -843,10 +932,14 @@ struct Run {
 
   void gemm(int gi, const float* x, float* out, int Hin, int Win, int epi, int pro = PRO_NONE, const float* pmul = nullptr,
             const float* padd = nullptr, int pstride = 0, const float* res = nullptr, const float* evec = nullptr) {
-    const GemmL& g = n->gemms[gi];
+    gemm_l(n->gemms[gi], x, out, Hin, Win, epi, pro, pmul, padd, pstride, res, evec);
+  }
+
+  void gemm_l(const GemmL& g, const float* x, float* out, int Hin, int Win, int epi, int pro = PRO_NONE, const float* pmul = nullptr,
+              const float* padd = nullptr, int pstride = 0, const float* res = nullptr, const float* evec = nullptr, float* out2 = nullptr) {
     GemmArgs a{};
-    a.x = x; a.w = P(g.woff); a.bias = P(g.boff); a.out = out;
-    a.stats = F(pl.stats); a.pmul = pmul; a.padd = padd; a.res = res; a.evec = evec;
+    a.x = x; a.w = P(g.woff); a.bias = P(g.boff); a.out = out; a.out2 = out2;
+    a.stats = stats ? stats : F(pl.stats); a.pmul = pmul; a.padd = padd; a.res = res; a.evec = evec;
     a.N = pl.N; a.Hin = Hin; a.Win = Win; a.Cin = g.cin;
     a.Hout = (Hin + 2 * g.p - g.ks) / g.s + 1;
     a.Wout = (Win + 2 * g.p - g.ks) / g.s + 1;
@@ -863,7 +956,7 @@ struct Run {
   }
 
   void ln_stats(const float* x, int M, int C) {
-    hipLaunchKernelGGL(naf_ln_stats_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, st, x, F(pl.stats), M, C);
+    hipLaunchKernelGGL(naf_ln_stats_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, st, x, stats ? stats : F(pl.stats), M, C);
     check();
   }
 
@@ -1023,6 +1116,8 @@ int ensure_table(fdsr_nafnet n, hipStream_t st) {
 
 }  // namespace
 
+#include "fdsr_nafnet_train.h"
+
 extern "C" {
 
 int fdsr_nafnet_create(const fdsr_nafnet_config* cfg, fdsr_nafnet* out) {
@@ -1045,7 +1140,8 @@ int fdsr_nafnet_create(const fdsr_nafnet_config* cfg, fdsr_nafnet* out) {
 void fdsr_nafnet_destroy(fdsr_nafnet n) {
   if (!n) return;
   drop_graph(n);
-  for (void* p : {(void*)n->d_arena, (void*)n->d_sde, (void*)n->d_rowtable, (void*)n->d_cur_row, (void*)n->d_ctl})
+  for (void* p : {(void*)n->d_arena, (void*)n->d_sde, (void*)n->d_rowtable, (void*)n->d_cur_row, (void*)n->d_ctl, (void*)n->d_master,
+                  (void*)n->d_grad, (void*)n->d_m, (void*)n->d_v, (void*)n->d_cum, (void*)n->d_map, (void*)n->d_rowmap})
     if (p) (void)hipFree(p);
   delete n;
 }
@@ -1067,6 +1163,8 @@ int fdsr_nafnet_load_weight(fdsr_nafnet n, const char* key, const float* host_f3
   if (!n || !key || !host_f32 || (ndim > 0 && !shape) || ndim < 0) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_load_weight: bad arguments");
   const auto it = n->key2w.find(key);
   if (it == n->key2w.end()) return fail(nullptr, FDSR_E_KEY, "fdsr_nafnet_load_weight: unknown tensor '%s'", key);
+  const int rc = host_from_master(n);   // after an optimizer step the other tensors' host copies are refreshed first
+  if (rc) return rc;
   WT& w = n->wts[it->second];
   if (ndim != (int)w.shape.size() || !std::equal(w.shape.begin(), w.shape.end(), shape))
     return fail(nullptr, FDSR_E_KEY, "fdsr_nafnet_load_weight: '%s' has the wrong shape", key);
@@ -1097,6 +1195,7 @@ int fdsr_nafnet_set_sde(fdsr_nafnet n, int T, const float* thetas, const float* 
   n->thetas.assign(thetas, thetas + T + 1);
   n->sigmas.assign(sigmas, sigmas + T + 1);
   n->sbars.assign(sigma_bars, sigma_bars + T + 1);
+  n->cum_T = 0;   // thetas_cumsum belongs to the schedule it was given with
   std::vector<float> all(n->thetas);
   all.insert(all.end(), n->sigmas.begin(), n->sigmas.end());
   all.insert(all.end(), n->sbars.begin(), n->sbars.end());

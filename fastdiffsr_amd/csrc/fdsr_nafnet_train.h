@@ -1,0 +1,1105 @@
+// EDiffSR training on gfx950: one step of DenoisingModel.optimize_parameters (EDiffSR/codes/config/sisr/models/denoising_model.py) for
+// ConditionalNAFNet + IR-SDE, fp32.  Part of fdsr_nafnet.hip's translation unit (it shares the forward kernels, the schema and Run).
+//
+//   saving forward   the forward's own kernels with the forward's arguments, every tensor the backward reads in a slot of its own
+//   loss head        xt_1_expection, xt_1_optimum, MatchingLoss (l1 / l2), d eps
+//   backward         input gradients: naf_gemm_kernel over the transposed packs (pack_forms); weight / bias gradients:
+//                    naf_wgrad_kernel (v_mfma_f32_32x32x2_f32, split over pixel chunks, second pass in chunk order); the rest elementwise
+//   optimizer        Adam / AdamW / Lion over the flat master, then a gather re-pack of every device form
+//
+// No atomics anywhere: every sum has one order, fixed by the shapes alone.  Kept per block: out, LN statistics, conv1's output, the
+// gated product, the SCA vector, y, conv4's pair before the gate and its product.  Recomputed in the backward: the LN-modulated
+// inputs of conv1 / conv4 and the SCA-scaled input of conv3 (prologues of the weight-gradient kernel), conv2's outputs (in the gate's
+// backward), conv3's and conv5's outputs (for d beta / d gamma), SCA's and the RCAB's pooled means.
+
+namespace {
+
+constexpr int WG_CHUNK = 2048;   // pixels per partial sum of a weight gradient
+constexpr int WG_PB = 16;        // pixels per LDS stage
+constexpr int WG_P = 64 + 32;    // LDS pitch, as AP / BP
+
+struct WgArgs {
+  const float* x;        // the convolution's input, NHWC [N][Hin][Win][Cin]
+  const float* dy;       // [M][ldy] gradient of its output
+  const float* stats;    // PRO_LN
+  const float* pmul;     // PRO_MUL / PRO_LN, image n at pmul + n * pstride
+  const float* padd;
+  const float* colmul;   // dy[.][co] *= colmul[co] (beta / gamma), or null
+  float* part;           // [nz][KP][CP]
+  int N, Hin, Win, Cin, Hout, Wout, Cout, KW, S, P, K, Keff, ldy, pstride;
+};
+
+// dW[k][co] = sum over pixels of A[p][k] dY[p][co]; A is the forward GEMM's operand (im2col, with the forward's prologue), and
+// row k == K (when Keff > K) is a column of ones: the bias gradient.  Workgroup: 64 k x 64 co of one pixel chunk; wave w owns the
+// 32 x 32 tile (w & 1, w >> 1).  MFMA 32x32x2: A[i = k][kk = pixel], B[kk = pixel][j = co]; 16 pixels per stage.
+template <int PRO>
+__global__ void __launch_bounds__(256) naf_wgrad_kernel(WgArgs p) {
+  __shared__ float sA[WG_PB * WG_P];
+  __shared__ float sB[WG_PB * WG_P];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int kl = t & 63, pl0 = t >> 6;
+  const int HWo = p.Hout * p.Wout, M = p.N * HWo;
+  const int k = blockIdx.x * 64 + kl, co = blockIdx.y * 64 + kl;
+  const bool kval = k < p.K, kone = k >= p.K && k < p.Keff, cval = co < p.Cout;
+  int ci = 0, ky = 0, kx = 0;
+  if (kval) {
+    const int tap = k / p.Cin;
+    ci = k - tap * p.Cin;
+    ky = tap / p.KW;
+    kx = tap - ky * p.KW;
+  }
+  const float cm = (cval && p.colmul) ? p.colmul[co] : 1.f;
+  const int pbeg = blockIdx.z * WG_CHUNK, pend = min(M, pbeg + WG_CHUNK);
+  f32x16 acc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  const int r31 = lane & 31, h = lane >> 5, kh = wave & 1, ch = wave >> 1;
+  for (int p0 = pbeg; p0 < pend; p0 += WG_PB) {
+    float ra[4], rb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int pix = p0 + pl0 + 4 * j;
+      float a = 0.f, b = 0.f;
+      if (pix < pend) {
+        if (cval) b = p.dy[(size_t)pix * p.ldy + co] * cm;
+        if (kone) a = 1.f;
+        else if (kval) {
+          const int n = pix / HWo, r = pix - n * HWo;
+          const int oy = r / p.Wout, ox = r - oy * p.Wout;
+          const int iy = oy * p.S - p.P + ky, ix = ox * p.S - p.P + kx;
+          if (iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win) {
+            a = p.x[(((size_t)n * p.Hin + iy) * p.Win + ix) * p.Cin + ci];
+            if (PRO == PRO_MUL) a *= p.pmul[(size_t)n * p.pstride + ci];
+            if (PRO == PRO_LN)
+              a = (a - p.stats[2 * (size_t)pix]) * p.stats[2 * (size_t)pix + 1] * p.pmul[(size_t)n * p.pstride + ci] + p.padd[(size_t)n * p.pstride + ci];
+          }
+        }
+      }
+      ra[j] = a;
+      rb[j] = b;
+    }
+    __syncthreads();   // the previous stage's LDS reads are done
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      sA[(pl0 + 4 * j) * WG_P + kl] = ra[j];
+      sB[(pl0 + 4 * j) * WG_P + kl] = rb[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < WG_PB / 2; ++s) {
+      const int pr = 2 * s + h;
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sA[pr * WG_P + 32 * kh + r31], sB[pr * WG_P + 32 * ch + r31], acc, 0, 0, 0);
+    }
+  }
+  // C/D map: column (co) = lane & 31, row (k) = (i & 3) + 8 (i >> 2) + 4 (lane >> 5)
+  const int KP = gridDim.x * 64, CP = gridDim.y * 64;
+  float* dst = p.part + ((size_t)blockIdx.z * KP + blockIdx.x * 64 + 32 * kh + 4 * h) * CP + blockIdx.y * 64 + 32 * ch + r31;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) dst[(size_t)((i & 3) + 8 * (i >> 2)) * CP] = acc[i];
+}
+
+// the chunks in order, into the reference's layout.  mode 0: weight[co][ci][ky][kx] (k = tap Cin + ci), bias[co] (k == K);
+// mode 1 (ups, operands exchanged): k = tap C' + c' is the output channel 4 c' + tap, the column is the input channel.
+__global__ void __launch_bounds__(256) naf_wgrad_finish_kernel(const float* __restrict__ part, int nz, int KP, int CP, int Keff, int K, int Cout,
+                                                               int Cin, int taps, int mode, float* __restrict__ gw, float* __restrict__ gb) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= Keff * Cout) return;
+  const int k = i / Cout, co = i - k * Cout;
+  float s = 0.f;
+  for (int z = 0; z < nz; ++z) s += part[((size_t)z * KP + k) * CP + co];
+  if (k >= K) { gb[co] = s; return; }
+  const int tap = k / Cin, ci = k - tap * Cin;
+  if (mode == 0) gw[((size_t)co * Cin + ci) * taps + tap] = s;
+  else gw[(size_t)(4 * ci + tap) * Cout + co] = s;
+}
+
+// per-strip channel sums of a (mode 0), a b (mode 1) or a (b - mean) rstd (mode 2): part[n][strip][ch], as naf_chansum_kernel
+__global__ void __launch_bounds__(256) naf_dot_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ stats,
+                                                      float* __restrict__ part, int HW, int c, int nstrips, int mode) {
+  __shared__ float red[4][64];
+  const int cl = threadIdx.x & 63, py = threadIdx.x >> 6;
+  const int ch = blockIdx.y * 64 + cl, n = blockIdx.z, strip = blockIdx.x;
+  float sum = 0.f;
+  if (ch < c)
+    for (int q = py; q < STRIP; q += 4) {
+      const int pix = strip * STRIP + q;
+      if (pix >= HW) break;
+      const size_t gp = (size_t)n * HW + pix, i = gp * c + ch;
+      float v = a[i];
+      if (mode == 1) v *= b[i];
+      if (mode == 2) v *= (b[i] - stats[2 * gp]) * stats[2 * gp + 1];
+      sum += v;
+    }
+  red[py][cl] = sum;
+  __syncthreads();
+  if (py == 0 && ch < c) part[((size_t)n * nstrips + strip) * c + ch] = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
+}
+
+// dst[g][ch] = scale * (part[g G][ch] + part[g G + 1][ch] + ...), in order
+__global__ void __launch_bounds__(256) naf_reduce_kernel(const float* __restrict__ part, float* __restrict__ dst, int groups, int G, int c, float scale,
+                                                         int dstride) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= groups * c) return;
+  const int g = i / c, ch = i - g * c;
+  float s = 0.f;
+  for (int k = 0; k < G; ++k) s += part[((size_t)g * G + k) * c + ch];
+  dst[(size_t)g * dstride + ch] = s * scale;
+}
+
+// LayerNorm + FiLM backward onto the running gradient: out = xh mul + add, xh = (x - mean) rstd;
+// g += rstd (d mul - mean_c(d mul) - xh mean_c(d mul xh)).  16 lanes per pixel, as naf_ln_stats_kernel.
+__global__ void __launch_bounds__(256) naf_ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ d, const float* __restrict__ stats,
+                                                         const float* __restrict__ mul, int mstride, float* __restrict__ g, int M, int HW, int C) {
+  const int sub = threadIdx.x & 15;
+  const int pix = blockIdx.x * 16 + (threadIdx.x >> 4);
+  const bool ok = pix < M;
+  const size_t base = (size_t)(ok ? pix : 0) * C;
+  const float* m = mul + (size_t)((ok ? pix : 0) / HW) * mstride;
+  const float mean = stats[2 * (size_t)(ok ? pix : 0)], rstd = stats[2 * (size_t)(ok ? pix : 0) + 1];
+  float s1 = 0.f, s2 = 0.f;
+  for (int c = sub; c < C; c += 16) {
+    const float dh = d[base + c] * m[c], xh = (x[base + c] - mean) * rstd;
+    s1 += dh;
+    s2 += dh * xh;
+  }
+#pragma unroll
+  for (int o = 8; o; o >>= 1) { s1 += __shfl_xor(s1, o, 16); s2 += __shfl_xor(s2, o, 16); }
+  s1 /= (float)C;
+  s2 /= (float)C;
+  if (!ok) return;
+  for (int c = sub; c < C; c += 16) {
+    const float dh = d[base + c] * m[c], xh = (x[base + c] - mean) * rstd;
+    g[base + c] += rstd * (dh - s1 - xh * s2);
+  }
+}
+
+// SimpleGate backward from the saved pair: out[p][j] = d[p][j] u[p][c + j], out[p][c + j] = d[p][j] u[p][j]
+__global__ void __launch_bounds__(256) naf_gate_bwd_kernel(const float* __restrict__ d, const float* __restrict__ u, float* __restrict__ out, int c,
+                                                           size_t total) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const size_t pix = i / c;
+  const int j = (int)(i - pix * c);
+  const float v = d[i];
+  out[pix * 2 * c + j] = v * u[pix * 2 * c + c + j];
+  out[pix * 2 * c + c + j] = v * u[pix * 2 * c + j];
+}
+
+// x sca backward, then conv2's SimpleGate: d t2 = d[p][ch] sca[n][ch] + dpool[n][ch]; conv2's two outputs are formed again from x.
+__global__ void __launch_bounds__(256) naf_dwgate_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
+                                                             const float* __restrict__ d, const float* __restrict__ sca, const float* __restrict__ dpool,
+                                                             float* __restrict__ out, int H, int W, int c, size_t total) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const size_t gp = i / c;
+  const int ch = (int)(i - gp * c), HW = H * W, C2 = 2 * c;
+  const int n = (int)(gp / HW), pix = (int)(gp - (size_t)n * HW);
+  const int yy = pix / W, xx = pix - yy * W;
+  const float* xn = x + (size_t)n * HW * C2;
+  float a0 = 0.f, a1 = 0.f;
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const int iy = yy + dy - 1, ix = xx + dx - 1;
+      if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
+      const float* src = xn + ((size_t)iy * W + ix) * C2;
+      a0 += w[(dy * 3 + dx) * C2 + ch] * src[ch];
+      a1 += w[(dy * 3 + dx) * C2 + c + ch] * src[c + ch];
+    }
+  a0 += b[ch];
+  a1 += b[c + ch];
+  const float dt2 = d[i] * sca[(size_t)n * c + ch] + dpool[(size_t)n * c + ch];
+  out[gp * C2 + ch] = dt2 * a1;
+  out[gp * C2 + c + ch] = dt2 * a0;
+}
+
+// depthwise 3x3 backward: dx[q][ch] = sum_k w[k][ch] da[q - off_k][ch]; and the strip's sums of da[p] x[p + off_k] (k < 9) and of da
+// (k = 9): part[n][strip][10][C2]
+__global__ void __launch_bounds__(256) naf_dw_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ da,
+                                                         float* __restrict__ dx, float* __restrict__ part, int H, int W, int C2, int nstrips) {
+  __shared__ float red[4][10][64];
+  const int cl = threadIdx.x & 63, py = threadIdx.x >> 6;
+  const int ch = blockIdx.y * 64 + cl, n = blockIdx.z, strip = blockIdx.x;
+  const int HW = H * W;
+  float acc[10];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) acc[k] = 0.f;
+  if (ch < C2) {
+    float wk[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) wk[k] = w[k * C2 + ch];
+    const float* xn = x + (size_t)n * HW * C2;
+    const float* dn = da + (size_t)n * HW * C2;
+    for (int q = py; q < STRIP; q += 4) {
+      const int pix = strip * STRIP + q;
+      if (pix >= HW) break;
+      const int yy = pix / W, xx = pix - yy * W;
+      const float dv = dn[(size_t)pix * C2 + ch];
+      float s = 0.f;
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dxx = 0; dxx < 3; ++dxx) {
+          const int k = dy * 3 + dxx;
+          const int fy = yy + dy - 1, fx = xx + dxx - 1;   // the forward tap of this pixel
+          if (fy >= 0 && fy < H && fx >= 0 && fx < W) acc[k] += dv * xn[((size_t)fy * W + fx) * C2 + ch];
+          const int by = yy - dy + 1, bx = xx - dxx + 1;   // the output pixel that read this one through tap k
+          if (by >= 0 && by < H && bx >= 0 && bx < W) s += wk[k] * dn[((size_t)by * W + bx) * C2 + ch];
+        }
+      acc[9] += dv;
+      dx[((size_t)n * HW + pix) * C2 + ch] = s;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 10; ++k) red[py][k][cl] = acc[k];
+  __syncthreads();
+  if (py == 0 && ch < C2)
+#pragma unroll
+    for (int k = 0; k < 10; ++k)
+      part[(((size_t)n * nstrips + strip) * 10 + k) * C2 + ch] = ((red[0][k][cl] + red[1][k][cl]) + red[2][k][cl]) + red[3][k][cl];
+}
+
+__global__ void __launch_bounds__(256) naf_dw_finish_kernel(const float* __restrict__ part, int G, int C2, float* __restrict__ gw, float* __restrict__ gb) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 10 * C2) return;
+  const int k = i / C2, ch = i - k * C2;
+  float s = 0.f;
+  for (int g = 0; g < G; ++g) s += part[((size_t)g * 10 + k) * C2 + ch];
+  if (k < 9) gw[(size_t)ch * 9 + k] = s;
+  else gb[ch] = s;
+}
+
+// SCA's mat-vec backward: dW[co][ci] = sum_n ds[n][co] pooled[n][ci], db[co] = sum_n ds[n][co]
+__global__ void __launch_bounds__(256) naf_sca_bwd_w_kernel(const float* __restrict__ ds, const float* __restrict__ pooled, float* __restrict__ gw,
+                                                            float* __restrict__ gb, int N, int c) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)c * c) return;
+  const int co = (int)(i / c), ci = (int)(i - (size_t)co * c);
+  float s = 0.f, sb = 0.f;
+  for (int n = 0; n < N; ++n) {
+    s += ds[(size_t)n * c + co] * pooled[(size_t)n * c + ci];
+    sb += ds[(size_t)n * c + co];
+  }
+  gw[i] = s;
+  if (ci == 0) gb[co] = sb;
+}
+
+// dpool[n][ci] = (sum_co W[co][ci] ds[n][co]) / HW: what every pixel of the pooled tensor receives
+__global__ void __launch_bounds__(256) naf_sca_bwd_x_kernel(const float* __restrict__ ds, const float* __restrict__ w, float* __restrict__ dpool, int N,
+                                                            int c, float inv_hw) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N * c) return;
+  const int n = i / c, ci = i - n * c;
+  float s = 0.f;
+  for (int co = 0; co < c; ++co) s += w[(size_t)co * c + ci] * ds[(size_t)n * c + co];
+  dpool[i] = s * inv_hw;
+}
+
+// RCAB's ChannelAttention backward, one block per image: pooled and hid are formed again; da [N][c] is sum_p d r.
+// Writes dz2 [N][c], dz1 [N][cs], hid [N][cs], pooled [N][c] for the weight gradients and dpool [N][c] (divided by HW).
+__global__ void __launch_bounds__(256) naf_ca_bwd_kernel(const float* __restrict__ part, int nstrips, int HW, const float* __restrict__ w1,
+                                                         const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ att,
+                                                         const float* __restrict__ da, float* __restrict__ dz2o, float* __restrict__ dz1o,
+                                                         float* __restrict__ hido, float* __restrict__ pooledo, float* __restrict__ dpool, int c, int cs) {
+  extern __shared__ float lds[];
+  float* pooled = lds;
+  float* tmp = lds + c;
+  float* hid = tmp + 256;
+  float* dz2 = hid + cs;
+  float* dz1 = dz2 + c;
+  const int n = blockIdx.x;
+  pooled_to_lds(part, n, nstrips, HW, c, pooled, tmp);
+  for (int j = threadIdx.x; j < cs; j += 256) {
+    float a = b1[j];
+    for (int ci = 0; ci < c; ++ci) a += w1[(size_t)j * c + ci] * pooled[ci];
+    hid[j] = fmaxf(a, 0.f);
+  }
+  for (int co = threadIdx.x; co < c; co += 256) {
+    const float a = att[(size_t)n * c + co];
+    dz2[co] = da[(size_t)n * c + co] * a * (1.f - a);
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < cs; j += 256) {
+    float s = 0.f;
+    for (int co = 0; co < c; ++co) s += w2[(size_t)co * cs + j] * dz2[co];
+    dz1[j] = hid[j] > 0.f ? s : 0.f;
+  }
+  __syncthreads();
+  for (int ci = threadIdx.x; ci < c; ci += 256) {
+    float s = 0.f;
+    for (int j = 0; j < cs; ++j) s += w1[(size_t)j * c + ci] * dz1[j];
+    dpool[(size_t)n * c + ci] = s / (float)HW;
+    dz2o[(size_t)n * c + ci] = dz2[ci];
+    pooledo[(size_t)n * c + ci] = pooled[ci];
+  }
+  for (int j = threadIdx.x; j < cs; j += 256) {
+    dz1o[(size_t)n * cs + j] = dz1[j];
+    hido[(size_t)n * cs + j] = hid[j];
+  }
+}
+
+// dW[r][j] = sum_b dr[b][r] in[b][j], db[r] = sum_b dr[b][r]: the gradients of a Linear / 1x1 on per-image vectors
+__global__ void __launch_bounds__(256) naf_linear_w_kernel(const float* __restrict__ dr, const float* __restrict__ in, float* __restrict__ gw,
+                                                           float* __restrict__ gb, int N, int R, int K) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)R * K) return;
+  const int r = (int)(i / K), j = (int)(i - (size_t)r * K);
+  float s = 0.f, sb = 0.f;
+  for (int b = 0; b < N; ++b) {
+    s += dr[(size_t)b * R + r] * in[(size_t)b * K + j];
+    sb += dr[(size_t)b * R + r];
+  }
+  gw[i] = s;
+  if (j == 0) gb[r] = sb;
+}
+
+// enhance: out = g a[n][ch] + dpool[n][ch]
+__global__ void __launch_bounds__(256) naf_scale_add_kernel(const float* __restrict__ g, const float* __restrict__ a, const float* __restrict__ dpool,
+                                                            float* __restrict__ out, int HW, int c, size_t total) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int ch = (int)(i % c);
+  const size_t n = i / ((size_t)HW * c);
+  out[i] = g[i] * a[n * c + ch] + dpool[n * c + ch];
+}
+
+__global__ void __launch_bounds__(256) naf_relu_mask_kernel(float* __restrict__ g, const float* __restrict__ y, size_t total) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < total && !(y[i] > 0.f)) g[i] = 0.f;
+}
+
+// g = 2 g + t: x + (rcab(x) + x) passes its gradient to x twice
+__global__ void __launch_bounds__(256) naf_twice_plus_kernel(float* __restrict__ g, const float* __restrict__ t, size_t total) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < total) g[i] = 2.f * g[i] + t[i];
+}
+
+// The blocks' Linear(2w, 4c) backward, one thread per row r.  In: drows[b][r] = the gradient of the FOLDED row (shift, or
+// (scale + 1) g).  Unfolds: d g[ch] = sum_b d[b] (raw[b] + 1), d raw[b] = d[b] g[ch]; then d bias, d W[r][:].  drows becomes d raw.
+// rowmap: [3][R] flat indices of W[r][0], bias[r] and g[ch] (-1 on shift rows).
+__global__ void __launch_bounds__(256) naf_rows_bwd_kernel(const float* __restrict__ tg, const float* __restrict__ wT, const float* __restrict__ bias,
+                                                           const float* __restrict__ mul, const int* __restrict__ rowmap, float* __restrict__ drows,
+                                                           float* __restrict__ grad, int N, int K, int R) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  const int iw = rowmap[r], ib = rowmap[R + r], ig = rowmap[2 * R + r];
+  float dg = 0.f, db = 0.f;
+  for (int b = 0; b < N; ++b) {
+    float d = drows[(size_t)b * R + r];
+    if (ig >= 0) {
+      float a = 0.f;
+      for (int j = 0; j < K; ++j) a += wT[(size_t)j * R + r] * tg[(size_t)b * K + j];
+      dg += d * ((a + bias[r]) + 1.f);
+      d *= mul[r];
+      drows[(size_t)b * R + r] = d;
+    }
+    db += d;
+  }
+  if (ig >= 0) grad[ig] = dg;
+  grad[ib] = db;
+  for (int j = 0; j < K; ++j) {
+    float s = 0.f;
+    for (int b = 0; b < N; ++b) s += drows[(size_t)b * R + r] * tg[(size_t)b * K + j];
+    grad[iw + j] = s;
+  }
+}
+
+// dtg[b][j] = sum_r draw[b][r] W[r][j]; one block per (j, b), a fixed tree over 256 interleaved partial sums
+__global__ void __launch_bounds__(256) naf_dtg_kernel(const float* __restrict__ drows, const float* __restrict__ wT, float* __restrict__ dtg, int K, int R) {
+  __shared__ float red[256];
+  const int j = blockIdx.x, b = blockIdx.y;
+  float s = 0.f;
+  for (int r = threadIdx.x; r < R; r += 256) s += drows[(size_t)b * R + r] * wT[(size_t)j * R + r];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) dtg[(size_t)b * K + j] = red[0];
+}
+
+// time_mlp backward for one time value: the forward of naf_time_kernel again, then back to d h2 [4w], g1 [4w], d h1 [8w], emb [w]
+__global__ void __launch_bounds__(256) naf_time_bwd_kernel(const float* __restrict__ time, const float* __restrict__ freq, const float* __restrict__ w1,
+                                                           const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
+                                                           const float* __restrict__ dtg, float* __restrict__ dh2o, float* __restrict__ g1o,
+                                                           float* __restrict__ dh1o, float* __restrict__ embo, int wd) {
+  extern __shared__ float lds[];
+  float* emb = lds;            // [wd]
+  float* h1 = emb + wd;        // [8 wd]
+  float* g1 = h1 + 8 * wd;     // [4 wd]
+  float* h2 = g1 + 4 * wd;     // [4 wd]
+  float* dh2 = h2 + 4 * wd;    // [4 wd]
+  const int b = blockIdx.x, half = wd / 2;
+  const float tv = time[b];
+  for (int j = threadIdx.x; j < wd; j += 256) {
+    const float a = __fmul_rn(tv, freq[j < half ? j : j - half]);
+    emb[j] = j < half ? sinf(a) : cosf(a);
+  }
+  __syncthreads();
+  for (int r = threadIdx.x; r < 8 * wd; r += 256) {
+    float a = 0.f;
+    for (int j = 0; j < wd; ++j) a += w1[(size_t)r * wd + j] * emb[j];
+    h1[r] = a + b1[r];
+  }
+  __syncthreads();
+  for (int r = threadIdx.x; r < 4 * wd; r += 256) g1[r] = h1[r] * h1[r + 4 * wd];
+  __syncthreads();
+  for (int r = threadIdx.x; r < 4 * wd; r += 256) {
+    float a = 0.f;
+    for (int j = 0; j < 4 * wd; ++j) a += w2[(size_t)r * 4 * wd + j] * g1[j];
+    h2[r] = a + b2[r];
+  }
+  __syncthreads();
+  for (int r = threadIdx.x; r < 2 * wd; r += 256) {
+    const float d = dtg[(size_t)b * 2 * wd + r];
+    dh2[r] = d * h2[r + 2 * wd];
+    dh2[r + 2 * wd] = d * h2[r];
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < 4 * wd; j += 256) {
+    float s = 0.f;
+    for (int r = 0; r < 4 * wd; ++r) s += w2[(size_t)r * 4 * wd + j] * dh2[r];
+    dh1o[(size_t)b * 8 * wd + j] = s * h1[j + 4 * wd];
+    dh1o[(size_t)b * 8 * wd + 4 * wd + j] = s * h1[j];
+    dh2o[(size_t)b * 4 * wd + j] = dh2[j];
+    g1o[(size_t)b * 4 * wd + j] = g1[j];
+  }
+  for (int j = threadIdx.x; j < wd; j += 256) embo[(size_t)b * wd + j] = emb[j];
+}
+
+__global__ void naf_i2f_kernel(const int* __restrict__ t, float* __restrict__ f, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) f[i] = (float)t[i];
+}
+
+struct LossTables { const float *theta, *sigma, *sbar, *cum; float dt; int T; };
+
+// The loss head on the cropped image.  Per element, rounded operations in the reference's order:
+//   expect = x - (theta (mu - x) - sigma^2 (-eps / sbar)) dt;  optimum = term1 (x - mu) + term2 (x0 - mu) + mu
+// term1, term2 (reverse_optimum_step's A, B, C) are evaluated per image in fp64 from the fp32 tables and rounded once: 1 - B^2 cancels
+// at small t, where an fp32 evaluation is only good to ~1e-5.  Writes d eps (padded NHWC; the border stays zero) and the block's sum
+// of |diff| or diff^2 (a fixed tree) to part[n][block].
+__global__ void __launch_bounds__(256) naf_loss_kernel(const float* __restrict__ eps, const float* __restrict__ x, const float* __restrict__ mu,
+                                                       const float* __restrict__ x0, const int* __restrict__ tt, LossTables tb, int l2, float gscale,
+                                                       float* __restrict__ deps, float* __restrict__ part, int H, int W, int Hp, int Wp) {
+  __shared__ float red[256];
+  const int n = blockIdx.y, HW = H * W;
+  int t = tt[n];
+  t = t < 1 ? 1 : t > tb.T ? tb.T : t;
+  const float theta = tb.theta[t], sigma = tb.sigma[t], sbar = tb.sbar[t];
+  const double dt = (double)tb.dt;
+  const double A = exp(-(double)theta * dt), B = exp(-(double)tb.cum[t] * dt), C = exp(-(double)tb.cum[t - 1] * dt);
+  const float term1 = (float)(A * (1.0 - C * C) / (1.0 - B * B)), term2 = (float)(C * (1.0 - A * A) / (1.0 - B * B));
+  const float s2 = __fmul_rn(sigma, sigma);
+  const float dexp = -(s2 / sbar) * tb.dt;   // d expect / d eps
+  float sum = 0.f;
+  for (int q = 0; q < 4; ++q) {
+    const int pix = (blockIdx.x * 4 + q) * 256 + threadIdx.x;
+    if (pix >= HW) break;
+    const int py = pix / W, px = pix - py * W;
+    const size_t ei = (((size_t)n * Hp + py) * Wp + px) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const size_t si = ((size_t)n * 3 + c) * HW + pix;
+      const float xv = x[si], m = mu[si];
+      const float score = __fdiv_rn(-eps[ei + c], sbar);
+      const float drift = __fmul_rn(__fsub_rn(__fmul_rn(theta, __fsub_rn(m, xv)), __fmul_rn(s2, score)), tb.dt);
+      const float expect = __fsub_rn(xv, drift);
+      const float opt = __fadd_rn(__fadd_rn(__fmul_rn(term1, __fsub_rn(xv, m)), __fmul_rn(term2, __fsub_rn(x0[si], m))), m);
+      const float diff = __fsub_rn(expect, opt);
+      float dl;
+      if (l2) { sum += diff * diff; dl = 2.f * diff; }
+      else { sum += fabsf(diff); dl = diff > 0.f ? 1.f : diff < 0.f ? -1.f : 0.f; }
+      deps[ei + c] = dl * gscale * dexp;
+    }
+  }
+  red[threadIdx.x] = sum;
+  __syncthreads();
+  for (int o = 128; o; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[(size_t)n * gridDim.x + blockIdx.x] = red[0];
+}
+
+// loss_out[1 + n] = mean over C H W of image n (its blocks in order); loss_out[0] = weight * mean over the images (in order)
+__global__ void naf_loss_finish_kernel(const float* __restrict__ part, int nblk, int N, float inv_chw, float weight, float* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  float tot = 0.f;
+  for (int n = 0; n < N; ++n) {
+    float s = 0.f;
+    for (int k = 0; k < nblk; ++k) s += part[(size_t)n * nblk + k];
+    s *= inv_chw;
+    out[1 + n] = s;
+    tot += s;
+  }
+  out[0] = weight * (tot / (float)N);
+}
+
+// every scalar is formed on the host in double, as Python forms it, and rounded once (torch hands its kernels such scalars)
+struct OptArgs { float lr, b1, b2, omb1, omb2, decay, eps, wd, step_size, bc2_sqrt; int kind; };
+
+// kind 0 Adam (torch's single-tensor path, weight decay as an L2 term of the gradient), 1 AdamW (decoupled), 2 Lion
+__global__ void __launch_bounds__(256) naf_optim_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                        OptArgs o, size_t total) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  float w = p[i], gr = g[i], mm = m[i];
+  if (o.kind == 2) {
+    w = __fmul_rn(w, o.decay);
+    const float u = __fadd_rn(__fmul_rn(mm, o.b1), __fmul_rn(gr, o.omb1));
+    const float sg = u > 0.f ? 1.f : u < 0.f ? -1.f : 0.f;
+    p[i] = __fadd_rn(w, __fmul_rn(-o.lr, sg));
+    m[i] = __fadd_rn(__fmul_rn(mm, o.b2), __fmul_rn(o.omb2, gr));
+    return;
+  }
+  if (o.kind == 1) w = __fmul_rn(w, o.decay);
+  else if (o.wd != 0.f) gr = __fadd_rn(gr, __fmul_rn(o.wd, w));
+  mm = __fadd_rn(mm, __fmul_rn(o.omb1, __fsub_rn(gr, mm)));                                  // exp_avg.lerp_(grad, 1 - beta1)
+  const float vv = __fadd_rn(__fmul_rn(v[i], o.b2), __fmul_rn(__fmul_rn(o.omb2, gr), gr));   // mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+  const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(vv), o.bc2_sqrt), o.eps);
+  p[i] = __fadd_rn(w, __fmul_rn(-o.step_size, __fdiv_rn(mm, denom)));
+  m[i] = mm;
+  v[i] = vv;
+}
+
+// every device form again from the master: arena[i] = master[map[i]] where the element holds a weight
+__global__ void __launch_bounds__(256) naf_repack_kernel(float* __restrict__ arena, const float* __restrict__ master, const int* __restrict__ map, size_t total) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int s = map[i];
+  if (s >= 0) arena[i] = master[s];
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+
+struct BlockSlots { size_t out, st1, t1, t2, sca, y, st2, p4, g4; };
+
+struct TrainPlan {
+  int N, H, W, Hp, Wp;
+  size_t xin, x0, r1, r, ca, enh, eps, deps, tg, trow, tf, part, losspart;
+  size_t gx, gt, gu, g2a, g2b, drows, dtg, small, wgpart, wg_floats;
+  std::vector<BlockSlots> blk;
+  std::vector<size_t> down, up, dskip;
+  size_t bytes;
+};
+
+int ilog2(int v) { int l = 0; while ((1 << (l + 1)) <= v) ++l; return l; }
+
+// floats of naf_wgrad_kernel's partial sums for gemm g over M output pixels
+size_t wg_need(int K, int cout, int M) {
+  return (size_t)((M + WG_CHUNK - 1) / WG_CHUNK) * round_up(K, 64) * round_up(cout, 64);
+}
+
+TrainPlan make_train_plan(fdsr_nafnet n, int N, int H, int W) {
+  TrainPlan p{};
+  const int pad = 1 << n->L, w = n->wd, L = n->L;
+  p.N = N; p.H = H; p.W = W;
+  p.Hp = round_up(H, pad);
+  p.Wp = round_up(W, pad);
+  const size_t M0 = (size_t)N * p.Hp * p.Wp;
+  size_t off = 0;
+  auto buf = [&](size_t floats) { const size_t o = off; off = align_up(off + floats * sizeof(float), 256); return o; };
+  p.xin = buf(M0 * 6);
+  p.x0 = buf(M0 * w); p.r1 = buf(M0 * w); p.r = buf(M0 * w); p.enh = buf(M0 * w);
+  p.ca = buf((size_t)N * w);
+  p.eps = buf(M0 * 3); p.deps = buf(M0 * 3);
+  p.tg = buf((size_t)N * 2 * w); p.trow = buf((size_t)N * n->R); p.tf = buf(N);
+  size_t part = 0;
+  for (int l = 0; l <= L; ++l) part = std::max(part, (size_t)nstrips_of((p.Hp >> l) * (p.Wp >> l)) * ((size_t)w << l) * 20);   // 10 [2c] rows of conv2
+  p.part = buf((size_t)N * part);
+  p.losspart = buf((size_t)N * ((H * W + 1023) / 1024));
+  p.gx = buf(M0 * w); p.gt = buf(M0 * w); p.gu = buf(M0 * w); p.g2a = buf(M0 * 2 * w); p.g2b = buf(M0 * 2 * w);
+  p.drows = buf((size_t)N * n->R);
+  p.dtg = buf((size_t)N * 2 * w);
+  p.small = buf((size_t)N * (((size_t)w << L) * 4 + 17 * (size_t)w + 64));
+  p.blk.resize(n->blocks.size());
+  for (size_t bi = 0; bi < n->blocks.size(); ++bi) {
+    const int c = n->blocks[bi].c, l = ilog2(c / w);
+    const size_t M = M0 >> (2 * l);
+    BlockSlots& s = p.blk[bi];
+    s.out = buf(M * c); s.st1 = buf(M * 2); s.t1 = buf(M * 2 * c); s.t2 = buf(M * c); s.sca = buf((size_t)N * c);
+    s.y = buf(M * c); s.st2 = buf(M * 2); s.p4 = buf(M * 2 * c); s.g4 = buf(M * c);
+  }
+  for (int l = 0; l < L; ++l) {
+    p.down.push_back(buf((M0 * w) >> (l + 1)));                 // level l + 1
+    p.up.push_back(buf((M0 * w) >> (L - 1 - l)));               // ups[l] lands on level L - 1 - l
+    p.dskip.push_back(buf((M0 * w) >> l));
+  }
+  size_t wg = 0;
+  for (const GemmL& g : n->gemms) {
+    const int l = g.cin < w ? 0 : ilog2(g.cin / w);
+    const size_t M = g.ks == 2 ? M0 >> (2 * (l + 1)) : M0 >> (2 * l);
+    wg = std::max(wg, wg_need(g.K() + 1, g.cout, (int)M));
+  }
+  p.wg_floats = wg;
+  p.wgpart = buf(wg);
+  p.bytes = off;
+  return p;
+}
+
+int ensure_train(fdsr_nafnet n) {
+  if (!n->d_master) {
+    for (float** q : {&n->d_master, &n->d_grad, &n->d_m, &n->d_v}) {
+      HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(q), n->P * sizeof(float)));
+      HIPCHK(nullptr, hipMemset(*q, 0, n->P * sizeof(float)));
+    }
+    std::vector<int> map(n->arena_floats, -1);
+    IndexSink sink{n, map};
+    pack_forms(n, sink);
+    HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_map), map.size() * sizeof(int)));
+    HIPCHK(nullptr, hipMemcpy(n->d_map, map.data(), map.size() * sizeof(int), hipMemcpyHostToDevice));
+    std::vector<int> rm(3 * (size_t)n->R, -1);
+    const int K2 = 2 * n->wd;
+    for (const BlockL& b : n->blocks)
+      for (int r = 0; r < 4 * b.c; ++r) {
+        const int gr = b.row_off + r, chunk = r / b.c, ch = r % b.c;
+        rm[gr] = (int)(n->poff[b.mlpw] + (size_t)r * K2);
+        rm[n->R + gr] = (int)(n->poff[b.mlpb] + r);
+        rm[2 * n->R + gr] = chunk == 1 ? (int)(n->poff[b.g1] + ch) : chunk == 3 ? (int)(n->poff[b.g2] + ch) : -1;
+      }
+    HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_rowmap), rm.size() * sizeof(int)));
+    HIPCHK(nullptr, hipMemcpy(n->d_rowmap, rm.data(), rm.size() * sizeof(int), hipMemcpyHostToDevice));
+  }
+  if (!n->master_valid) {
+    HIPCHK(nullptr, hipDeviceSynchronize());
+    for (size_t i = 0; i < n->wts.size(); ++i)
+      HIPCHK(nullptr, hipMemcpy(n->d_master + n->poff[i], n->wts[i].host.data(), n->wts[i].host.size() * sizeof(float), hipMemcpyHostToDevice));
+    n->master_valid = true;
+  }
+  return FDSR_OK;
+}
+
+struct TrainRun {
+  fdsr_nafnet n;
+  TrainPlan tp;
+  Run r;   // the forward's launchers (its plan carries the sizes only; every buffer is one of tp's)
+  char* ws;
+  hipStream_t st;
+
+  float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
+  const float* P(size_t off) const { return n->d_arena + off; }
+  float* G(int wi) const { return n->d_grad + n->poff[wi]; }
+  static unsigned nb(size_t total) { return (unsigned)((total + 255) / 256); }
+
+  // ---- the saving forward: Run::block / Run::net with every output in its slot ----
+  void block_fwd(int bi, const float* cur, int h, int w) {
+    const BlockL& b = n->blocks[bi];
+    const BlockSlots& s = tp.blk[bi];
+    const int c = b.c, HW = h * w, M = tp.N * HW, ns = nstrips_of(HW);
+    const float* rw = r.rows + b.row_off;
+    r.stats = F(s.st1);
+    r.ln_stats(cur, M, c);
+    r.gemm(b.conv1, cur, F(s.t1), h, w, EPI_BIAS, PRO_LN, rw + c, rw, r.rstride);
+    hipLaunchKernelGGL(naf_dw_gate_kernel, dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)tp.N), dim3(256), 0, st, F(s.t1), P(b.off_dww),
+                       P(b.off_dwb), F(s.t2), F(tp.part), h, w, c, ns);
+    r.check();
+    hipLaunchKernelGGL(naf_sca_kernel, dim3((unsigned)((c + 15) / 16), (unsigned)tp.N), dim3(256), (c + 256) * sizeof(float), st, F(tp.part), ns, HW,
+                       P(b.off_scaw), P(b.off_scab), F(s.sca), c);
+    r.check();
+    r.gemm(b.conv3, F(s.t2), F(s.y), h, w, EPI_RES, PRO_MUL, F(s.sca), nullptr, c, cur, P(b.off_beta));
+    r.stats = F(s.st2);
+    r.ln_stats(F(s.y), M, c);
+    r.gemm_l(n->gemms[b.conv4], F(s.y), F(s.g4), h, w, EPI_GATE, PRO_LN, rw + 3 * c, rw + 2 * c, r.rstride, nullptr, nullptr, F(s.p4));
+    r.gemm(b.conv5, F(s.g4), F(s.out), h, w, EPI_RES, PRO_NONE, nullptr, nullptr, 0, F(s.y), P(b.off_gamma));
+  }
+
+  // the input of block j of a list whose first block reads `first`
+  const float* chain_in(const std::vector<int>& list, size_t j, const float* first) const { return j == 0 ? first : F(tp.blk[list[j - 1]].out); }
+  const float* chain_out(const std::vector<int>& list, const float* first) const { return list.empty() ? first : F(tp.blk[list.back()].out); }
+  const float* enc_in(int i) const { return i == 0 ? F(tp.enh) : F(tp.down[i - 1]); }
+  const float* mid_in() const { return F(tp.down[n->L - 1]); }
+
+  void net_fwd() {
+    const int wd = n->wd, L = n->L;
+    int h = tp.Hp, w = tp.Wp;
+    r.gemm(n->g_intro, F(tp.xin), F(tp.x0), h, w, EPI_BIAS);
+    r.gemm(n->g_rcab0, F(tp.x0), F(tp.r1), h, w, EPI_RELU);
+    r.gemm(n->g_rcab2, F(tp.r1), F(tp.r), h, w, EPI_BIAS);
+    {
+      const int HW = h * w, ns = nstrips_of(HW);
+      hipLaunchKernelGGL(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)tp.N), dim3(256), 0, st, F(tp.r), F(tp.part), HW,
+                         wd, ns);
+      r.check();
+      hipLaunchKernelGGL(naf_ca_kernel, dim3((unsigned)tp.N), dim3(256), (wd + 256 + wd / 16) * sizeof(float), st, F(tp.part), ns, HW, P(n->off_ca1w),
+                         P(n->off_ca1b), P(n->off_ca2w), P(n->off_ca2b), F(tp.ca), wd, wd / 16);
+      r.check();
+      const size_t total = (size_t)tp.N * HW * wd;
+      hipLaunchKernelGGL(naf_enhance_kernel, dim3(nb(total)), dim3(256), 0, st, F(tp.x0), F(tp.r), F(tp.ca), F(tp.enh), HW, wd, total);
+      r.check();
+    }
+    for (int i = 0; i < L; ++i) {
+      for (size_t j = 0; j < n->enc[i].size(); ++j) block_fwd(n->enc[i][j], chain_in(n->enc[i], j, enc_in(i)), h, w);
+      r.gemm(n->downs[i], chain_out(n->enc[i], enc_in(i)), F(tp.down[i]), h, w, EPI_BIAS);
+      h /= 2; w /= 2;
+    }
+    for (size_t j = 0; j < n->mid.size(); ++j) block_fwd(n->mid[j], chain_in(n->mid, j, mid_in()), h, w);
+    const float* cur = chain_out(n->mid, mid_in());
+    for (int i = 0; i < L; ++i) {
+      const float* skip = chain_out(n->enc[L - 1 - i], enc_in(L - 1 - i));
+      r.gemm(n->ups[i], cur, F(tp.up[i]), h, w, EPI_PSHUF, PRO_NONE, nullptr, nullptr, 0, skip);
+      h *= 2; w *= 2;
+      for (size_t j = 0; j < n->dec[i].size(); ++j) block_fwd(n->dec[i][j], chain_in(n->dec[i], j, F(tp.up[i])), h, w);
+      cur = chain_out(n->dec[i], F(tp.up[i]));
+    }
+    r.stats = nullptr;
+    r.gemm(n->g_ending, cur, F(tp.eps), h, w, EPI_BIAS);
+  }
+
+  // ---- backward launchers ----
+  // weight (and bias) gradient of gemm gi: x its forward input (Hin x Win), dy [M][cout]
+  void wgrad(int gi, const float* x, const float* dy, int Hin, int Win, int pro = PRO_NONE, const float* stats = nullptr, const float* pmul = nullptr,
+             const float* padd = nullptr, int pstride = 0, const float* colmul = nullptr) {
+    const GemmL& g = n->gemms[gi];
+    WgArgs a{};
+    a.x = x; a.dy = dy; a.stats = stats; a.pmul = pmul; a.padd = padd; a.colmul = colmul; a.part = F(tp.wgpart);
+    a.N = tp.N; a.Hin = Hin; a.Win = Win; a.Cin = g.cin;
+    a.Hout = (Hin + 2 * g.p - g.ks) / g.s + 1;
+    a.Wout = (Win + 2 * g.p - g.ks) / g.s + 1;
+    a.Cout = g.cout; a.KW = g.ks; a.S = g.s; a.P = g.p; a.K = g.K(); a.Keff = g.b >= 0 ? a.K + 1 : a.K; a.ldy = g.cout; a.pstride = pstride;
+    wgrad_launch(a, pro, 0, g.ks * g.ks, G(g.w), g.b >= 0 ? G(g.b) : nullptr);
+  }
+
+  void wgrad_launch(const WgArgs& a, int pro, int mode, int taps, float* gw, float* gb) {
+    const int M = a.N * a.Hout * a.Wout, nz = (M + WG_CHUNK - 1) / WG_CHUNK;
+    const dim3 grid((unsigned)((a.Keff + 63) / 64), (unsigned)((a.Cout + 63) / 64), (unsigned)nz);
+    if ((size_t)nz * grid.x * 64 * grid.y * 64 > tp.wg_floats) {
+      if (r.err == FDSR_OK) r.err = fail(nullptr, FDSR_E_WORKSPACE, "fdsr_nafnet_train_grads: weight-gradient scratch too small");
+      return;
+    }
+    if (pro == PRO_LN) hipLaunchKernelGGL((naf_wgrad_kernel<PRO_LN>), grid, dim3(256), 0, st, a);
+    else if (pro == PRO_MUL) hipLaunchKernelGGL((naf_wgrad_kernel<PRO_MUL>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((naf_wgrad_kernel<PRO_NONE>), grid, dim3(256), 0, st, a);
+    r.check();
+    hipLaunchKernelGGL(naf_wgrad_finish_kernel, dim3(nb((size_t)a.Keff * a.Cout)), dim3(256), 0, st, a.part, nz, (int)grid.x * 64, (int)grid.y * 64,
+                       a.Keff, a.K, a.Cout, a.Cin, taps, mode, gw, gb);
+    r.check();
+  }
+
+  // per-channel sums over pixels: dst[g][ch], groups = N (per image, rows dstride apart) or 1 (everything)
+  void dot(const float* a, const float* b, const float* stats, int mode, int HW, int c, float* dst, bool per_image, int dstride, float scale = 1.f) {
+    const int ns = nstrips_of(HW);
+    hipLaunchKernelGGL(naf_dot_kernel, dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)tp.N), dim3(256), 0, st, a, b, stats, F(tp.part), HW, c, ns,
+                       mode);
+    r.check();
+    const int groups = per_image ? tp.N : 1, Gn = per_image ? ns : tp.N * ns;
+    hipLaunchKernelGGL(naf_reduce_kernel, dim3(nb((size_t)groups * c)), dim3(256), 0, st, F(tp.part), dst, groups, Gn, c, scale, dstride);
+    r.check();
+  }
+
+  // LayerNorm + FiLM backward: g += d x; the image's d (folded scale) and d shift rows into drows
+  void ln_bwd(const float* x, const float* d, const float* stats, const float* mulrow, float* g, int HW, int c, float* dmul, float* dadd) {
+    const int M = tp.N * HW;
+    dot(d, x, stats, 2, HW, c, dmul, true, n->R);
+    dot(d, nullptr, nullptr, 0, HW, c, dadd, true, n->R);
+    hipLaunchKernelGGL(naf_ln_bwd_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, st, x, d, stats, mulrow, r.rstride, g, M, HW, c);
+    r.check();
+  }
+
+  // g: d out on entry, d inp on return (in place); cur: the block's input
+  void block_bwd(int bi, const float* cur, float* g, int h, int w) {
+    const BlockL& b = n->blocks[bi];
+    const BlockSlots& s = tp.blk[bi];
+    const int c = b.c, HW = h * w, M = tp.N * HW, ns = nstrips_of(HW);
+    const size_t tot = (size_t)M * c;
+    const float* rw = r.rows + b.row_off;
+    float *gt = F(tp.gt), *g2a = F(tp.g2a), *g2b = F(tp.g2b), *dr = F(tp.drows) + b.row_off;
+    float* sm = F(tp.small);
+    float *ds = sm, *pooled = sm + (size_t)tp.N * c, *dpool = sm + 2 * (size_t)tp.N * c;
+    // out = y + conv5(g4) gamma
+    r.gemm(b.conv5, F(s.g4), gt, h, w, EPI_BIAS);
+    dot(g, gt, nullptr, 1, HW, c, G(b.gamma), false, 0);
+    wgrad(b.conv5, F(s.g4), g, h, w, PRO_NONE, nullptr, nullptr, nullptr, 0, P(b.off_gamma));
+    r.gemm_l(n->tgemms[b.conv5], g, gt, h, w, EPI_BIAS, PRO_MUL, P(b.off_gamma), nullptr, 0);
+    hipLaunchKernelGGL(naf_gate_bwd_kernel, dim3(nb(tot)), dim3(256), 0, st, gt, F(s.p4), g2a, c, tot);
+    r.check();
+    wgrad(b.conv4, F(s.y), g2a, h, w, PRO_LN, F(s.st2), rw + 3 * c, rw + 2 * c, r.rstride);
+    r.gemm_l(n->tgemms[b.conv4], g2a, gt, h, w, EPI_BIAS);
+    ln_bwd(F(s.y), gt, F(s.st2), rw + 3 * c, g, HW, c, dr + 3 * c, dr + 2 * c);
+    // y = inp + conv3(t2 sca) beta
+    r.gemm(b.conv3, F(s.t2), gt, h, w, EPI_BIAS, PRO_MUL, F(s.sca), nullptr, c);
+    dot(g, gt, nullptr, 1, HW, c, G(b.beta), false, 0);
+    wgrad(b.conv3, F(s.t2), g, h, w, PRO_MUL, nullptr, F(s.sca), nullptr, c, P(b.off_beta));
+    r.gemm_l(n->tgemms[b.conv3], g, gt, h, w, EPI_BIAS, PRO_MUL, P(b.off_beta), nullptr, 0);
+    dot(gt, F(s.t2), nullptr, 1, HW, c, ds, true, c);
+    dot(F(s.t2), nullptr, nullptr, 0, HW, c, pooled, true, c, 1.f / (float)HW);
+    hipLaunchKernelGGL(naf_sca_bwd_w_kernel, dim3(nb((size_t)c * c)), dim3(256), 0, st, ds, pooled, G(b.scaw), G(b.scab), tp.N, c);
+    r.check();
+    hipLaunchKernelGGL(naf_sca_bwd_x_kernel, dim3(nb((size_t)tp.N * c)), dim3(256), 0, st, ds, P(b.off_scaw), dpool, tp.N, c, 1.f / (float)HW);
+    r.check();
+    hipLaunchKernelGGL(naf_dwgate_bwd_kernel, dim3(nb(tot)), dim3(256), 0, st, F(s.t1), P(b.off_dww), P(b.off_dwb), gt, F(s.sca), dpool, g2a, h, w, c, tot);
+    r.check();
+    hipLaunchKernelGGL(naf_dw_bwd_kernel, dim3((unsigned)ns, (unsigned)((2 * c + 63) / 64), (unsigned)tp.N), dim3(256), 0, st, F(s.t1), P(b.off_dww), g2a,
+                       g2b, F(tp.part), h, w, 2 * c, ns);
+    r.check();
+    hipLaunchKernelGGL(naf_dw_finish_kernel, dim3(nb((size_t)20 * c)), dim3(256), 0, st, F(tp.part), tp.N * ns, 2 * c, G(b.dww), G(b.dwb));
+    r.check();
+    wgrad(b.conv1, cur, g2b, h, w, PRO_LN, F(s.st1), rw + c, rw, r.rstride);
+    r.gemm_l(n->tgemms[b.conv1], g2b, gt, h, w, EPI_BIAS);
+    ln_bwd(cur, gt, F(s.st1), rw + c, g, HW, c, dr + c, dr);
+  }
+
+  void chain_bwd(const std::vector<int>& list, const float* first, float* g, int h, int w) {
+    for (size_t j = list.size(); j-- > 0;) block_bwd(list[j], chain_in(list, j, first), g, h, w);
+  }
+
+  void net_bwd() {
+    const int wd = n->wd, L = n->L;
+    int h = tp.Hp, w = tp.Wp, c = wd;
+    float *g = F(tp.gx), *gt = F(tp.gt), *gu = F(tp.gu);
+    const float* last = chain_out(n->dec[L - 1], F(tp.up[L - 1]));
+    wgrad(n->g_ending, last, F(tp.deps), h, w);
+    r.gemm_l(n->tgemms[n->g_ending], F(tp.deps), g, h, w, EPI_BIAS);
+    for (int i = L - 1; i >= 0; --i) {
+      chain_bwd(n->dec[i], F(tp.up[i]), g, h, w);
+      // ups[i]: g is d (shuffle(conv(x)) + skip).  The skip's share is g itself; the convolution's is a 2x2 stride-2 gather of g.
+      const size_t bytes = (size_t)tp.N * h * w * c * sizeof(float);
+      (void)hipMemcpyAsync(F(tp.dskip[L - 1 - i]), g, bytes, hipMemcpyDeviceToDevice, st);
+      r.check();
+      const float* x = i == 0 ? chain_out(n->mid, mid_in()) : chain_out(n->dec[i - 1], F(tp.up[i - 1]));
+      const GemmL& t = n->tgemms[n->ups[i]];
+      const GemmL& gf = n->gemms[n->ups[i]];
+      {
+        WgArgs a{};   // operands exchanged: the gathered gradient is A, the forward input is "dy"
+        a.x = F(tp.dskip[L - 1 - i]); a.dy = x; a.part = F(tp.wgpart);
+        a.N = tp.N; a.Hin = h; a.Win = w; a.Cin = t.cin; a.Hout = h / 2; a.Wout = w / 2; a.Cout = t.cout; a.KW = 2; a.S = 2; a.P = 0;
+        a.K = t.K(); a.Keff = a.K; a.ldy = t.cout;
+        wgrad_launch(a, PRO_NONE, 1, 4, G(gf.w), nullptr);
+      }
+      r.gemm_l(t, F(tp.dskip[L - 1 - i]), g, h, w, EPI_BIAS);
+      h /= 2; w /= 2; c *= 2;
+    }
+    chain_bwd(n->mid, mid_in(), g, h, w);
+    for (int i = L - 1; i >= 0; --i) {
+      // downs[i]: g is d out at level i + 1
+      const float* x = chain_out(n->enc[i], enc_in(i));
+      wgrad(n->downs[i], x, g, 2 * h, 2 * w);
+      r.gemm_l(n->tgemms[n->downs[i]], g, gt, h, w, EPI_PSHUF, PRO_NONE, nullptr, nullptr, 0, F(tp.dskip[i]));
+      h *= 2; w *= 2; c /= 2;
+      (void)hipMemcpyAsync(g, gt, (size_t)tp.N * h * w * c * sizeof(float), hipMemcpyDeviceToDevice, st);
+      r.check();
+      chain_bwd(n->enc[i], enc_in(i), g, h, w);
+    }
+    // enh = x0 + (r a + x0), a = CA(mean r)
+    const int HW = h * w, ns = nstrips_of(HW), cs = wd / 16;
+    const size_t tot = (size_t)tp.N * HW * wd;
+    float* sm = F(tp.small);
+    float *da = sm, *dz2 = sm + (size_t)tp.N * wd, *pooled = sm + 2 * (size_t)tp.N * wd, *dpool = sm + 3 * (size_t)tp.N * wd,
+          *dz1 = sm + 4 * (size_t)tp.N * wd, *hid = dz1 + (size_t)tp.N * cs;
+    dot(g, F(tp.r), nullptr, 1, HW, wd, da, true, wd);
+    hipLaunchKernelGGL(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)tp.N), dim3(256), 0, st, F(tp.r), F(tp.part), HW, wd, ns);
+    r.check();
+    hipLaunchKernelGGL(naf_ca_bwd_kernel, dim3((unsigned)tp.N), dim3(256), (3 * wd + 256 + 2 * cs) * sizeof(float), st, F(tp.part), ns, HW, P(n->off_ca1w),
+                       P(n->off_ca1b), P(n->off_ca2w), F(tp.ca), da, dz2, dz1, hid, pooled, dpool, wd, cs);
+    r.check();
+    hipLaunchKernelGGL(naf_linear_w_kernel, dim3(nb((size_t)wd * cs)), dim3(256), 0, st, dz2, hid, G(n->ca2w), G(n->ca2b), tp.N, wd, cs);
+    r.check();
+    hipLaunchKernelGGL(naf_linear_w_kernel, dim3(nb((size_t)wd * cs)), dim3(256), 0, st, dz1, pooled, G(n->ca1w), G(n->ca1b), tp.N, cs, wd);
+    r.check();
+    hipLaunchKernelGGL(naf_scale_add_kernel, dim3(nb(tot)), dim3(256), 0, st, g, F(tp.ca), dpool, gt, HW, wd, tot);
+    r.check();
+    wgrad(n->g_rcab2, F(tp.r1), gt, h, w);
+    r.gemm_l(n->tgemms[n->g_rcab2], gt, gu, h, w, EPI_BIAS);
+    hipLaunchKernelGGL(naf_relu_mask_kernel, dim3(nb(tot)), dim3(256), 0, st, gu, F(tp.r1), tot);
+    r.check();
+    wgrad(n->g_rcab0, F(tp.x0), gu, h, w);
+    r.gemm_l(n->tgemms[n->g_rcab0], gu, gt, h, w, EPI_BIAS);
+    hipLaunchKernelGGL(naf_twice_plus_kernel, dim3(nb(tot)), dim3(256), 0, st, g, gt, tot);
+    r.check();
+    wgrad(n->g_intro, F(tp.xin), g, h, w);
+  }
+
+  // the rows back through every block's Linear, SimpleGate and time_mlp
+  void time_bwd() {
+    const int wd = n->wd, K2 = 2 * wd, R = n->R, N = tp.N;
+    hipLaunchKernelGGL(naf_rows_bwd_kernel, dim3(nb(R)), dim3(256), 0, st, F(tp.tg), P(n->off_rowsw), P(n->off_rowsb), P(n->off_rowsmul), n->d_rowmap,
+                       F(tp.drows), n->d_grad, N, K2, R);
+    r.check();
+    hipLaunchKernelGGL(naf_dtg_kernel, dim3((unsigned)K2, (unsigned)N), dim3(256), 0, st, F(tp.drows), P(n->off_rowsw), F(tp.dtg), K2, R);
+    r.check();
+    float* sm = F(tp.small);
+    float *dh2 = sm, *g1 = sm + (size_t)N * 4 * wd, *dh1 = sm + (size_t)N * 8 * wd, *emb = sm + (size_t)N * 16 * wd;
+    hipLaunchKernelGGL(naf_time_bwd_kernel, dim3((unsigned)N), dim3(256), 21 * wd * sizeof(float), st, F(tp.tf), P(n->off_freq), P(n->off_t1w), P(n->off_t1b),
+                       P(n->off_t2w), P(n->off_t2b), F(tp.dtg), dh2, g1, dh1, emb, wd);
+    r.check();
+    hipLaunchKernelGGL(naf_linear_w_kernel, dim3(nb((size_t)16 * wd * wd)), dim3(256), 0, st, dh2, g1, G(n->t2w), G(n->t2b), N, 4 * wd, 4 * wd);
+    r.check();
+    hipLaunchKernelGGL(naf_linear_w_kernel, dim3(nb((size_t)8 * wd * wd)), dim3(256), 0, st, dh1, emb, G(n->t1w), G(n->t1b), N, 8 * wd, wd);
+    r.check();
+  }
+};
+
+int find_weight(fdsr_nafnet n, const char* fn, const char* key) {
+  if (!n || !key) return fail(nullptr, FDSR_E_INVALID, "%s: null argument", fn);
+  const auto it = n->key2w.find(key);
+  if (it == n->key2w.end()) return fail(nullptr, FDSR_E_KEY, "%s: unknown tensor '%s'", fn, key);
+  return it->second;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fdsr_nafnet_set_thetas_cumsum(fdsr_nafnet n, int T, const float* thetas_cumsum) {
+  if (!n || !thetas_cumsum || T < 1) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_set_thetas_cumsum: bad arguments (T %d)", T);
+  if (n->T != T) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet_set_thetas_cumsum: T %d is not the schedule's (fdsr_nafnet_set_sde first)", T);
+  HIPCHK(nullptr, hipDeviceSynchronize());
+  if (n->d_cum) { (void)hipFree(n->d_cum); n->d_cum = nullptr; }
+  HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_cum), (size_t)(T + 1) * sizeof(float)));
+  HIPCHK(nullptr, hipMemcpy(n->d_cum, thetas_cumsum, (size_t)(T + 1) * sizeof(float), hipMemcpyHostToDevice));
+  n->cum_T = T;
+  return FDSR_OK;
+}
+
+int fdsr_nafnet_train_workspace_bytes(fdsr_nafnet n, int batch, int height, int width, size_t* bytes) {
+  if (!n || !bytes || batch < 1 || height < 1 || width < 1)
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_train_workspace_bytes: bad arguments (B %d, %dx%d)", batch, height, width);
+  *bytes = make_train_plan(n, batch, height, width).bytes;
+  return FDSR_OK;
+}
+
+int fdsr_nafnet_train_grads(fdsr_nafnet n, const float* state_nchw, const float* cond_nchw, const float* gt_nchw, const int32_t* timesteps_dev,
+                            int loss_type, float weight, float* loss_out_dev, int batch, int height, int width, void* workspace,
+                            size_t workspace_bytes, void* hip_stream) {
+  const char* fn = "fdsr_nafnet_train_grads";
+  if (!n || !state_nchw || !cond_nchw || !gt_nchw || !timesteps_dev || !loss_out_dev || !workspace || batch < 1 || height < 1 || width < 1)
+    return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, batch, height, width);
+  if (loss_type & FDSR_NAFNET_LOSS_WEIGHTED) return fail(nullptr, FDSR_E_INVALID, "%s: is_weighted is not supported (the reference passes no weights)", fn);
+  if (loss_type != FDSR_NAFNET_LOSS_L1 && loss_type != FDSR_NAFNET_LOSS_L2) return fail(nullptr, FDSR_E_INVALID, "%s: loss_type %d (l1 = 0, l2 = 1)", fn, loss_type);
+  if ((size_t)batch * round_up(height, 1 << n->L) * round_up(width, 1 << n->L) * 2 * n->wd >= (1ull << 31) || batch > 65535)
+    return fail(nullptr, FDSR_E_INVALID, "%s: B %d at %dx%d exceeds the 32-bit pixel indexing of the kernels", fn, batch, height, width);
+  for (const WT& w : n->wts)
+    if (!w.loaded) return fail(nullptr, FDSR_E_STATE, "%s: tensor '%s' is missing", fn, w.key.c_str());
+  if (n->T < 1 || n->cum_T != n->T) return fail(nullptr, FDSR_E_STATE, "%s: no schedule (fdsr_nafnet_set_sde, fdsr_nafnet_set_thetas_cumsum)", fn);
+  const TrainPlan tp = make_train_plan(n, batch, height, width);
+  if (workspace_bytes < tp.bytes || (reinterpret_cast<uintptr_t>(workspace) & 255))
+    return fail(nullptr, FDSR_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes) or not 256-byte aligned", fn, workspace_bytes, tp.bytes);
+  int rc = finalize(n);
+  if (rc) return rc;
+  if ((rc = ensure_train(n))) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  Plan pl{};
+  pl.N = batch; pl.H = height; pl.W = width; pl.Hp = tp.Hp; pl.Wp = tp.Wp;
+  TrainRun t{n, tp, Run{n, pl, static_cast<char*>(workspace), st, nullptr, n->R}, static_cast<char*>(workspace), st};
+  HIPCHK(nullptr, hipMemsetAsync(n->d_grad, 0, n->P * sizeof(float), st));
+  HIPCHK(nullptr, hipMemsetAsync(t.F(tp.deps), 0, (size_t)batch * tp.Hp * tp.Wp * 3 * sizeof(float), st));
+  hipLaunchKernelGGL(naf_i2f_kernel, dim3(TrainRun::nb(batch)), dim3(256), 0, st, timesteps_dev, t.F(tp.tf), batch);
+  t.r.check();
+  t.r.time_rows(t.F(tp.tf), batch, t.F(tp.tg), t.F(tp.trow));
+  t.r.rows = t.F(tp.trow);
+  {
+    const size_t total = (size_t)batch * tp.Hp * tp.Wp;
+    hipLaunchKernelGGL(naf_prep_kernel, dim3(TrainRun::nb(total)), dim3(256), 0, st, state_nchw, cond_nchw, t.F(tp.xin), height, width, tp.Hp, tp.Wp, total);
+    t.r.check();
+  }
+  t.net_fwd();
+  {
+    LossTables tb{n->d_sde, n->d_sde + (n->T + 1), n->d_sde + 2 * (n->T + 1), n->d_cum, n->dt, n->T};
+    const int HW = height * width, nblk = (HW + 1023) / 1024;
+    const float gscale = weight / ((float)batch * 3.f * (float)HW);
+    hipLaunchKernelGGL(naf_loss_kernel, dim3((unsigned)nblk, (unsigned)batch), dim3(256), 0, st, t.F(tp.eps), state_nchw, cond_nchw, gt_nchw, timesteps_dev,
+                       tb, loss_type == FDSR_NAFNET_LOSS_L2 ? 1 : 0, gscale, t.F(tp.deps), t.F(tp.losspart), height, width, tp.Hp, tp.Wp);
+    t.r.check();
+    hipLaunchKernelGGL(naf_loss_finish_kernel, dim3(1), dim3(64), 0, st, t.F(tp.losspart), nblk, batch, 1.f / (3.f * (float)HW), weight, loss_out_dev);
+    t.r.check();
+  }
+  t.net_bwd();
+  t.time_bwd();
+  return t.r.err;
+}
+
+int fdsr_nafnet_grad_buffer(fdsr_nafnet n, float** device_ptr, size_t* count) {
+  if (!n || !device_ptr || !count) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_grad_buffer: null argument");
+  if (!n->d_grad) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet_grad_buffer: no gradients yet (fdsr_nafnet_train_grads)");
+  *device_ptr = n->d_grad;
+  *count = n->P;
+  return FDSR_OK;
+}
+
+int fdsr_nafnet_read_grad(fdsr_nafnet n, const char* key, float* host_f32) {
+  if (!host_f32) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_read_grad: null argument");
+  const int wi = find_weight(n, "fdsr_nafnet_read_grad", key);
+  if (wi < 0) return wi;
+  if (!n->d_grad) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet_read_grad: no gradients yet (fdsr_nafnet_train_grads)");
+  HIPCHK(nullptr, hipDeviceSynchronize());
+  HIPCHK(nullptr, hipMemcpy(host_f32, n->d_grad + n->poff[wi], numel(n->wts[wi].shape) * sizeof(float), hipMemcpyDeviceToHost));
+  return FDSR_OK;
+}
+
+int fdsr_nafnet_optim_step(fdsr_nafnet n, int kind, double lr, double beta1, double beta2, double eps, double weight_decay, void* hip_stream) {
+  if (!n || kind < FDSR_NAFNET_ADAM || kind > FDSR_NAFNET_LION || !(lr >= 0.) || !(beta1 >= 0. && beta1 < 1.) || !(beta2 >= 0. && beta2 < 1.) ||
+      !(eps >= 0.) || !(weight_decay >= 0.))
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_optim_step: bad arguments (kind %d)", kind);
+  if (!n->d_grad || !n->master_valid || n->dirty) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet_optim_step: no gradients (fdsr_nafnet_train_grads first)");
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  n->opt_step += 1;
+  OptArgs o{};
+  o.kind = kind; o.lr = (float)lr; o.b1 = (float)beta1; o.b2 = (float)beta2; o.eps = (float)eps; o.wd = (float)weight_decay;
+  o.omb1 = (float)(1.0 - beta1); o.omb2 = (float)(1.0 - beta2); o.decay = (float)(1.0 - lr * weight_decay);
+  const double bc1 = 1.0 - std::pow(beta1, (double)n->opt_step), bc2 = 1.0 - std::pow(beta2, (double)n->opt_step);
+  o.step_size = (float)(lr / bc1);
+  o.bc2_sqrt = (float)std::sqrt(bc2);
+  hipLaunchKernelGGL(naf_optim_kernel, dim3(TrainRun::nb(n->P)), dim3(256), 0, st, n->d_master, n->d_grad, n->d_m, n->d_v, o, n->P);
+  HIPCHK(nullptr, hipGetLastError());
+  hipLaunchKernelGGL(naf_repack_kernel, dim3(TrainRun::nb(n->arena_floats)), dim3(256), 0, st, n->d_arena, n->d_master, n->d_map, n->arena_floats);
+  HIPCHK(nullptr, hipGetLastError());
+  n->host_stale = true;
+  n->table_valid = false;
+  drop_graph(n);
+  return FDSR_OK;
+}
+
+int fdsr_nafnet_read_weight(fdsr_nafnet n, const char* key, float* dst, int dst_on_device, void* hip_stream) {
+  if (!dst) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_read_weight: null argument");
+  const int wi = find_weight(n, "fdsr_nafnet_read_weight", key);
+  if (wi < 0) return wi;
+  const WT& w = n->wts[wi];
+  if (!w.loaded) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet_read_weight: tensor '%s' is missing", key);
+  const size_t bytes = numel(w.shape) * sizeof(float);
+  if (!n->host_stale) {   // the host copy is current
+    if (dst_on_device) HIPCHK(nullptr, hipMemcpyAsync(dst, w.host.data(), bytes, hipMemcpyHostToDevice, reinterpret_cast<hipStream_t>(hip_stream)));
+    else memcpy(dst, w.host.data(), bytes);
+    if (dst_on_device) HIPCHK(nullptr, hipStreamSynchronize(reinterpret_cast<hipStream_t>(hip_stream)));
+    return FDSR_OK;
+  }
+  if (dst_on_device) {
+    HIPCHK(nullptr, hipMemcpyAsync(dst, n->d_master + n->poff[wi], bytes, hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(hip_stream)));
+  } else {
+    HIPCHK(nullptr, hipStreamSynchronize(reinterpret_cast<hipStream_t>(hip_stream)));
+    HIPCHK(nullptr, hipMemcpy(dst, n->d_master + n->poff[wi], bytes, hipMemcpyDeviceToHost));
+  }
+  return FDSR_OK;
+}
+
+int fdsr_nafnet_optim_get_state(fdsr_nafnet n, const char* key, float* exp_avg_host, float* exp_avg_sq_host, int64_t* step) {
+  const int wi = find_weight(n, "fdsr_nafnet_optim_get_state", key);
+  if (wi < 0) return wi;
+  if (!n->d_m) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet_optim_get_state: no optimizer state yet");
+  const size_t bytes = numel(n->wts[wi].shape) * sizeof(float);
+  HIPCHK(nullptr, hipDeviceSynchronize());
+  if (exp_avg_host) HIPCHK(nullptr, hipMemcpy(exp_avg_host, n->d_m + n->poff[wi], bytes, hipMemcpyDeviceToHost));
+  if (exp_avg_sq_host) HIPCHK(nullptr, hipMemcpy(exp_avg_sq_host, n->d_v + n->poff[wi], bytes, hipMemcpyDeviceToHost));
+  if (step) *step = n->opt_step;
+  return FDSR_OK;
+}
+
+int fdsr_nafnet_optim_set_state(fdsr_nafnet n, const char* key, const float* exp_avg_host, const float* exp_avg_sq_host, int64_t step) {
+  const int wi = find_weight(n, "fdsr_nafnet_optim_set_state", key);
+  if (wi < 0) return wi;
+  if (step < 0) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_optim_set_state: negative step");
+  for (const WT& w : n->wts)
+    if (!w.loaded) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet_optim_set_state: tensor '%s' is missing", w.key.c_str());
+  int rc = finalize(n);
+  if (rc) return rc;
+  if ((rc = ensure_train(n))) return rc;
+  const size_t bytes = numel(n->wts[wi].shape) * sizeof(float);
+  HIPCHK(nullptr, hipDeviceSynchronize());
+  if (exp_avg_host) HIPCHK(nullptr, hipMemcpy(n->d_m + n->poff[wi], exp_avg_host, bytes, hipMemcpyHostToDevice));
+  if (exp_avg_sq_host) HIPCHK(nullptr, hipMemcpy(n->d_v + n->poff[wi], exp_avg_sq_host, bytes, hipMemcpyHostToDevice));
+  n->opt_step = step;
+  return FDSR_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 """ConditionalNAFNet on the HIP engine (include/fdsr.h: fdsr_nafnet_*): an nn.Module that owns the reference's parameters
 under the reference's names -- `latest_G.pth` loads with load_state_dict(strict=True) -- and whose forward runs the device
-kernels.  Sampling only: there is no backward pass, and no PyTorch fallback."""
+kernels.  Training runs through train_grads / optim_step (denoising_model.DenoisingModel drives them); there is no
+torch-autograd bridge and no PyTorch fallback."""
 import ctypes as C
 
 import torch
@@ -130,7 +131,8 @@ class ConditionalNAFNet(nn.Module):
 
     def forward(self, inp, cond, time):
         if torch.is_grad_enabled() and any(p.requires_grad for _, p in self.named_reference_parameters()):
-            raise NotImplementedError('EDiffSR training is not implemented on this engine (sampling only)')
+            raise NotImplementedError('ConditionalNAFNet.forward has no torch-autograd bridge: train through '
+                                      'fastdiffsr_amd.ediffsr.DenoisingModel (or train_grads / optim_step)')
         x, cond = self._check_pair(inp, cond)
         b, _, h, w = x.shape
         self.sync_weights(x.device)
@@ -162,12 +164,98 @@ class ConditionalNAFNet(nn.Module):
         th, tw, tc = dims[0], dims[1], dims[2]
         return out[:b * th * tw * tc].view(b, th, tw, tc).permute(0, 3, 1, 2).contiguous()
 
-    def set_sde(self, thetas, sigmas, sigma_bars, dt, device):
+    def set_sde(self, thetas, sigmas, sigma_bars, dt, device, thetas_cumsum=None):
         T = thetas.numel() - 1
         arr = [a.detach().to('cpu', torch.float32).contiguous() for a in (thetas, sigmas, sigma_bars)]
         f = C.POINTER(C.c_float)
         with torch.cuda.device(device):
             _lib.check(None, _lib.load().fdsr_nafnet_set_sde(self._handle(), T, *[C.cast(a.data_ptr(), f) for a in arr], float(dt)))
+            if thetas_cumsum is not None:
+                cum = thetas_cumsum.detach().to('cpu', torch.float32).contiguous()
+                _lib.check(None, _lib.load().fdsr_nafnet_set_thetas_cumsum(self._handle(), T, C.cast(cum.data_ptr(), f)))
+
+    # ---- training ----
+    LOSSES = {'l1': 0, 'l2': 1}
+    OPTIMIZERS = {'Adam': 0, 'AdamW': 1, 'Lion': 2}
+
+    def train_grads(self, state, cond, gt, timesteps, loss_type='l1', weight=1.0, is_weighted=False):
+        """The loss of DenoisingModel.optimize_parameters and its gradients (kept in the engine: read_grad).  Returns a
+        device tensor [1 + B]: the loss, then every image's own mean."""
+        x, cond = self._check_pair(state, cond)
+        gt = gt.to(x.device).float().contiguous()
+        if gt.shape != x.shape:
+            raise ValueError('GT must have the state\'s shape')
+        if loss_type not in self.LOSSES:
+            raise ValueError('invalid loss type %s' % (loss_type,))
+        b, _, h, w = x.shape
+        self.sync_weights(x.device)
+        lib, hd = _lib.load(), self._handle()
+        with torch.cuda.device(x.device):
+            t = torch.as_tensor(timesteps).to(x.device).reshape(-1).to(torch.int32).contiguous()
+            if t.numel() != b:
+                raise ValueError('one timestep per image')
+            need = C.c_size_t()
+            _lib.check(None, lib.fdsr_nafnet_train_workspace_bytes(hd, b, h, w, C.byref(need)))
+            key = ('train', str(x.device))
+            ws = self._ws.get(key)
+            if ws is None or ws.numel() < need.value:
+                ws = self._ws[key] = torch.empty(need.value, dtype=torch.uint8, device=x.device)
+            out = torch.empty(1 + b, dtype=torch.float32, device=x.device)
+            st = torch.cuda.current_stream(x.device).cuda_stream
+            code = self.LOSSES[loss_type] | (_lib.FDSR_NAFNET_LOSS_WEIGHTED if is_weighted else 0)
+            _lib.check(None, lib.fdsr_nafnet_train_grads(hd, _ptr(x), _ptr(cond), _ptr(gt), _ptr(t), code, float(weight), _ptr(out), b, h, w,
+                                                         _ptr(ws), ws.numel(), C.c_void_p(st)))
+        return out
+
+    def train_workspace_bytes(self, b, h, w):
+        need = C.c_size_t()
+        _lib.check(None, _lib.load().fdsr_nafnet_train_workspace_bytes(self._handle(), b, h, w, C.byref(need)))
+        return need.value
+
+    def read_grad(self, key):
+        shape = self.schema[key]
+        out = torch.empty(shape, dtype=torch.float32)
+        _lib.check(None, _lib.load().fdsr_nafnet_read_grad(self._handle(), key.encode(), _ptr(out)))
+        return out
+
+    def grads(self):
+        return {k: self.read_grad(k) for k in self._names}
+
+    def grad_buffer(self):
+        """(device pointer, floats) of the flat gradient buffer."""
+        p, cnt = C.c_void_p(), C.c_size_t()
+        _lib.check(None, _lib.load().fdsr_nafnet_grad_buffer(self._handle(), C.byref(p), C.byref(cnt)))
+        return p.value, cnt.value
+
+    def optim_step(self, kind, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        """One optimizer step from the engine's gradients; afterwards the nn.Parameters hold the new values (device copies
+        into their storage, which leaves their versions -- the upload stamp -- as they were)."""
+        params = self.named_reference_parameters()
+        dev = params[0][1].device
+        lib, hd = _lib.load(), self._handle()
+        with torch.cuda.device(dev):
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _lib.check(None, lib.fdsr_nafnet_optim_step(hd, self.OPTIMIZERS[kind], float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                                        float(weight_decay), st))
+            for k, p in params:
+                if p.dtype != torch.float32 or not p.is_contiguous():
+                    raise TypeError('training needs contiguous fp32 parameters')
+                _lib.check(None, lib.fdsr_nafnet_read_weight(hd, k.encode(), _ptr(p), 1, st))
+        self._uploaded = (str(dev), tuple((p.data_ptr(), p._version) for _, p in params))
+
+    def optim_state(self, key):
+        shape = self.schema[key]
+        m, v, step = torch.empty(shape), torch.empty(shape), C.c_int64()
+        _lib.check(None, _lib.load().fdsr_nafnet_optim_get_state(self._handle(), key.encode(), _ptr(m), _ptr(v), C.byref(step)))
+        return m, v, step.value
+
+    def set_optim_state(self, key, exp_avg, exp_avg_sq, step):
+        dev = next(self.parameters()).device
+        self.sync_weights(dev)
+        m = None if exp_avg is None else exp_avg.detach().to('cpu', torch.float32).contiguous()
+        v = None if exp_avg_sq is None else exp_avg_sq.detach().to('cpu', torch.float32).contiguous()
+        with torch.cuda.device(dev):
+            _lib.check(None, _lib.load().fdsr_nafnet_optim_set_state(self._handle(), key.encode(), _ptr(m), _ptr(v), int(step)))
 
     def sample(self, state, cond, noise=None, seed=0, first_image=0, graph=False, ode=False, trajectory=False):
         """IRSDE.reverse_sde / reverse_ode in one engine call (set_sde first).  noise [T,B,3,H,W] or None (engine draws)."""
@@ -178,8 +266,8 @@ class ConditionalNAFNet(nn.Module):
         with torch.cuda.device(x.device):
             if noise is not None:
                 noise = noise.to(x.device, torch.float32).contiguous()
-                if noise.dim() != 5 or tuple(noise.shape[1:]) != tuple(x.shape):
-                    raise ValueError('noise must be [T,B,3,H,W]')
+                if noise.dim() != 5 or tuple(noise.shape[1:]) != tuple(x.shape) or noise.shape[0] != self._T():
+                    raise ValueError('noise must be [T,B,3,H,W] with the schedule\'s T')
             out = torch.empty_like(x)
             traj = torch.empty((self._T(),) + tuple(x.shape), dtype=torch.float32, device=x.device) if trajectory else None
             ws = self.workspace(b, h, w, x.device)

@@ -1,4 +1,4 @@
-"""IRSDE (EDiffSR/codes/utils/sde_utils.py) as far as sampling needs it.  The tables are built with the reference's own
+"""IRSDE (EDiffSR/codes/utils/sde_utils.py) as far as sampling and training need it.  The tables are built with the reference's own
 fp32 torch operations, so they equal the reference's bit for bit.  With this package's ConditionalNAFNet as the model,
 reverse_sde / reverse_ode are one engine call; with any other callable they run the reference's Python loop."""
 import math
@@ -55,7 +55,7 @@ class IRSDE:
         self.model = model
         if isinstance(model, ConditionalNAFNet):
             dev = self.device if self.device is not None and torch.device(self.device).type == 'cuda' else torch.device('cuda', torch.cuda.current_device())
-            model.set_sde(self.thetas, self.sigmas, self.sigma_bars, float(self.dt), dev)
+            model.set_sde(self.thetas, self.sigmas, self.sigma_bars, float(self.dt), dev, thetas_cumsum=self.thetas_cumsum)
             model._sde_T = self.T
 
     def mu_bar(self, x0, t):
@@ -117,5 +117,33 @@ class IRSDE:
             x = x - self.ode_reverse_drift(x, score, t)
         return x
 
+    def get_score_from_noise(self, noise, t):
+        return -noise / self.sigma_bar(t)
+
+    def reverse_sde_step_mean(self, x, score, t):
+        return x - self.sde_reverse_drift(x, score, t)
+
+    def reverse_optimum_step(self, xt, x0, t):
+        A = torch.exp(-self.thetas[t] * self.dt)
+        B = torch.exp(-self.thetas_cumsum[t] * self.dt)
+        C = torch.exp(-self.thetas_cumsum[t - 1] * self.dt)
+        term1 = A * (1 - C ** 2) / (1 - B ** 2)
+        term2 = C * (1 - A ** 2) / (1 - B ** 2)
+        return term1 * (xt - self.mu) + term2 * (x0 - self.mu) + self.mu
+
     def generate_random_states(self, x0, mu):
-        raise NotImplementedError('EDiffSR training is not implemented on this engine (sampling only)')
+        """The training states: timesteps by randint, then the noise by randn_like, in the reference's order.  As in the
+        reference's train.py, the model is set first (set_model): an IRSDE without one has nothing to train and refuses."""
+        if self.model is None:
+            raise NotImplementedError('IRSDE.generate_random_states: no model is set (set_model); EDiffSR trains through '
+                                      'fastdiffsr_amd.ediffsr.DenoisingModel')
+        x0 = x0.to(self.device)
+        mu = mu.to(self.device)
+        self.set_mu(mu)
+        batch = x0.shape[0]
+        timesteps = torch.randint(1, self.T + 1, (batch, 1, 1, 1)).long()
+        state_mean = self.mu_bar(x0, timesteps)
+        noises = torch.randn_like(state_mean)
+        noise_level = self.sigma_bar(timesteps)
+        noisy_states = noises * noise_level + state_mean
+        return timesteps, noisy_states.to(torch.float32)

@@ -367,6 +367,49 @@ int fdsr_upscale_bicubic_f32(const float* src_nchw, float* dst_nchw, int batch, 
                              void* hip_stream);
 void fdsr_nafnet_destroy(fdsr_nafnet n);
 
+/* EDiffSR training: one step of DenoisingModel.optimize_parameters (models/denoising_model.py) on the device, fp32.
+ *   fdsr_nafnet_set_thetas_cumsum   IRSDE.thetas_cumsum [T+1] host fp32, after fdsr_nafnet_set_sde (which forgets it).
+ *   fdsr_nafnet_train_grads   eps = model(state, cond, t);  score = -eps / sigma_bar[t]
+ *                               xt_1_expection = state - (theta[t] (cond - state) - sigma[t]^2 score) dt        (reverse_sde_step_mean)
+ *                               xt_1_optimum   = reverse_optimum_step(state, gt, t)
+ *                               loss = weight * mean_b mean_chw |.| (l1) or (.)^2 (l2)                           (MatchingLoss)
+ *                             and the gradient of loss with respect to every weight, into the object's flat gradient buffer.
+ *                             timesteps_dev: int32 [B] in 1..T.  loss_out_dev [1 + B]: the loss, then every image's own mean.
+ *                             loss_type: FDSR_NAFNET_LOSS_L1 / _L2; with FDSR_NAFNET_LOSS_WEIGHTED or'ed in: FDSR_E_INVALID
+ *                             (is_weighted; the reference's driver passes no weights).  The workspace is the training one
+ *                             (fdsr_nafnet_train_workspace_bytes); a forward / sample workspace is not touched.
+ *                             Every sum has one order: two calls on the same inputs give the same bits.
+ *   fdsr_nafnet_grad_buffer   the flat gradient: device pointer and length in floats; tensors in fdsr_nafnet_weight_info order,
+ *                             each in the reference's own layout (what an all-reduce would be applied to).
+ *   fdsr_nafnet_read_grad     one tensor of it to the host (synchronises).
+ *   fdsr_nafnet_optim_step    kind FDSR_NAFNET_ADAM (torch.optim.Adam, weight_decay as an L2 term), _ADAMW (decoupled), _LION
+ *                             (models/optimizer.py; eps unused) over the flat master copy -- hyperparameters as doubles, every
+ *                             derived scalar (1 - beta, 1 - lr wd, lr / bias_correction1) formed in double and rounded once -- then a device-side re-pack of every
+ *                             form the kernels read.  Drops the sampler's time-row table and graph.  No host round trip.
+ *   fdsr_nafnet_read_weight   the current value of one tensor, to host memory or (dst_on_device) stream-ordered to device memory.
+ *   fdsr_nafnet_optim_get_state / _set_state   exp_avg, exp_avg_sq (either may be NULL) and the step count, per key; the step
+ *                             count is one number for the whole object.
+ * FDSR_E_STATE: weights, fdsr_nafnet_set_sde or fdsr_nafnet_set_thetas_cumsum missing; fdsr_nafnet_optim_step without gradients. */
+#define FDSR_NAFNET_LOSS_L1 0
+#define FDSR_NAFNET_LOSS_L2 1
+#define FDSR_NAFNET_LOSS_WEIGHTED 256
+#define FDSR_NAFNET_ADAM 0
+#define FDSR_NAFNET_ADAMW 1
+#define FDSR_NAFNET_LION 2
+int fdsr_nafnet_set_thetas_cumsum(fdsr_nafnet n, int T, const float* thetas_cumsum);
+int fdsr_nafnet_train_workspace_bytes(fdsr_nafnet n, int batch, int height, int width, size_t* bytes);
+int fdsr_nafnet_train_grads(fdsr_nafnet n, const float* state_nchw, const float* cond_nchw, const float* gt_nchw,
+                            const int32_t* timesteps_dev, int loss_type, float weight, float* loss_out_dev, int batch, int height,
+                            int width, void* workspace, size_t workspace_bytes, void* hip_stream);
+int fdsr_nafnet_grad_buffer(fdsr_nafnet n, float** device_ptr, size_t* count);
+int fdsr_nafnet_read_grad(fdsr_nafnet n, const char* key, float* host_f32);
+int fdsr_nafnet_optim_step(fdsr_nafnet n, int kind, double lr, double beta1, double beta2, double eps, double weight_decay,
+                           void* hip_stream);
+int fdsr_nafnet_read_weight(fdsr_nafnet n, const char* key, float* dst, int dst_on_device, void* hip_stream);
+int fdsr_nafnet_optim_get_state(fdsr_nafnet n, const char* key, float* exp_avg_host, float* exp_avg_sq_host, int64_t* step);
+int fdsr_nafnet_optim_set_state(fdsr_nafnet n, const char* key, const float* exp_avg_host, const float* exp_avg_sq_host,
+                                int64_t step);
+
 /* -- input-pipeline helper------------------------------------ */
 /* The dataset's tensor transform on the device (data/util.py:66-75 transform_augment: ToTensor() = uint8 / 255 as fp32,
  * HWC -> CHW, then img * (hi - lo) + lo; LRHR_dataset.py:113-119 passes min_max = (-1, 1)): the loader threads hand over

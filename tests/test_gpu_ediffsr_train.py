@@ -1,0 +1,272 @@
+"""EDiffSR training on the device against fp64 autograd over tests/ediffsr_train_restatement.py, computed here.  Every measured
+value is printed before it is judged.
+
+Gradients, per tensor k, as tests/test_gpu_sr3_train.py: with typ = the median over tensors of max|g64|, a tensor with
+max|g64_k| >= 1e-5 typ must have max|g_dev - g64| <= 1e-4 max|g64_k|, a smaller one max|g_dev - g64| <= 1e-4 typ.
+Loss: |loss_dev - loss64| <= 4 |loss32 - loss64|, no tighter than 2^-22 relative."""
+import numpy as np
+import pytest
+import torch
+
+import ediffsr_restatement as R
+import ediffsr_train_restatement as TR
+
+pytestmark = pytest.mark.gpu
+
+TEST_SETTING = dict(width=16, enc_blk_nums=[2, 1, 1, 1], middle_blk_num=1, dec_blk_nums=[1, 1, 1, 1])
+SHIPPED_SETTING = dict(width=64, enc_blk_nums=[14, 1, 1, 1], middle_blk_num=1, dec_blk_nums=[1, 1, 1, 1])
+DEV = 'cuda'
+SDE = dict(max_sigma=50, T=100, schedule='cosine', eps=0.005)
+
+
+def _model(setting, seed=0):
+    from fastdiffsr_amd.ediffsr import ConditionalNAFNet, IRSDE
+    from fastdiffsr_amd.synth import synth_nafnet
+    sd = {k: torch.from_numpy(v) for k, v in synth_nafnet(seed, **setting).items()}
+    m = ConditionalNAFNet(**setting)
+    m.load_state_dict(sd, strict=True)
+    m = m.to(DEV).eval()
+    sde = IRSDE(device='cpu', **SDE)
+    sde.set_model(m)
+    return m, sd, sde
+
+
+def _batch(seed, b, h, w, t, sde):
+    """GT, the upscaled-LQ stand-in mu, and the noisy state of generate_random_states at the given timesteps."""
+    g = torch.Generator().manual_seed(seed)
+    gt = torch.rand(b, 3, h, w, generator=g)
+    mu = (gt + 0.1 * torch.randn(b, 3, h, w, generator=g)).clamp(0, 1)
+    ts = torch.tensor(t).reshape(b, 1, 1, 1).long()
+    sde.set_mu(mu)
+    state = torch.randn(b, 3, h, w, generator=g) * sde.sigma_bar(ts) + sde.mu_bar(gt, ts)
+    return gt, mu, state.float(), ts
+
+
+def _reference(sd, sde, gt, mu, state, ts, loss_type, weight=1.0):
+    l32, g32 = TR.loss_and_grads(sd, TR.cast_tables(sde, torch.float32), state, mu, gt, ts, loss_type, weight)
+    l64, g64 = TR.loss_and_grads(R.cast_sd(sd, torch.float64), TR.cast_tables(sde, torch.float64), state.double(), mu.double(), gt.double(),
+                                 ts, loss_type, weight)
+    return float(l32), float(l64), g64
+
+
+def _judge_grads(gdev, g64):
+    mx = {k: float(v.abs().max()) for k, v in g64.items()}
+    typ = float(np.median(list(mx.values())))
+    fails, zero = [], 0
+    for k, ref in g64.items():
+        d = float((gdev[k].double() - ref).abs().max())
+        big = mx[k] >= 1e-5 * typ
+        bound = 1e-4 * (mx[k] if big else typ)
+        zero += mx[k] == 0
+        ok = d <= bound
+        print('%-44s max|g64| %.3e  max|dev - g64| %.3e  bound %.3e  %s%s' % (k, mx[k], d, bound, 'rel' if big else 'abs', '' if ok else '  FAIL'))
+        if not ok:
+            fails.append(k)
+    print('typ %.3e, %d tensors, %d with an exactly zero gradient' % (typ, len(g64), zero))
+    return fails
+
+
+def _judge_loss(name, ldev, l32, l64):
+    bound = max(4 * abs(l32 - l64), 2.0 ** -22 * abs(l64))
+    print('%s: loss dev %.9g  f32 %.9g  f64 %.12g  |dev - f64| %.3e  bound %.3e' % (name, ldev, l32, l64, abs(ldev - l64), bound))
+    return abs(ldev - l64) <= bound
+
+
+CASES = {
+    'a': (TEST_SETTING, 2, 36, 44, [1, 100], 'l1'),
+    'b': (TEST_SETTING, 3, 32, 32, [7, 50, 93], 'l2'),
+    'c': (TEST_SETTING, 2, 64, 64, [23, 71], 'l1'),
+    'd': (SHIPPED_SETTING, 2, 32, 32, [12, 88], 'l1'),
+}
+
+
+@pytest.mark.parametrize('case', list(CASES))
+def test_gradients(case):
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    setting, b, h, w, t, loss_type = CASES[case]
+    m, sd, sde = _model(setting)
+    gt, mu, state, ts = _batch(31, b, h, w, t, sde)
+    l32, l64, g64 = _reference(sd, sde, gt, mu, state, ts, loss_type)
+    out = m.train_grads(state.to(DEV), mu.to(DEV), gt.to(DEV), ts, loss_type=loss_type).cpu()
+    gdev = m.grads()
+    assert len(gdev) == len(g64)
+    ok_loss = _judge_loss('case ' + case, float(out[0]), l32, l64)
+    fails = _judge_grads(gdev, g64)
+    assert not fails, fails
+    assert ok_loss
+
+
+@pytest.fixture(scope='module')
+def small():
+    torch.set_num_threads(min(16, torch.get_num_threads()))
+    return _model(TEST_SETTING)
+
+
+def test_two_calls_are_bitwise_equal_and_inference_is_undisturbed(small):
+    m, sd, sde = small
+    gt, mu, state, ts = _batch(32, 2, 36, 44, [3, 64], sde)
+    x, c, g = state.to(DEV), mu.to(DEV), gt.to(DEV)
+    before = m(x, c, 37)
+    l1 = m.train_grads(x, c, g, ts).cpu()
+    g1 = m.grads()
+    after = m(x, c, 37)
+    l2 = m.train_grads(x, c, g, ts).cpu()
+    g2 = m.grads()
+    assert torch.equal(before, after)
+    assert torch.equal(l1, l2)
+    assert all(torch.equal(g1[k], g2[k]) for k in g1)
+    with pytest.raises(Exception, match='is_weighted'):
+        m.train_grads(x, c, g, ts, is_weighted=True)
+
+
+def test_sample_after_a_step_equals_a_fresh_model():
+    """The re-pack, the time-row table and the graph are rebuilt after a step (a 4-step schedule keeps the sampler short)."""
+    from fastdiffsr_amd.ediffsr import ConditionalNAFNet, IRSDE
+    from fastdiffsr_amd.synth import synth_nafnet
+    sd = {k: torch.from_numpy(v) for k, v in synth_nafnet(0, **TEST_SETTING).items()}
+    m = ConditionalNAFNet(**TEST_SETTING)
+    m.load_state_dict(sd, strict=True)
+    m = m.to(DEV).eval()
+    short = IRSDE(max_sigma=50, T=4, schedule='cosine', eps=0.005, device='cpu')
+    short.set_model(m)
+    gt, mu, state, ts = _batch(33, 2, 32, 32, [1, 4], short)
+    x, c, g = state.to(DEV), mu.to(DEV), gt.to(DEV)
+    noise = torch.randn(4, 2, 3, 32, 32, generator=torch.Generator().manual_seed(5)).to(DEV)
+    first = m.sample(x, c, noise=noise, graph=True)        # builds the time-row table and the step graph of the old weights
+    m.train_grads(x, c, g, ts)
+    m.optim_step('AdamW', 1e-3, (0.9, 0.99), 1e-8, 0.01)
+    stepped = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
+    assert any(not torch.equal(stepped[k], sd[k]) for k in sd)
+    got = m.sample(x, c, noise=noise, graph=True)
+    fresh = ConditionalNAFNet(**TEST_SETTING)
+    fresh.load_state_dict(stepped, strict=True)
+    fresh = fresh.to(DEV).eval()
+    short.set_model(fresh)
+    want = fresh.sample(x, c, noise=noise)
+    assert torch.equal(got, want)
+    assert not torch.equal(first, got)
+
+
+OPT = [('Adam', 0.0), ('Adam', 0.01), ('AdamW', 0.0), ('AdamW', 0.01), ('Lion', 0.01)]
+
+
+def _torch_optim(kind, p, lr, betas, eps, wd):
+    cls = {'Adam': torch.optim.Adam, 'AdamW': torch.optim.AdamW}[kind]
+    return cls([p], lr=lr, betas=betas, eps=eps, weight_decay=wd, foreach=False)
+
+
+@pytest.mark.parametrize('kind,wd', OPT)
+def test_optimizers(kind, wd):
+    m, sd, sde = _model(TEST_SETTING)
+    lr, betas, eps = 1e-3, (0.9, 0.99), 1e-8
+    st32 = {k: {} for k in sd}
+    st64 = {k: {} for k in sd}
+    w32 = {k: v.clone() for k, v in sd.items()}
+    topt = None if kind == 'Lion' else {k: _torch_optim(kind, torch.nn.Parameter(v.clone()), lr, betas, eps, wd) for k, v in sd.items()}
+    fails = []
+    for step in range(2):
+        gt, mu, state, ts = _batch(40 + step, 2, 32, 32, [9 + step, 77], sde)
+        m.train_grads(state.to(DEV), mu.to(DEV), gt.to(DEV), ts)
+        g = m.grads()
+        wprev = {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}
+        m.optim_step(kind, lr, betas, eps, wd)
+        wdev = {k: v.detach().cpu() for k, v in m.state_dict().items()}
+        worst = 0.0
+        for k in sd:
+            # the yardstick: the same update in fp64 from the device's own fp32 gradient and previous weight; its state runs in fp64
+            if step == 1:
+                mm, vv, cnt = m.optim_state(k)
+            y64 = TR.optim_step(kind, wprev[k].double(), g[k].double(), st64[k], lr, betas[0], betas[1], eps, wd)
+            if kind == 'Lion':
+                y32 = TR.optim_step(kind, wprev[k], g[k], st32[k], lr, betas[0], betas[1], eps, wd)
+            else:
+                p = topt[k].param_groups[0]['params'][0]
+                with torch.no_grad():
+                    p.copy_(wprev[k])
+                p.grad = g[k].clone()
+                topt[k].step()
+                y32 = p.detach().clone()
+            ulp = torch.abs(torch.nextafter(wprev[k].abs(), torch.tensor(float('inf'))) - wprev[k].abs()).double()
+            bound = torch.maximum(4 * (y32.double() - y64).abs().max() * torch.ones_like(ulp), ulp)
+            d = (wdev[k].double() - y64).abs()
+            ratio = float((d / bound).max())
+            worst = max(worst, ratio)
+            if ratio > 1:
+                fails.append((step, k, ratio))
+        print('%s wd %g step %d: worst |dev - f64| / bound %.3g' % (kind, wd, step + 1, worst))
+    assert not fails, fails[:8]
+    mm, vv, cnt = m.optim_state('intro.weight')
+    assert cnt == 2
+    m.set_optim_state('intro.weight', mm, vv, 7)
+    m2, v2, c2 = m.optim_state('intro.weight')
+    assert torch.equal(mm, m2) and torch.equal(vv, v2) and c2 == 7
+
+
+def test_short_trajectory(small):
+    m, sd, sde = _model(TEST_SETTING)
+    lr, betas, eps, wd = 4e-5, (0.9, 0.99), 1e-8, 0.0
+    t32, t64 = TR.cast_tables(sde, torch.float32), TR.cast_tables(sde, torch.float64)
+    w32 = {k: v.clone() for k, v in sd.items()}
+    w64 = R.cast_sd(sd, torch.float64)
+    s32, s64 = {k: {} for k in sd}, {k: {} for k in sd}
+    fails = []
+    for step in range(5):
+        gt, mu, state, ts = _batch(50 + step, 2, 32, 32, [5 + 17 * step, 96 - 11 * step], sde)
+        ldev = float(m.train_grads(state.to(DEV), mu.to(DEV), gt.to(DEV), ts)[0])
+        m.optim_step('AdamW', lr, betas, eps, wd)
+        l32, g32 = TR.loss_and_grads(w32, t32, state, mu, gt, ts)
+        l64, g64 = TR.loss_and_grads(w64, t64, state.double(), mu.double(), gt.double(), ts)
+        w32 = {k: TR.optim_step('AdamW', w32[k], g32[k], s32[k], lr, *betas, eps, wd) for k in w32}
+        w64 = {k: TR.optim_step('AdamW', w64[k], g64[k], s64[k], lr, *betas, eps, wd) for k in w64}
+        l32, l64 = float(l32), float(l64)
+        bound = max(4 * abs(l32 - l64), 1e-5 * abs(l64))
+        print('step %d: loss dev %.9g  f32 %.9g  f64 %.12g  |f32 - f64| %.3e  |dev - f64| %.3e  bound %.3e' % (
+            step + 1, ldev, l32, l64, abs(l32 - l64), abs(ldev - l64), bound))
+        if not abs(ldev - l64) <= bound:
+            fails.append(step + 1)
+    assert not fails, fails
+
+
+def test_cli_end_to_end(tmp_path):
+    """python -m fastdiffsr_amd.ediffsr.train on eight synthetic 8^2 -> 32^2 pairs: six steps, a val pass, a checkpoint, a resume."""
+    import math
+    import yaml
+    from PIL import Image
+    from fastdiffsr_amd.ediffsr import ConditionalNAFNet, train
+    from fastdiffsr_amd.synth import synth_nafnet
+    rng = np.random.RandomState(7)
+    for d in ('hr', 'lr'):
+        (tmp_path / d).mkdir()
+    for i in range(8):
+        hr = rng.randint(0, 256, (32, 32, 3)).astype(np.uint8)
+        Image.fromarray(hr).save(tmp_path / 'hr' / ('%d.png' % i))
+        Image.fromarray(hr.reshape(8, 4, 8, 4, 3).mean(axis=(1, 3)).astype(np.uint8)).save(tmp_path / 'lr' / ('%d.png' % i))
+    sd = {k: torch.from_numpy(v) for k, v in synth_nafnet(0, **TEST_SETTING).items()}
+    torch.save(sd, tmp_path / 'init_G.pth')
+    ds = dict(dataroot_GT=str(tmp_path / 'hr'), dataroot_LQ=str(tmp_path / 'lr'))
+    opt = dict(name='cli', sde=dict(max_sigma=50, T=4, schedule='cosine', eps=0.005), degradation=dict(scale=4),
+               datasets=dict(train=dict(ds, name='t', batch_size=2, GT_size=32, use_flip=True, use_rot=True), val=dict(ds, name='v')),
+               network_G=dict(which_model_G='ConditionalNAFNet', setting=TEST_SETTING),
+               path=dict(pretrain_model_G=str(tmp_path / 'init_G.pth'), strict_load=True, resume_state=None),
+               train=dict(optimizer='AdamW', lr_G=4e-5, lr_scheme='TrueCosineAnnealingLR', beta1=0.9, beta2=0.99, niter=6, warmup_iter=-1,
+                          eta_min=1e-7, is_weighted=False, loss_type='l1', weight=1.0, manual_seed=0, val_freq=3),
+               logger=dict(print_freq=1, save_checkpoint_freq=6))
+    (tmp_path / 'opt.yml').write_text(yaml.safe_dump(opt))
+    root = tmp_path / 'exp'
+    res = train.main(['-opt', str(tmp_path / 'opt.yml'), '--root', str(root)])
+    print(res)
+    assert res['iter'] == 6 and len(res['losses']) == 6 and all(math.isfinite(v) for v in res['losses'])
+    for k, lr in enumerate(res['lrs']):
+        assert math.isclose(lr, 1e-7 + (4e-5 - 1e-7) * (1 + math.cos(math.pi * k / 6)) / 2, rel_tol=1e-9), (k, lr)
+    assert [s for s, _ in res['psnr']] == [3, 6] and all(math.isfinite(p) for _, p in res['psnr'])
+    fresh = ConditionalNAFNet(**TEST_SETTING)
+    saved = torch.load(root / 'models' / '6_G.pth', map_location='cpu', weights_only=True)
+    fresh.load_state_dict(saved, strict=True)
+    assert any(not torch.equal(saved[k], sd[k]) for k in sd)
+    opt['path']['resume_state'] = str(root / 'training_state' / '6.state')
+    opt['train']['niter'] = 8
+    (tmp_path / 'opt2.yml').write_text(yaml.safe_dump(opt))
+    res2 = train.main(['-opt', str(tmp_path / 'opt2.yml'), '--root', str(root)])
+    print(res2)
+    assert res2['iter'] == 8 and len(res2['losses']) == 2 and res2['opt_step'] == 8
+    assert all(math.isfinite(v) for v in res2['losses'])
