@@ -1,5 +1,5 @@
-// Internal types of the engine shared by fdsr_engine.cpp (plan, forward, sampling, C ABI) and
-// fdsr_train.cpp (backward pass, Adam).  Not part of the C ABI (include/fdsr.h).
+// Internal types of the engine shared by fdsr_plan.cpp (the static plan: ops, tensors, weight schema), fdsr_engine.cpp
+// (workspace planning, forward, sampling, C ABI) and fdsr_train.cpp (backward pass, Adam).  Not part of the C ABI (include/fdsr.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -212,6 +212,8 @@ int fail(fdsr_handle h, int code, const char* fmt, ...);
       return fail(h, FDSR_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
   } while (0)
 
+// fdsr_plan.cpp
+int build_plan(fdsr_handle h);   // ops, tensors and weight schema from h->cfg (fdsr_create)
 // fdsr_engine.cpp
 int get_plan(fdsr_handle h, int N, int H, int W);
 int check_ready(fdsr_handle h, bool need_schedule);

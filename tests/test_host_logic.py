@@ -50,7 +50,7 @@ def test_sampling_scalars_match_reference_formation():
                                 dict(in_channel=6, out_channel=3, inner_channel=64, channel_mults=(1, 2, 4, 8, 8), res_blocks=1),
                                 dict(in_channel=3, out_channel=3, inner_channel=32, channel_mults=(1, 2), res_blocks=3)])
 def test_native_plan_schema_matches_python_schema(kw):
-    """csrc/fdsr_engine.cpp derives the same checkpoint schema as arch.param_schema (C ABI, no GPU)."""
+    """csrc/fdsr_plan.cpp (build_plan, called by fdsr_create) derives the same checkpoint schema as arch.param_schema (C ABI, no GPU)."""
     cfg = UNetConfig(**kw)
     eng = Engine(cfg)
     py = param_schema(cfg)
@@ -59,6 +59,27 @@ def test_native_plan_schema_matches_python_schema(kw):
     assert all(tuple(py[k]) == s for k, s, _ in native)
     assert sorted(k for k, _, live in native if not live) == sorted(dead_keys(cfg))
     assert not eng.weights_complete
+
+
+def test_plan_fingerprints_are_the_parents(golden_dir):
+    """The static plan of csrc/fdsr_plan.cpp, seen through the C ABI, is the one tests/golden/plan_fingerprints.json recorded from
+    the library of the commit before the plan builders moved there (tools/make_plan_fingerprints.py): per config the sha256 of the
+    (key, shape, live) schema, workspace_bytes at three shapes plain and in debug mode, train_workspace_bytes at two (it plans
+    without a device, so it is part of the record; training mode on where the config has dropout).  These follow tensor count and
+    order, widths, levels, liveness, need_part and the GroupNorm / dropout slot counts; a swapped gamma / beta index is for the
+    GPU suite to see."""
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location(
+        'make_plan_fingerprints', os.path.join(os.path.dirname(__file__), '..', 'tools', 'make_plan_fingerprints.py'))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    doc = json.load(open(os.path.join(golden_dir, 'plan_fingerprints.json')))
+    assert [tuple(s) for s in doc['shapes']] == tool.SHAPES
+    now = {name: {k: list(v) if isinstance(v, tuple) else v for k, v in kw.items()} for name, kw in tool.configs().items()}
+    assert {name: rec['config'] for name, rec in doc['configs'].items()} == now       # the file covers the tool's configs, as they are
+    for name, rec in doc['configs'].items():
+        assert tool.fingerprint(rec['config']) == rec['fingerprint'], name
 
 
 def test_fastdiffsr_counts():
