@@ -138,6 +138,8 @@ SYMBOLS = {
     'fdsr_nafnet_optim_get_state': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     'fdsr_nafnet_optim_set_state': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64]),
     'fdsr_nafnet_destroy': (None, [C.c_void_p]),
+    'fdsr_nafnet_set_precision': (C.c_int, [C.c_void_p, C.c_int]),
+    'fdsr_nafnet_check_saturation': (C.c_int, [C.c_void_p, C.c_void_p]),
     'fdsr_set_debug': (C.c_int, [C.c_void_p, C.c_int]),
     'fdsr_debug_option': (C.c_int, [C.c_char_p, C.c_longlong]),
     'fdsr_check_saturation': (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -54,6 +54,10 @@ struct GemmArgs {
   const float* res;    // EPI_RES: out = res + v evec[co];  EPI_PSHUF: out = v + res (the encoder skip)
   const float* evec;
   int N, Hin, Win, Cin, Hout, Wout, Cout, KW, S, P, K, Kpad, CoutPad, ostride, pstride, epi;
+  // FDSR_PREC_F16X3 (naf_gemm_h3_kernel): the split weight fragments, 2^-e of their scale, the sticky range flag
+  const uint4* wq;
+  float winv;
+  int* sat;
 };
 
 // One workgroup: BM output pixels x BN packed output columns; 4 waves, each 32 pixels x 64 columns (two 32x32 accumulators, so the
@@ -214,6 +218,8 @@ __global__ void __launch_bounds__(NT) naf_gemm_kernel(GemmArgs p) {
     }
   }
 }
+
+#include "fdsr_nafnet_h3.h"
 
 // LayerNorm statistics: (mean, 1 / sqrt(var + eps)) per pixel over C channels, biased variance, two passes.  16 lanes per pixel,
 // a butterfly of commutative adds: every lane ends with the same bits.
@@ -565,6 +571,11 @@ struct GemmL {
   int cin = 0, cout = 0, ks = 1, s = 1, p = 0;
   bool gate = false;
   size_t woff = 0, boff = 0;   // float offsets into the device arena
+  bool split = false;          // f16x3: has a split form (the forward GEMMs; build_schema)
+  size_t hoff = 0;             //        its first 16-byte fragment
+  float hinv = 1.f;            //        2^-e of the split form's scale (split_weights)
+  int K32() const { return round_up(K(), HK); }
+  size_t hfrags() const { return (size_t)(CoutPad() / BN) * (K32() / HK) * 8 * 64; }
   int K() const { return ks * ks * cin; }
   int Kpad() const { return round_up(K(), BK); }
   int CoutPad() const { return gate ? 2 * round_up(cout / 2, 32) : round_up(cout, BN); }
@@ -605,6 +616,11 @@ struct fdsr_nafnet_obj {
   size_t arena_floats = 0;
   float* d_arena = nullptr;
   bool dirty = true;
+  // FDSR_PREC_F16X3: hi / lo planes of the forward GEMMs' weights (built by finalize in that mode) and the range flag
+  int prec = FDSR_PREC_F32;
+  size_t hfrags = 0;
+  uint4* d_wq = nullptr;
+  int *d_sat = nullptr, *h_sat = nullptr;
   // training (fdsr_nafnet_train.h): flat fp32 buffers in the reference's layout, tensors in state_dict order
   float *d_master = nullptr, *d_grad = nullptr, *d_m = nullptr, *d_v = nullptr, *d_cum = nullptr;
   int *d_map = nullptr, *d_rowmap = nullptr;
@@ -759,6 +775,7 @@ void build_schema(fdsr_nafnet n) {
   n->off_zero = take(off, zmax);
   for (GemmL& t : n->tgemms) t.boff = n->off_zero;
   n->arena_floats = off;
+  for (GemmL& g : n->gemms) { g.split = true; g.hoff = n->hfrags; n->hfrags += g.hfrags(); }
   size_t po = 0;
   for (const WT& wt : n->wts) { n->poff.push_back(po); po += numel(wt.shape); }
   n->P = po;
@@ -843,6 +860,40 @@ void pack_forms(fdsr_nafnet n, S& s) {
   }
 }
 
+// FDSR_PREC_F16X3: the forward GEMMs' packed weights (arena `a`, as pack_forms wrote them) as hi = f16(w s), lo = f16(w s - hi) in
+// the B-fragment order naf_gemm_h3_kernel loads.  s = 2^e <= 2^12 with max|w s| <= 2^15, the rule of the UNets' pack_weights_h: it
+// keeps lo out of the f16 subnormal range for all but tiny weights, and the kernel multiplies the accumulator by 2^-e.
+std::vector<uint16_t> split_weights(fdsr_nafnet n, const std::vector<float>& a) {
+  std::vector<uint16_t> q(n->hfrags * 8, 0);
+  auto bits = [](_Float16 v) { uint16_t b; memcpy(&b, &v, 2); return b; };
+  for (GemmL& g : n->gemms) {
+    const int Cp = g.CoutPad(), Kp = g.Kpad(), nk = g.K32() / HK;
+    const float* w = a.data() + g.woff;
+    float amax = 0.f;
+    for (size_t i = 0; i < (size_t)Kp * Cp; ++i) amax = std::max(amax, std::min(std::fabs(w[i]), F16_MAX));
+    int e = 12;
+    if (amax > 0.f) e = std::min(12, (int)std::floor(std::log2(32768.0 / (double)amax)));
+    const float scale = std::ldexp(1.0f, e);
+    g.hinv = std::ldexp(1.0f, -e);
+    for (int cot = 0; cot < Cp / BN; ++cot)
+      for (int kc = 0; kc < nk; ++kc)
+        for (int nb = 0; nb < 2; ++nb)
+          for (int s = 0; s < 2; ++s)
+            for (int l = 0; l < 64; ++l) {
+              const size_t f = g.hoff + ((((size_t)cot * nk + kc) * 2 + nb) * 2 + s) * 2 * 64 + l;
+              const int col = cot * BN + nb * 32 + (l & 31);
+              for (int j = 0; j < 8; ++j) {
+                const int k = kc * HK + 16 * s + 8 * (l >> 5) + j;
+                const float v = k < Kp ? std::min(std::max(w[(size_t)k * Cp + col], -F16_MAX), F16_MAX) * scale : 0.f;
+                const _Float16 hi = (_Float16)v;
+                q[f * 8 + j] = bits(hi);
+                q[(f + 64) * 8 + j] = bits((_Float16)(v - (float)hi));
+              }
+            }
+  }
+  return q;
+}
+
 // every device form from the host copies, one upload
 int finalize(fdsr_nafnet n) {
   if (!n->dirty) return FDSR_OK;
@@ -854,6 +905,15 @@ int finalize(fdsr_nafnet n) {
   if (!n->d_arena) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_arena), a.size() * sizeof(float)));
   HIPCHK(nullptr, hipDeviceSynchronize());   // nothing in flight reads the old forms
   HIPCHK(nullptr, hipMemcpy(n->d_arena, a.data(), a.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (n->prec == FDSR_PREC_F16X3) {
+    const std::vector<uint16_t> q = split_weights(n, a);
+    if (!n->d_wq) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_wq), q.size() * sizeof(uint16_t)));
+    HIPCHK(nullptr, hipMemcpy(n->d_wq, q.data(), q.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    if (!n->d_sat) {
+      HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_sat), 256));
+      HIPCHK(nullptr, hipMemset(n->d_sat, 0, 256));
+    }
+  }
   n->dirty = false;
   n->table_valid = false;
   n->master_valid = false;
@@ -948,6 +1008,19 @@ struct Run {
     a.pstride = pstride; a.epi = epi;
     const int M = pl.N * a.Hout * a.Wout;
     const dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(a.CoutPad / BN));
+    if (n->prec == FDSR_PREC_F16X3) {
+      if (out2 || !g.split) {
+        if (err == FDSR_OK) err = fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet: this GEMM has no f16x3 form");
+        return;
+      }
+      a.wq = n->d_wq + g.hoff; a.winv = g.hinv; a.sat = n->d_sat;
+      if (g.cin % 8) hipLaunchKernelGGL((naf_gemm_h3_kernel<PRO_NONE, false>), grid, dim3(NT), 0, st, a);
+      else if (pro == PRO_LN) hipLaunchKernelGGL((naf_gemm_h3_kernel<PRO_LN, true>), grid, dim3(NT), 0, st, a);
+      else if (pro == PRO_MUL) hipLaunchKernelGGL((naf_gemm_h3_kernel<PRO_MUL, true>), grid, dim3(NT), 0, st, a);
+      else hipLaunchKernelGGL((naf_gemm_h3_kernel<PRO_NONE, true>), grid, dim3(NT), 0, st, a);
+      check();
+      return;
+    }
     if (g.cin % 8) hipLaunchKernelGGL((naf_gemm_kernel<PRO_NONE, false>), grid, dim3(NT), 0, st, a);
     else if (pro == PRO_LN) hipLaunchKernelGGL((naf_gemm_kernel<PRO_LN, true>), grid, dim3(NT), 0, st, a);
     else if (pro == PRO_MUL) hipLaunchKernelGGL((naf_gemm_kernel<PRO_MUL, true>), grid, dim3(NT), 0, st, a);
@@ -1141,8 +1214,10 @@ void fdsr_nafnet_destroy(fdsr_nafnet n) {
   if (!n) return;
   drop_graph(n);
   for (void* p : {(void*)n->d_arena, (void*)n->d_sde, (void*)n->d_rowtable, (void*)n->d_cur_row, (void*)n->d_ctl, (void*)n->d_master,
-                  (void*)n->d_grad, (void*)n->d_m, (void*)n->d_v, (void*)n->d_cum, (void*)n->d_map, (void*)n->d_rowmap})
+                  (void*)n->d_grad, (void*)n->d_m, (void*)n->d_v, (void*)n->d_cum, (void*)n->d_map, (void*)n->d_rowmap, (void*)n->d_wq,
+                  (void*)n->d_sat})
     if (p) (void)hipFree(p);
+  if (n->h_sat) (void)hipHostFree(n->h_sat);
   delete n;
 }
 
@@ -1181,6 +1256,35 @@ int fdsr_nafnet_weights_complete(fdsr_nafnet n) {
   for (const WT& w : n->wts)
     if (!w.loaded) return 0;
   return 1;
+}
+
+int fdsr_nafnet_set_precision(fdsr_nafnet n, int mode) {
+  if (!n || (mode != FDSR_PREC_F32 && mode != FDSR_PREC_F16X3))
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_set_precision: mode must be FDSR_PREC_F32 (0) or FDSR_PREC_F16X3 (1), not %d", mode);
+  if (mode == n->prec) return FDSR_OK;
+  // the device forms are rebuilt from the fp32 master through pack_forms by the next call that runs (finalize); after optimizer
+  // steps the master is on the device
+  const int rc = host_from_master(n);
+  if (rc) return rc;
+  n->prec = mode;
+  n->dirty = true;
+  drop_graph(n);
+  return FDSR_OK;
+}
+
+int fdsr_nafnet_check_saturation(fdsr_nafnet n, void* hip_stream) {
+  if (!n) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_check_saturation: null object");
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCHK(nullptr, hipStreamSynchronize(st));
+  if (n->prec != FDSR_PREC_F16X3 || !n->d_sat) return FDSR_OK;
+  if (!n->h_sat) HIPCHK(nullptr, hipHostMalloc(reinterpret_cast<void**>(&n->h_sat), 64, hipHostMallocDefault));
+  *n->h_sat = 0;
+  HIPCHK(nullptr, hipMemcpyAsync(n->h_sat, n->d_sat, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(nullptr, hipStreamSynchronize(st));
+  if (!*n->h_sat) return FDSR_OK;
+  HIPCHK(nullptr, hipMemsetAsync(n->d_sat, 0, sizeof(int), st));
+  return fail(nullptr, FDSR_E_SATURATED, "f16x3: a GEMM input of the NAFNet exceeded the f16 range (+-65504) and was clamped; "
+                                         "re-run this call after fdsr_nafnet_set_precision(FDSR_PREC_F32)");
 }
 
 int fdsr_nafnet_set_sde(fdsr_nafnet n, int T, const float* thetas, const float* sigmas, const float* sigma_bars, float dt) {

@@ -972,6 +972,8 @@ int fdsr_nafnet_train_grads(fdsr_nafnet n, const float* state_nchw, const float*
     return fail(nullptr, FDSR_E_INVALID, "%s: B %d at %dx%d exceeds the 32-bit pixel indexing of the kernels", fn, batch, height, width);
   for (const WT& w : n->wts)
     if (!w.loaded) return fail(nullptr, FDSR_E_STATE, "%s: tensor '%s' is missing", fn, w.key.c_str());
+  if (n->prec != FDSR_PREC_F32)
+    return fail(nullptr, FDSR_E_INVALID, "%s: training runs in FDSR_PREC_F32 only, the object is in f16x3 (fdsr_nafnet_set_precision)", fn);
   if (n->T < 1 || n->cum_T != n->T) return fail(nullptr, FDSR_E_STATE, "%s: no schedule (fdsr_nafnet_set_sde, fdsr_nafnet_set_thetas_cumsum)", fn);
   const TrainPlan tp = make_train_plan(n, batch, height, width);
   if (workspace_bytes < tp.bytes || (reinterpret_cast<uintptr_t>(workspace) & 255))
@@ -1032,6 +1034,8 @@ int fdsr_nafnet_optim_step(fdsr_nafnet n, int kind, double lr, double beta1, dou
   if (!n || kind < FDSR_NAFNET_ADAM || kind > FDSR_NAFNET_LION || !(lr >= 0.) || !(beta1 >= 0. && beta1 < 1.) || !(beta2 >= 0. && beta2 < 1.) ||
       !(eps >= 0.) || !(weight_decay >= 0.))
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_optim_step: bad arguments (kind %d)", kind);
+  if (n->prec != FDSR_PREC_F32)   // the device-side re-pack below writes the fp32 forms only
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_optim_step: training runs in FDSR_PREC_F32 only, the object is in f16x3");
   if (!n->d_grad || !n->master_valid || n->dirty) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet_optim_step: no gradients (fdsr_nafnet_train_grads first)");
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   n->opt_step += 1;

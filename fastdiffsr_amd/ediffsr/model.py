@@ -2,6 +2,7 @@
 under the reference's names -- `latest_G.pth` loads with load_state_dict(strict=True) -- and whose forward runs the device
 kernels.  Training runs through train_grads / optim_step (denoising_model.DenoisingModel drives them); there is no
 torch-autograd bridge and no PyTorch fallback."""
+import contextlib
 import ctypes as C
 
 import torch
@@ -163,6 +164,35 @@ class ConditionalNAFNet(nn.Module):
                                                                   _ptr(out), cap, dims, _ptr(ws), ws.numel(), C.c_void_p(st)))
         th, tw, tc = dims[0], dims[1], dims[2]
         return out[:b * th * tw * tc].view(b, th, tw, tc).permute(0, 3, 1, 2).contiguous()
+
+    # ---- precision of the GEMMs (include/fdsr.h: fdsr_nafnet_set_precision) ----
+    PRECISIONS = ('f32', 'f16x3')
+
+    @property
+    def precision(self):
+        return getattr(self, '_precision', 'f32')
+
+    def set_precision(self, mode):
+        """'f32' (exact, the default) or 'f16x3' (fp32-grade, three f16 MFMAs per product).  forward, debug_tensor and sample
+        follow the mode; training runs in 'f32' only."""
+        if mode not in self.PRECISIONS:
+            raise ValueError('precision must be one of %s, not %r' % (self.PRECISIONS, mode))
+        dev = next(self.parameters()).device
+        with torch.cuda.device(dev) if dev.type == 'cuda' else contextlib.nullcontext():
+            _lib.check(None, _lib.load().fdsr_nafnet_set_precision(self._handle(), _lib.PRECISIONS[mode]))
+        self._precision = mode
+
+    def check_saturation(self):
+        """f16x3 clamps GEMM inputs beyond +-65504 and raises a sticky flag: synchronises, reads and clears it.  Raises
+        _lib.FdsrSaturated when it was set (re-run the calls since the last check in 'f32'); a no-op in 'f32'."""
+        dev = next(self.parameters()).device
+        with torch.cuda.device(dev):
+            st = torch.cuda.current_stream(dev).cuda_stream
+            rc = _lib.load().fdsr_nafnet_check_saturation(self._handle(), C.c_void_p(st))
+        if rc == _lib.FDSR_E_SATURATED:
+            msg = _lib.load().fdsr_last_error(None)
+            raise _lib.FdsrSaturated(rc, msg.decode() if msg else '?')
+        _lib.check(None, rc)
 
     def set_sde(self, thetas, sigmas, sigma_bars, dt, device, thetas_cumsum=None):
         T = thetas.numel() - 1

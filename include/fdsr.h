@@ -366,6 +366,23 @@ int fdsr_nafnet_randn(float* dst_nchw, int batch, int height, int width, int pla
 int fdsr_upscale_bicubic_f32(const float* src_nchw, float* dst_nchw, int batch, int channels, int height, int width, int scale,
                              void* hip_stream);
 void fdsr_nafnet_destroy(fdsr_nafnet n);
+/* Precision of the NAFNet's GEMMs (every 1x1 / 2x2 / 3x3 convolution that is not depthwise).
+ *   fdsr_nafnet_set_precision   FDSR_PREC_F32 (default: the exact kernel above) or FDSR_PREC_F16X3: fp32-grade, the staged fp32
+ *                             activation (after LN + FiLM / the SCA multiply) and the weights are each split into an f16 hi and
+ *                             lo part and every product is lo.hi + hi.lo + hi.hi on v_mfma_f32_32x32x16_f16 with an fp32
+ *                             accumulator, one summation order per output (no split-K): the bitwise properties above hold in
+ *                             either mode.  Activations stay fp32 in memory; LayerNorm statistics, the depthwise convolution,
+ *                             SCA / CA, the time path, bias / epilogues and the SDE tail are fp32 in both modes; workspace sizes
+ *                             do not change.  Any other mode: FDSR_E_INVALID.  A switch drops the cached graph and rebuilds the
+ *                             device weight forms from the fp32 master (after optimizer steps: the trained weights) on the next
+ *                             call.  fdsr_nafnet_forward / _debug_tensor / _sample follow the mode; fdsr_nafnet_train_grads and
+ *                             fdsr_nafnet_optim_step run in FDSR_PREC_F32 only (FDSR_E_INVALID under f16x3).
+ *   fdsr_nafnet_check_saturation   f16x3 clamps a GEMM input beyond +-65504 to the f16 range and raises a sticky device flag (so does a NaN).
+ *                             This call synchronises hip_stream, reads and clears the flag: FDSR_OK or FDSR_E_SATURATED (the
+ *                             outputs since the last check are then not fp32-grade: re-run them in FDSR_PREC_F32, which has no
+ *                             such limit).  Always FDSR_OK in FDSR_PREC_F32. */
+int fdsr_nafnet_set_precision(fdsr_nafnet n, int mode);
+int fdsr_nafnet_check_saturation(fdsr_nafnet n, void* hip_stream);
 
 /* EDiffSR training: one step of DenoisingModel.optimize_parameters (models/denoising_model.py) on the device, fp32.
  *   fdsr_nafnet_set_thetas_cumsum   IRSDE.thetas_cumsum [T+1] host fp32, after fdsr_nafnet_set_sde (which forgets it).

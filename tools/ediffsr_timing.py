@@ -1,6 +1,6 @@
 """EDiffSR sampling times on one GPU -> profiles/ediffsr_timing.txt (or --out).
 
-    python tools/ediffsr_timing.py [--out FILE] [--size 256] [--steps 100] [--baseline]
+    python tools/ediffsr_timing.py [--out FILE] [--size 256] [--steps 100] [--baseline] [--precision f32|f16x3]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/ediffsr_timing.py --forward-only     # per-kernel split of forwards
 
 Shipped setting (width 64, enc [14,1,1,1]), synthetic weights, T = --steps, B = 1 and B = 16, eager and graph: ms per image,
@@ -60,6 +60,7 @@ def main():
     ap.add_argument('--batches', type=int, nargs='+', default=[1, 16])
     ap.add_argument('--baseline', action='store_true')
     ap.add_argument('--forward-only', action='store_true')
+    ap.add_argument('--precision', choices=('f32', 'f16x3'), default='f32')
     a = ap.parse_args()
     from fastdiffsr_amd.ediffsr import ConditionalNAFNet, IRSDE
     from fastdiffsr_amd.synth import synth_nafnet
@@ -68,18 +69,22 @@ def main():
     net = ConditionalNAFNet(**SETTING)
     net.load_state_dict(sd, strict=True)
     net = net.to(dev).eval()
+    net.set_precision(a.precision)
     sde = IRSDE(max_sigma=50, T=a.steps, schedule='cosine', eps=0.005, device=dev, rng='engine')
     sde.set_model(net)
-    lines = ['EDiffSR timing: %s, width 64 enc [14,1,1,1], %dx%d, T = %d, fp32 (exact-fp32 MFMA), engine-drawn noise'
-             % (torch.cuda.get_device_name(0), a.size, a.size, a.steps)]
+    lines = ['EDiffSR timing: %s, width 64 enc [14,1,1,1], %dx%d, T = %d, %s, engine-drawn noise'
+             % (torch.cuda.get_device_name(0), a.size, a.size, a.steps,
+                'fp32 (exact-fp32 MFMA)' if a.precision == 'f32' else 'f16x3 (three f16 MFMAs per product, fp32 accumulate)')]
     fl = conv1x1_flops(SETTING, a.size, a.size)
     for b in a.batches:
         g = torch.Generator().manual_seed(b)
         cond = torch.rand(b, 3, a.size, a.size, generator=g).to(dev)
         state = cond + 0.2 * torch.randn(b, 3, a.size, a.size, generator=g).to(dev)
         med, lo, hi = timed(lambda: net(state, cond, 50), 20)
-        lines.append('forward   B=%-2d         %8.3f ms/image (median of 20; min %.3f max %.3f per call / B)  1x1 GEMMs >= %.1f TF = %.3f of %.1f'
-                     % (b, med / b, lo / b, hi / b, fl * b / med / 1e9, fl * b / med / 1e9 / PEAK_TF, PEAK_TF))
+        line = 'forward   B=%-2d         %8.3f ms/image (median of 20; min %.3f max %.3f per call / B)' % (b, med / b, lo / b, hi / b)
+        if a.precision == 'f32':   # a share of the exact-fp32 MFMA peak: no such figure for three f16 MFMAs per product
+            line += '  1x1 GEMMs >= %.1f TF = %.3f of %.1f' % (fl * b / med / 1e9, fl * b / med / 1e9 / PEAK_TF, PEAK_TF)
+        lines.append(line)
         if a.forward_only:
             continue
         sde.set_mu(cond)
@@ -94,6 +99,9 @@ def main():
                 med, lo, hi = timed(lambda: R.forward(dsd, state, cond, torch.full((1,), 50.0, device=dev)), 10)
             lines.append('baseline  B=%-2d forward  %8.3f ms/image (stock PyTorch, fp32, the restatement; x %d steps = %.1f ms/image)'
                          % (b, med / b, a.steps, med / b * a.steps))
+    if a.precision == 'f16x3':
+        net.check_saturation()   # raises if any timed call left the f16 range
+        lines.append('range guard: clear')
     text = '\n'.join(lines) + '\n'
     print(text, end='')
     if a.out:
