@@ -964,10 +964,45 @@ Plan make_plan(fdsr_nafnet n, int N, int H, int W) {
   return p;
 }
 
+// Where the forward walk (Run::net / Run::block) puts every tensor.  Sampling fills the table with aliases of four shared buffers
+// (sample_dst), training with a slot per tensor its backward reads (train_dst in fdsr_nafnet_train.h).
+template <class T> struct Slots { T out, st1, t1, t2, sca, y, st2, p4, g4; };   // a block's; st1 / st2: LayerNorm statistics, p4: conv4's pair before the gate
+typedef Slots<float*> BlockDst;                              // p4 null: not kept
+
+struct NetDst {
+  int N, H, W, Hp, Wp;
+  float *xin, *intro, *r1, *r, *ca, *enh, *eps, *part, *tg, *trow;   // r1, r: the RCAB's two convolutions
+  // per level i: downs[i]'s and ups[i]'s outputs; where encoder level i's skip and decoder step i's result are wanted -- a chain of
+  // blocks that ends elsewhere (an empty list) is copied there; mid: the same for the middle blocks
+  float *down[FDSR_NAFNET_MAX_LEVELS], *up[FDSR_NAFNET_MAX_LEVELS], *skip[FDSR_NAFNET_MAX_LEVELS], *dec[FDSR_NAFNET_MAX_LEVELS], *mid;
+  std::vector<BlockDst> blk;
+};
+
+// A block may write over its input (out == input); its input and out may be none of y, t1, t2 -- except that the input may be y.
+// downs[i] reads skip[i] and writes down[i]: the two are different buffers.
+NetDst sample_dst(fdsr_nafnet n, int N, int H, int W, void* workspace) {
+  const Plan pl = make_plan(n, N, H, W);
+  auto F = [&](size_t off) { return reinterpret_cast<float*>(static_cast<char*>(workspace) + off); };
+  float *A = F(pl.A), *B = F(pl.B), *T1 = F(pl.T1), *T2 = F(pl.T2), *st = F(pl.stats);
+  NetDst d{};
+  d.N = pl.N; d.H = pl.H; d.W = pl.W; d.Hp = pl.Hp; d.Wp = pl.Wp;
+  d.xin = F(pl.xin); d.intro = B; d.r1 = T2; d.r = T1; d.ca = F(pl.ca); d.enh = A; d.eps = F(pl.eps); d.part = F(pl.part);
+  d.tg = F(pl.tg); d.trow = F(pl.trow);
+  d.blk.assign(n->blocks.size(), BlockDst{A, st, T1, T2, F(pl.sca), B, st, nullptr, T2});
+  d.mid = A;
+  for (int i = 0; i < n->L; ++i) {
+    d.down[i] = d.dec[i] = A; d.up[i] = B; d.skip[i] = F(pl.skip[i]);
+    if (!n->enc[i].empty()) d.blk[n->enc[i].back()].out = d.skip[i];
+  }
+  return d;
+}
+
+typedef void (*GemmFn)(GemmArgs);
+template <int PRO, bool VEC> GemmFn gemm_fn(bool h3) { return h3 ? naf_gemm_h3_kernel<PRO, VEC> : naf_gemm_kernel<PRO, VEC>; }
+
 struct Run {
   fdsr_nafnet n;
-  Plan pl;
-  char* ws;
+  NetDst d;
   hipStream_t st;
   const float* rows;   // the blocks' time rows, image b at rows + b * rstride
   int rstride;
@@ -976,13 +1011,20 @@ struct Run {
   const float* tap_ptr = nullptr;
   int tap_h = 0, tap_w = 0, tap_c = 0;
   int err = FDSR_OK;
-  float* stats = nullptr;   // training: this LayerNorm's own slot instead of pl.stats
 
-  float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
   const float* P(size_t off) const { return n->d_arena + off; }
+  static unsigned nb(size_t total) { return (unsigned)((total + 255) / 256); }
   void check() {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess && err == FDSR_OK) err = fail(nullptr, FDSR_E_HIP, "fdsr_nafnet: kernel launch failed: %s", hipGetErrorString(e));
+  }
+  template <class K, class... A> void launch(K kernel, dim3 grid, dim3 block, size_t lds, A... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    check();
+  }
+  void copy(float* dst, const float* src, size_t floats) {
+    (void)hipMemcpyAsync(dst, src, floats * sizeof(float), hipMemcpyDeviceToDevice, st);
+    check();
   }
   bool tap(const std::string& name, const float* ptr, int h, int w, int c) {
     if (err != FDSR_OK) return true;
@@ -990,150 +1032,109 @@ struct Run {
     return false;
   }
 
-  void gemm(int gi, const float* x, float* out, int Hin, int Win, int epi, int pro = PRO_NONE, const float* pmul = nullptr,
-            const float* padd = nullptr, int pstride = 0, const float* res = nullptr, const float* evec = nullptr) {
-    gemm_l(n->gemms[gi], x, out, Hin, Win, epi, pro, pmul, padd, pstride, res, evec);
-  }
+  template <class... A> void gemm(int gi, A... a) { gemm_l(n->gemms[gi], a...); }
 
   void gemm_l(const GemmL& g, const float* x, float* out, int Hin, int Win, int epi, int pro = PRO_NONE, const float* pmul = nullptr,
-              const float* padd = nullptr, int pstride = 0, const float* res = nullptr, const float* evec = nullptr, float* out2 = nullptr) {
+              const float* padd = nullptr, int pstride = 0, const float* stats = nullptr, const float* res = nullptr,
+              const float* evec = nullptr, float* out2 = nullptr) {
     GemmArgs a{};
     a.x = x; a.w = P(g.woff); a.bias = P(g.boff); a.out = out; a.out2 = out2;
-    a.stats = stats ? stats : F(pl.stats); a.pmul = pmul; a.padd = padd; a.res = res; a.evec = evec;
-    a.N = pl.N; a.Hin = Hin; a.Win = Win; a.Cin = g.cin;
+    a.stats = stats; a.pmul = pmul; a.padd = padd; a.res = res; a.evec = evec;
+    a.N = d.N; a.Hin = Hin; a.Win = Win; a.Cin = g.cin;
     a.Hout = (Hin + 2 * g.p - g.ks) / g.s + 1;
     a.Wout = (Win + 2 * g.p - g.ks) / g.s + 1;
     a.Cout = g.cout; a.KW = g.ks; a.S = g.s; a.P = g.p; a.K = g.K(); a.Kpad = g.Kpad(); a.CoutPad = g.CoutPad();
     a.ostride = epi == EPI_GATE ? g.cout / 2 : epi == EPI_PSHUF ? g.cout / 4 : g.cout;
     a.pstride = pstride; a.epi = epi;
-    const int M = pl.N * a.Hout * a.Wout;
+    const int M = d.N * a.Hout * a.Wout;
     const dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(a.CoutPad / BN));
-    if (n->prec == FDSR_PREC_F16X3) {
+    const bool h3 = n->prec == FDSR_PREC_F16X3;
+    if (h3) {
       if (out2 || !g.split) {
         if (err == FDSR_OK) err = fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet: this GEMM has no f16x3 form");
         return;
       }
       a.wq = n->d_wq + g.hoff; a.winv = g.hinv; a.sat = n->d_sat;
-      if (g.cin % 8) hipLaunchKernelGGL((naf_gemm_h3_kernel<PRO_NONE, false>), grid, dim3(NT), 0, st, a);
-      else if (pro == PRO_LN) hipLaunchKernelGGL((naf_gemm_h3_kernel<PRO_LN, true>), grid, dim3(NT), 0, st, a);
-      else if (pro == PRO_MUL) hipLaunchKernelGGL((naf_gemm_h3_kernel<PRO_MUL, true>), grid, dim3(NT), 0, st, a);
-      else hipLaunchKernelGGL((naf_gemm_h3_kernel<PRO_NONE, true>), grid, dim3(NT), 0, st, a);
-      check();
-      return;
     }
-    if (g.cin % 8) hipLaunchKernelGGL((naf_gemm_kernel<PRO_NONE, false>), grid, dim3(NT), 0, st, a);
-    else if (pro == PRO_LN) hipLaunchKernelGGL((naf_gemm_kernel<PRO_LN, true>), grid, dim3(NT), 0, st, a);
-    else if (pro == PRO_MUL) hipLaunchKernelGGL((naf_gemm_kernel<PRO_MUL, true>), grid, dim3(NT), 0, st, a);
-    else hipLaunchKernelGGL((naf_gemm_kernel<PRO_NONE, true>), grid, dim3(NT), 0, st, a);
-    check();
+    const GemmFn k = g.cin % 8 ? gemm_fn<PRO_NONE, false>(h3) : pro == PRO_LN ? gemm_fn<PRO_LN, true>(h3)
+                     : pro == PRO_MUL ? gemm_fn<PRO_MUL, true>(h3) : gemm_fn<PRO_NONE, true>(h3);
+    launch(k, grid, dim3(NT), 0, a);
   }
 
-  void ln_stats(const float* x, int M, int C) {
-    hipLaunchKernelGGL(naf_ln_stats_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, st, x, stats ? stats : F(pl.stats), M, C);
-    check();
-  }
+  void ln_stats(const float* x, float* stats, int M, int C) { launch(naf_ln_stats_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, x, stats, M, C); }
 
-  // cur -> out (out may be cur; neither may be B, T1, T2 -- except cur == B)
-  void block(int bi, const float* cur, float* out, int h, int w) {
+  void block(int bi, const float* cur, int h, int w) {
     const BlockL& b = n->blocks[bi];
-    const int c = b.c, HW = h * w, M = pl.N * HW, ns = nstrips_of(HW);
+    const BlockDst& s = d.blk[bi];
+    const int c = b.c, HW = h * w, M = d.N * HW, ns = nstrips_of(HW);
     const float* rw = rows + b.row_off;
-    float *B = F(pl.B), *T1 = F(pl.T1), *T2 = F(pl.T2), *part = F(pl.part), *sca = F(pl.sca);
-    ln_stats(cur, M, c);
-    gemm(b.conv1, cur, T1, h, w, EPI_BIAS, PRO_LN, rw + c, rw, rstride);
-    hipLaunchKernelGGL(naf_dw_gate_kernel, dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)pl.N), dim3(256), 0, st, T1, P(b.off_dww),
-                       P(b.off_dwb), T2, part, h, w, c, ns);
-    check();
-    hipLaunchKernelGGL(naf_sca_kernel, dim3((unsigned)((c + 15) / 16), (unsigned)pl.N), dim3(256), (c + 256) * sizeof(float), st, part, ns, HW,
-                       P(b.off_scaw), P(b.off_scab), sca, c);
-    check();
-    gemm(b.conv3, T2, B, h, w, EPI_RES, PRO_MUL, sca, nullptr, c, cur, P(b.off_beta));
-    ln_stats(B, M, c);
-    gemm(b.conv4, B, T2, h, w, EPI_GATE, PRO_LN, rw + 3 * c, rw + 2 * c, rstride);
-    gemm(b.conv5, T2, out, h, w, EPI_RES, PRO_NONE, nullptr, nullptr, 0, B, P(b.off_gamma));
+    ln_stats(cur, s.st1, M, c);
+    gemm(b.conv1, cur, s.t1, h, w, EPI_BIAS, PRO_LN, rw + c, rw, rstride, s.st1);
+    launch(naf_dw_gate_kernel, dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)d.N), dim3(256), 0, s.t1, P(b.off_dww), P(b.off_dwb), s.t2,
+           d.part, h, w, c, ns);
+    launch(naf_sca_kernel, dim3((unsigned)((c + 15) / 16), (unsigned)d.N), dim3(256), (c + 256) * sizeof(float), d.part, ns, HW, P(b.off_scaw),
+           P(b.off_scab), s.sca, c);
+    gemm(b.conv3, s.t2, s.y, h, w, EPI_RES, PRO_MUL, s.sca, nullptr, c, nullptr, cur, P(b.off_beta));
+    ln_stats(s.y, s.st2, M, c);
+    gemm(b.conv4, s.y, s.g4, h, w, EPI_GATE, PRO_LN, rw + 3 * c, rw + 2 * c, rstride, s.st2, nullptr, nullptr, s.p4);
+    gemm(b.conv5, s.g4, s.out, h, w, EPI_RES, PRO_NONE, nullptr, nullptr, 0, nullptr, s.y, P(b.off_gamma));
   }
 
-  // the network up to `ending` (padded NHWC [N][Hp][Wp][3] in pl.eps); xin is staged already
+  // the blocks of `list` from cur on; the result is wanted at `want` and copied there if the chain ended elsewhere.  False: stop (a tap, an error)
+  bool chain(const std::vector<int>& list, const float* cur, float* want, int h, int w, int c) {
+    for (int bi : list) {
+      block(bi, cur, h, w);
+      cur = d.blk[bi].out;
+      if (tap(n->blocks[bi].name, cur, h, w, c)) return false;
+    }
+    if (cur != want) copy(want, cur, (size_t)d.N * h * w * c);
+    return true;
+  }
+
+  // the network up to `ending` (padded NHWC [N][Hp][Wp][3] in d.eps); xin is staged already
   void net() {
     const int wd = n->wd, L = n->L;
-    int h = pl.Hp, w = pl.Wp;
-    float *A = F(pl.A), *B = F(pl.B), *T1 = F(pl.T1), *T2 = F(pl.T2);
-    gemm(n->g_intro, F(pl.xin), B, h, w, EPI_BIAS);
-    if (tap("intro", B, h, w, wd)) return;
-    gemm(n->g_rcab0, B, T2, h, w, EPI_RELU);
-    gemm(n->g_rcab2, T2, T1, h, w, EPI_BIAS);
-    {
-      const int HW = h * w, ns = nstrips_of(HW);
-      hipLaunchKernelGGL(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)pl.N), dim3(256), 0, st, T1, F(pl.part), HW,
-                         wd, ns);
-      check();
-      hipLaunchKernelGGL(naf_ca_kernel, dim3((unsigned)pl.N), dim3(256), (wd + 256 + wd / 16) * sizeof(float), st, F(pl.part), ns, HW,
-                         P(n->off_ca1w), P(n->off_ca1b), P(n->off_ca2w), P(n->off_ca2b), F(pl.ca), wd, wd / 16);
-      check();
-      const size_t total = (size_t)pl.N * HW * wd;
-      hipLaunchKernelGGL(naf_enhance_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, B, T1, F(pl.ca), A, HW, wd, total);
-      check();
-    }
-    if (tap("enhance", A, h, w, wd)) return;
-    int c = wd;
+    int h = d.Hp, w = d.Wp, c = wd;
+    gemm(n->g_intro, d.xin, d.intro, h, w, EPI_BIAS);
+    if (tap("intro", d.intro, h, w, wd)) return;
+    gemm(n->g_rcab0, d.intro, d.r1, h, w, EPI_RELU);
+    gemm(n->g_rcab2, d.r1, d.r, h, w, EPI_BIAS);
+    const int HW = h * w, ns = nstrips_of(HW);
+    launch(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)d.N), dim3(256), 0, d.r, d.part, HW, wd, ns);
+    launch(naf_ca_kernel, dim3((unsigned)d.N), dim3(256), (wd + 256 + wd / 16) * sizeof(float), d.part, ns, HW, P(n->off_ca1w), P(n->off_ca1b),
+           P(n->off_ca2w), P(n->off_ca2b), d.ca, wd, wd / 16);
+    const size_t total = (size_t)d.N * HW * wd;
+    launch(naf_enhance_kernel, dim3(nb(total)), dim3(256), 0, d.intro, d.r, d.ca, d.enh, HW, wd, total);
+    if (tap("enhance", d.enh, h, w, wd)) return;
     for (int i = 0; i < L; ++i) {
-      float* skip = F(pl.skip[i]);
-      const float* cur = A;
-      const int nb = (int)n->enc[i].size();
-      for (int j = 0; j < nb; ++j) {
-        float* out = j == nb - 1 ? skip : A;
-        block(n->enc[i][j], cur, out, h, w);
-        if (tap(n->blocks[n->enc[i][j]].name, out, h, w, c)) return;
-        cur = out;
-      }
-      if (nb == 0) {
-        (void)hipMemcpyAsync(skip, A, (size_t)pl.N * h * w * c * sizeof(float), hipMemcpyDeviceToDevice, st);
-        check();
-      }
-      gemm(n->downs[i], skip, A, h, w, EPI_BIAS);
+      if (!chain(n->enc[i], i ? d.down[i - 1] : d.enh, d.skip[i], h, w, c)) return;
+      gemm(n->downs[i], d.skip[i], d.down[i], h, w, EPI_BIAS);
       h /= 2; w /= 2; c *= 2;
-      if (tap("downs." + std::to_string(i), A, h, w, c)) return;
+      if (tap("downs." + std::to_string(i), d.down[i], h, w, c)) return;
     }
-    for (size_t j = 0; j < n->mid.size(); ++j) {
-      block(n->mid[j], A, A, h, w);
-      if (tap(n->blocks[n->mid[j]].name, A, h, w, c)) return;
-    }
+    if (!chain(n->mid, d.down[L - 1], d.mid, h, w, c)) return;
     for (int i = 0; i < L; ++i) {
-      const float* skip = F(pl.skip[L - 1 - i]);
-      gemm(n->ups[i], A, B, h, w, EPI_PSHUF, PRO_NONE, nullptr, nullptr, 0, skip);
+      gemm(n->ups[i], i ? d.dec[i - 1] : d.mid, d.up[i], h, w, EPI_PSHUF, PRO_NONE, nullptr, nullptr, 0, nullptr, d.skip[L - 1 - i]);
       h *= 2; w *= 2; c /= 2;
-      if (tap("ups." + std::to_string(i), B, h, w, c)) return;
-      const float* cur = B;
-      for (size_t j = 0; j < n->dec[i].size(); ++j) {
-        block(n->dec[i][j], cur, A, h, w);
-        if (tap(n->blocks[n->dec[i][j]].name, A, h, w, c)) return;
-        cur = A;
-      }
-      if (n->dec[i].empty()) {
-        (void)hipMemcpyAsync(A, B, (size_t)pl.N * h * w * c * sizeof(float), hipMemcpyDeviceToDevice, st);
-        check();
-      }
+      if (tap("ups." + std::to_string(i), d.up[i], h, w, c)) return;
+      if (!chain(n->dec[i], d.up[i], d.dec[i], h, w, c)) return;
     }
-    gemm(n->g_ending, A, F(pl.eps), h, w, EPI_BIAS);
-    tap("ending", F(pl.eps), h, w, n->cfg.img_channel);
+    gemm(n->g_ending, d.dec[L - 1], d.eps, h, w, EPI_BIAS);
+    tap("ending", d.eps, h, w, n->cfg.img_channel);
   }
 
   void prep(const float* x, const float* cond) {
-    const size_t total = (size_t)pl.N * pl.Hp * pl.Wp;
-    hipLaunchKernelGGL(naf_prep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, x, cond, F(pl.xin), pl.H, pl.W, pl.Hp, pl.Wp,
-                       total);
-    check();
+    const size_t total = (size_t)d.N * d.Hp * d.Wp;
+    launch(naf_prep_kernel, dim3(nb(total)), dim3(256), 0, x, cond, d.xin, d.H, d.W, d.Hp, d.Wp, total);
   }
 
   // time rows of `count` time values (device) into dst [count][R]; tg: scratch [count][2 wd]
   void time_rows(const float* time_dev, int count, float* tg, float* dst) {
     const int wd = n->wd;
-    hipLaunchKernelGGL(naf_time_kernel, dim3((unsigned)count), dim3(256), 17 * wd * sizeof(float), st, time_dev, P(n->off_freq), P(n->off_t1w),
-                       P(n->off_t1b), P(n->off_t2w), P(n->off_t2b), tg, wd);
-    check();
-    hipLaunchKernelGGL(naf_rows_kernel, dim3((unsigned)((n->R + 255) / 256), (unsigned)count), dim3(256), 0, st, tg, P(n->off_rowsw),
-                       P(n->off_rowsb), P(n->off_rowsadd), P(n->off_rowsmul), dst, 2 * wd, n->R);
-    check();
+    launch(naf_time_kernel, dim3((unsigned)count), dim3(256), 17 * wd * sizeof(float), time_dev, P(n->off_freq), P(n->off_t1w), P(n->off_t1b),
+           P(n->off_t2w), P(n->off_t2b), tg, wd);
+    launch(naf_rows_kernel, dim3((unsigned)((n->R + 255) / 256), (unsigned)count), dim3(256), 0, tg, P(n->off_rowsw), P(n->off_rowsb),
+           P(n->off_rowsadd), P(n->off_rowsmul), dst, 2 * wd, n->R);
   }
 
   void tail(int mode, float* x, const float* cond, const float* noise, float* traj, unsigned long long seed, long long first) {
@@ -1146,22 +1147,25 @@ struct Run {
       tb.sqrt_dt = (float)std::sqrt((double)n->dt);
       tb.T = n->T;
     }
-    const size_t total = (size_t)pl.N * pl.H * pl.W;
-    hipLaunchKernelGGL(naf_tail_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, F(pl.eps), x, cond, noise, traj, n->d_ctl, tb, seed,
-                       first, mode, pl.H, pl.W, pl.Hp, pl.Wp, total);
-    check();
+    const size_t total = (size_t)d.N * d.H * d.W;
+    launch(naf_tail_kernel, dim3(nb(total)), dim3(256), 0, d.eps, x, cond, noise, traj, n->d_ctl, tb, seed, first, mode, d.H, d.W, d.Hp, d.Wp, total);
   }
 };
 
-int check_args(fdsr_nafnet n, const char* fn, int batch, int height, int width, void* ws, size_t ws_bytes, Plan* pl) {
+size_t plan_bytes(fdsr_nafnet n, int N, int H, int W) { return make_plan(n, N, H, W).bytes; }
+
+// What every call that runs the network checks first: the shape limits, the weights (finalize), the workspace against the bytes of
+// the call's plan (plan_bytes, train_plan_bytes), asked for once the shape is known to be good.
+int check_args(fdsr_nafnet n, const char* fn, int batch, int height, int width, void* ws, size_t ws_bytes,
+               size_t (*need_bytes)(fdsr_nafnet, int, int, int)) {
   if (!n || batch < 1 || height < 1 || width < 1 || !ws) return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, batch, height, width);
   if ((size_t)batch * round_up(height, 1 << n->L) * round_up(width, 1 << n->L) * 2 * n->wd >= (1ull << 31) || batch > 65535)
     return fail(nullptr, FDSR_E_INVALID, "%s: B %d at %dx%d exceeds the 32-bit pixel indexing of the kernels", fn, batch, height, width);
   const int rc = finalize(n);
   if (rc) return rc;
-  *pl = make_plan(n, batch, height, width);
-  if (ws_bytes < pl->bytes || (reinterpret_cast<uintptr_t>(ws) & 255))
-    return fail(nullptr, FDSR_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes) or not 256-byte aligned", fn, ws_bytes, pl->bytes);
+  const size_t need = need_bytes(n, batch, height, width);
+  if (ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 255))
+    return fail(nullptr, FDSR_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes) or not 256-byte aligned", fn, ws_bytes, need);
   return FDSR_OK;
 }
 
@@ -1174,9 +1178,8 @@ int ensure_table(fdsr_nafnet n, hipStream_t st) {
   if (!n->d_ctl) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_ctl), 256));
   HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&times), cnt * sizeof(float)));
   HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&tg), (size_t)cnt * 2 * n->wd * sizeof(float)));
-  Run r{n, Plan{}, nullptr, st, nullptr, 0};
-  hipLaunchKernelGGL(naf_iota_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, times, cnt);
-  r.check();
+  Run r{n, NetDst{}, st, nullptr, 0};
+  r.launch(naf_iota_kernel, dim3(Run::nb(cnt)), dim3(256), 0, times, cnt);
   r.time_rows(times, cnt, tg, n->d_rowtable);
   const hipError_t e = hipStreamSynchronize(st);   // once per (weights, schedule): the scratch is freed below
   (void)hipFree(times);
@@ -1312,19 +1315,18 @@ int fdsr_nafnet_set_sde(fdsr_nafnet n, int T, const float* thetas, const float* 
 int fdsr_nafnet_workspace_bytes(fdsr_nafnet n, int batch, int height, int width, size_t* bytes) {
   if (!n || !bytes || batch < 1 || height < 1 || width < 1)
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_workspace_bytes: bad arguments (B %d, %dx%d)", batch, height, width);
-  *bytes = make_plan(n, batch, height, width).bytes;
+  *bytes = plan_bytes(n, batch, height, width);
   return FDSR_OK;
 }
 
 int fdsr_nafnet_forward(fdsr_nafnet n, const float* x_nchw, const float* cond_nchw, const float* time_dev, float* out_nchw, int batch,
                         int height, int width, void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (!x_nchw || !cond_nchw || !time_dev || !out_nchw) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_forward: null tensor");
-  Plan pl;
-  const int rc = check_args(n, "fdsr_nafnet_forward", batch, height, width, workspace, workspace_bytes, &pl);
+  const int rc = check_args(n, "fdsr_nafnet_forward", batch, height, width, workspace, workspace_bytes, plan_bytes);
   if (rc) return rc;
-  Run r{n, pl, static_cast<char*>(workspace), reinterpret_cast<hipStream_t>(hip_stream), nullptr, n->R};
-  r.time_rows(time_dev, batch, r.F(pl.tg), r.F(pl.trow));
-  r.rows = r.F(pl.trow);
+  Run r{n, sample_dst(n, batch, height, width, workspace), reinterpret_cast<hipStream_t>(hip_stream), nullptr, n->R};
+  r.time_rows(time_dev, batch, r.d.tg, r.d.trow);
+  r.rows = r.d.trow;
   r.prep(x_nchw, cond_nchw);
   r.net();
   r.tail(0, out_nchw, nullptr, nullptr, nullptr, 0, 0);
@@ -1335,13 +1337,12 @@ int fdsr_nafnet_debug_tensor(fdsr_nafnet n, const char* name, const float* x_nch
                              int batch, int height, int width, float* out_nhwc, size_t capacity_floats, int* dims3, void* workspace,
                              size_t workspace_bytes, void* hip_stream) {
   if (!name || !x_nchw || !cond_nchw || !time_dev || !out_nhwc || !dims3) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_debug_tensor: null argument");
-  Plan pl;
-  const int rc = check_args(n, "fdsr_nafnet_debug_tensor", batch, height, width, workspace, workspace_bytes, &pl);
+  const int rc = check_args(n, "fdsr_nafnet_debug_tensor", batch, height, width, workspace, workspace_bytes, plan_bytes);
   if (rc) return rc;
-  Run r{n, pl, static_cast<char*>(workspace), reinterpret_cast<hipStream_t>(hip_stream), nullptr, n->R};
+  Run r{n, sample_dst(n, batch, height, width, workspace), reinterpret_cast<hipStream_t>(hip_stream), nullptr, n->R};
   r.stop = name;
-  r.time_rows(time_dev, batch, r.F(pl.tg), r.F(pl.trow));
-  r.rows = r.F(pl.trow);
+  r.time_rows(time_dev, batch, r.d.tg, r.d.trow);
+  r.rows = r.d.trow;
   r.prep(x_nchw, cond_nchw);
   r.net();
   if (r.err) return r.err;
@@ -1362,22 +1363,19 @@ int fdsr_nafnet_sample(fdsr_nafnet n, const float* state_nchw, const float* cond
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   const bool use_graph = flags & FDSR_SAMPLE_GRAPH;
   if (use_graph && !st) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_sample: FDSR_SAMPLE_GRAPH needs a created stream");
-  Plan pl;
-  int rc = check_args(n, "fdsr_nafnet_sample", batch, height, width, workspace, workspace_bytes, &pl);
+  int rc = check_args(n, "fdsr_nafnet_sample", batch, height, width, workspace, workspace_bytes, plan_bytes);
   if (rc) return rc;
   if ((rc = ensure_table(n, st))) return rc;
   const int mode = (flags & FDSR_NAFNET_ODE) ? 2 : 1;
   HIPCHK(nullptr, hipMemcpyAsync(out_nchw, state_nchw, (size_t)batch * 3 * height * width * sizeof(float), hipMemcpyDeviceToDevice, st));
   HIPCHK(nullptr, hipMemsetAsync(n->d_ctl, 0, sizeof(int), st));
+  Run r{n, sample_dst(n, batch, height, width, workspace), st, n->d_cur_row, 0};
   auto step = [&]() -> int {
-    Run r{n, pl, static_cast<char*>(workspace), st, n->d_cur_row, 0};
-    hipLaunchKernelGGL(naf_row_copy_kernel, dim3((unsigned)((n->R + 255) / 256)), dim3(256), 0, st, n->d_rowtable, n->d_cur_row, n->d_ctl, n->T, n->R);
-    r.check();
+    r.launch(naf_row_copy_kernel, dim3(Run::nb(n->R)), dim3(256), 0, n->d_rowtable, n->d_cur_row, n->d_ctl, n->T, n->R);
     r.prep(out_nchw, cond_nchw);
     r.net();
     r.tail(mode, out_nchw, cond_nchw, noise, traj, seed, first_image);
-    hipLaunchKernelGGL(naf_advance_kernel, dim3(1), dim3(64), 0, st, n->d_ctl);
-    r.check();
+    r.launch(naf_advance_kernel, dim3(1), dim3(64), 0, n->d_ctl);
     return r.err;
   };
   if (!use_graph) {

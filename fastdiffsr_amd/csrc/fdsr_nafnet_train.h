@@ -1,7 +1,8 @@
 // EDiffSR training on gfx950: one step of DenoisingModel.optimize_parameters (EDiffSR/codes/config/sisr/models/denoising_model.py) for
 // ConditionalNAFNet + IR-SDE, fp32.  Part of fdsr_nafnet.hip's translation unit (it shares the forward kernels, the schema and Run).
 //
-//   saving forward   the forward's own kernels with the forward's arguments, every tensor the backward reads in a slot of its own
+//   forward          Run::net itself, the walk sampling runs, over another destination table (train_dst): every tensor the backward
+//                    reads lands in a slot of its own instead of one of sampling's four shared buffers, and conv4 keeps its pair
 //   loss head        xt_1_expection, xt_1_optimum, MatchingLoss (l1 / l2), d eps
 //   backward         input gradients: naf_gemm_kernel over the transposed packs (pack_forms); weight / bias gradients:
 //                    naf_wgrad_kernel (v_mfma_f32_32x32x2_f32, split over pixel chunks, second pass in chunk order); the rest elementwise
@@ -575,7 +576,7 @@ __global__ void __launch_bounds__(256) naf_repack_kernel(float* __restrict__ are
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 
-struct BlockSlots { size_t out, st1, t1, t2, sca, y, st2, p4, g4; };
+typedef Slots<size_t> BlockSlots;   // workspace offsets
 
 struct TrainPlan {
   int N, H, W, Hp, Wp;
@@ -672,81 +673,39 @@ int ensure_train(fdsr_nafnet n) {
   return FDSR_OK;
 }
 
-struct TrainRun {
-  fdsr_nafnet n;
+size_t train_plan_bytes(fdsr_nafnet n, int N, int H, int W) { return make_train_plan(n, N, H, W).bytes; }
+
+// the forward walk's table for training: every tensor in its own slot, and every chain of blocks wanted where it ends (no copies)
+NetDst train_dst(fdsr_nafnet n, const TrainPlan& tp, char* ws) {
+  auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+  NetDst d{};
+  d.N = tp.N; d.H = tp.H; d.W = tp.W; d.Hp = tp.Hp; d.Wp = tp.Wp;
+  d.xin = F(tp.xin); d.intro = F(tp.x0); d.r1 = F(tp.r1); d.r = F(tp.r); d.ca = F(tp.ca); d.enh = F(tp.enh); d.eps = F(tp.eps);
+  d.part = F(tp.part); d.tg = F(tp.tg); d.trow = F(tp.trow);
+  for (const BlockSlots& s : tp.blk)
+    d.blk.push_back({F(s.out), F(s.st1), F(s.t1), F(s.t2), F(s.sca), F(s.y), F(s.st2), F(s.p4), F(s.g4)});
+  auto end = [&](const std::vector<int>& list, float* first) { return list.empty() ? first : d.blk[list.back()].out; };
+  for (int i = 0; i < n->L; ++i) {
+    d.down[i] = F(tp.down[i]);
+    d.up[i] = F(tp.up[i]);
+    d.skip[i] = end(n->enc[i], i ? d.down[i - 1] : d.enh);
+    d.dec[i] = end(n->dec[i], d.up[i]);
+  }
+  d.mid = end(n->mid, d.down[n->L - 1]);
+  return d;
+}
+
+// Run's forward walk over train_dst, then the backward over what it left there
+struct TrainRun : Run {
   TrainPlan tp;
-  Run r;   // the forward's launchers (its plan carries the sizes only; every buffer is one of tp's)
   char* ws;
-  hipStream_t st;
 
   float* F(size_t off) const { return reinterpret_cast<float*>(ws + off); }
-  const float* P(size_t off) const { return n->d_arena + off; }
   float* G(int wi) const { return n->d_grad + n->poff[wi]; }
-  static unsigned nb(size_t total) { return (unsigned)((total + 255) / 256); }
-
-  // ---- the saving forward: Run::block / Run::net with every output in its slot ----
-  void block_fwd(int bi, const float* cur, int h, int w) {
-    const BlockL& b = n->blocks[bi];
-    const BlockSlots& s = tp.blk[bi];
-    const int c = b.c, HW = h * w, M = tp.N * HW, ns = nstrips_of(HW);
-    const float* rw = r.rows + b.row_off;
-    r.stats = F(s.st1);
-    r.ln_stats(cur, M, c);
-    r.gemm(b.conv1, cur, F(s.t1), h, w, EPI_BIAS, PRO_LN, rw + c, rw, r.rstride);
-    hipLaunchKernelGGL(naf_dw_gate_kernel, dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)tp.N), dim3(256), 0, st, F(s.t1), P(b.off_dww),
-                       P(b.off_dwb), F(s.t2), F(tp.part), h, w, c, ns);
-    r.check();
-    hipLaunchKernelGGL(naf_sca_kernel, dim3((unsigned)((c + 15) / 16), (unsigned)tp.N), dim3(256), (c + 256) * sizeof(float), st, F(tp.part), ns, HW,
-                       P(b.off_scaw), P(b.off_scab), F(s.sca), c);
-    r.check();
-    r.gemm(b.conv3, F(s.t2), F(s.y), h, w, EPI_RES, PRO_MUL, F(s.sca), nullptr, c, cur, P(b.off_beta));
-    r.stats = F(s.st2);
-    r.ln_stats(F(s.y), M, c);
-    r.gemm_l(n->gemms[b.conv4], F(s.y), F(s.g4), h, w, EPI_GATE, PRO_LN, rw + 3 * c, rw + 2 * c, r.rstride, nullptr, nullptr, F(s.p4));
-    r.gemm(b.conv5, F(s.g4), F(s.out), h, w, EPI_RES, PRO_NONE, nullptr, nullptr, 0, F(s.y), P(b.off_gamma));
-  }
 
   // the input of block j of a list whose first block reads `first`
-  const float* chain_in(const std::vector<int>& list, size_t j, const float* first) const { return j == 0 ? first : F(tp.blk[list[j - 1]].out); }
-  const float* chain_out(const std::vector<int>& list, const float* first) const { return list.empty() ? first : F(tp.blk[list.back()].out); }
-  const float* enc_in(int i) const { return i == 0 ? F(tp.enh) : F(tp.down[i - 1]); }
-  const float* mid_in() const { return F(tp.down[n->L - 1]); }
-
-  void net_fwd() {
-    const int wd = n->wd, L = n->L;
-    int h = tp.Hp, w = tp.Wp;
-    r.gemm(n->g_intro, F(tp.xin), F(tp.x0), h, w, EPI_BIAS);
-    r.gemm(n->g_rcab0, F(tp.x0), F(tp.r1), h, w, EPI_RELU);
-    r.gemm(n->g_rcab2, F(tp.r1), F(tp.r), h, w, EPI_BIAS);
-    {
-      const int HW = h * w, ns = nstrips_of(HW);
-      hipLaunchKernelGGL(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)tp.N), dim3(256), 0, st, F(tp.r), F(tp.part), HW,
-                         wd, ns);
-      r.check();
-      hipLaunchKernelGGL(naf_ca_kernel, dim3((unsigned)tp.N), dim3(256), (wd + 256 + wd / 16) * sizeof(float), st, F(tp.part), ns, HW, P(n->off_ca1w),
-                         P(n->off_ca1b), P(n->off_ca2w), P(n->off_ca2b), F(tp.ca), wd, wd / 16);
-      r.check();
-      const size_t total = (size_t)tp.N * HW * wd;
-      hipLaunchKernelGGL(naf_enhance_kernel, dim3(nb(total)), dim3(256), 0, st, F(tp.x0), F(tp.r), F(tp.ca), F(tp.enh), HW, wd, total);
-      r.check();
-    }
-    for (int i = 0; i < L; ++i) {
-      for (size_t j = 0; j < n->enc[i].size(); ++j) block_fwd(n->enc[i][j], chain_in(n->enc[i], j, enc_in(i)), h, w);
-      r.gemm(n->downs[i], chain_out(n->enc[i], enc_in(i)), F(tp.down[i]), h, w, EPI_BIAS);
-      h /= 2; w /= 2;
-    }
-    for (size_t j = 0; j < n->mid.size(); ++j) block_fwd(n->mid[j], chain_in(n->mid, j, mid_in()), h, w);
-    const float* cur = chain_out(n->mid, mid_in());
-    for (int i = 0; i < L; ++i) {
-      const float* skip = chain_out(n->enc[L - 1 - i], enc_in(L - 1 - i));
-      r.gemm(n->ups[i], cur, F(tp.up[i]), h, w, EPI_PSHUF, PRO_NONE, nullptr, nullptr, 0, skip);
-      h *= 2; w *= 2;
-      for (size_t j = 0; j < n->dec[i].size(); ++j) block_fwd(n->dec[i][j], chain_in(n->dec[i], j, F(tp.up[i])), h, w);
-      cur = chain_out(n->dec[i], F(tp.up[i]));
-    }
-    r.stats = nullptr;
-    r.gemm(n->g_ending, cur, F(tp.eps), h, w, EPI_BIAS);
-  }
+  const float* chain_in(const std::vector<int>& list, size_t j, const float* first) const { return j == 0 ? first : d.blk[list[j - 1]].out; }
+  const float* enc_in(int i) const { return i ? d.down[i - 1] : d.enh; }
 
   // ---- backward launchers ----
   // weight (and bias) gradient of gemm gi: x its forward input (Hin x Win), dy [M][cout]
@@ -766,79 +725,65 @@ struct TrainRun {
     const int M = a.N * a.Hout * a.Wout, nz = (M + WG_CHUNK - 1) / WG_CHUNK;
     const dim3 grid((unsigned)((a.Keff + 63) / 64), (unsigned)((a.Cout + 63) / 64), (unsigned)nz);
     if ((size_t)nz * grid.x * 64 * grid.y * 64 > tp.wg_floats) {
-      if (r.err == FDSR_OK) r.err = fail(nullptr, FDSR_E_WORKSPACE, "fdsr_nafnet_train_grads: weight-gradient scratch too small");
+      if (err == FDSR_OK) err = fail(nullptr, FDSR_E_WORKSPACE, "fdsr_nafnet_train_grads: weight-gradient scratch too small");
       return;
     }
-    if (pro == PRO_LN) hipLaunchKernelGGL((naf_wgrad_kernel<PRO_LN>), grid, dim3(256), 0, st, a);
-    else if (pro == PRO_MUL) hipLaunchKernelGGL((naf_wgrad_kernel<PRO_MUL>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((naf_wgrad_kernel<PRO_NONE>), grid, dim3(256), 0, st, a);
-    r.check();
-    hipLaunchKernelGGL(naf_wgrad_finish_kernel, dim3(nb((size_t)a.Keff * a.Cout)), dim3(256), 0, st, a.part, nz, (int)grid.x * 64, (int)grid.y * 64,
-                       a.Keff, a.K, a.Cout, a.Cin, taps, mode, gw, gb);
-    r.check();
+    launch(pro == PRO_LN ? naf_wgrad_kernel<PRO_LN> : pro == PRO_MUL ? naf_wgrad_kernel<PRO_MUL> : naf_wgrad_kernel<PRO_NONE>, grid, dim3(256), 0, a);
+    launch(naf_wgrad_finish_kernel, dim3(nb((size_t)a.Keff * a.Cout)), dim3(256), 0, a.part, nz, (int)grid.x * 64, (int)grid.y * 64, a.Keff, a.K,
+           a.Cout, a.Cin, taps, mode, gw, gb);
   }
 
   // per-channel sums over pixels: dst[g][ch], groups = N (per image, rows dstride apart) or 1 (everything)
   void dot(const float* a, const float* b, const float* stats, int mode, int HW, int c, float* dst, bool per_image, int dstride, float scale = 1.f) {
     const int ns = nstrips_of(HW);
-    hipLaunchKernelGGL(naf_dot_kernel, dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)tp.N), dim3(256), 0, st, a, b, stats, F(tp.part), HW, c, ns,
-                       mode);
-    r.check();
+    launch(naf_dot_kernel, dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)tp.N), dim3(256), 0, a, b, stats, d.part, HW, c, ns, mode);
     const int groups = per_image ? tp.N : 1, Gn = per_image ? ns : tp.N * ns;
-    hipLaunchKernelGGL(naf_reduce_kernel, dim3(nb((size_t)groups * c)), dim3(256), 0, st, F(tp.part), dst, groups, Gn, c, scale, dstride);
-    r.check();
+    launch(naf_reduce_kernel, dim3(nb((size_t)groups * c)), dim3(256), 0, d.part, dst, groups, Gn, c, scale, dstride);
   }
 
   // LayerNorm + FiLM backward: g += d x; the image's d (folded scale) and d shift rows into drows
-  void ln_bwd(const float* x, const float* d, const float* stats, const float* mulrow, float* g, int HW, int c, float* dmul, float* dadd) {
+  void ln_bwd(const float* x, const float* dy, const float* stats, const float* mulrow, float* g, int HW, int c, float* dmul, float* dadd) {
     const int M = tp.N * HW;
-    dot(d, x, stats, 2, HW, c, dmul, true, n->R);
-    dot(d, nullptr, nullptr, 0, HW, c, dadd, true, n->R);
-    hipLaunchKernelGGL(naf_ln_bwd_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, st, x, d, stats, mulrow, r.rstride, g, M, HW, c);
-    r.check();
+    dot(dy, x, stats, 2, HW, c, dmul, true, n->R);
+    dot(dy, nullptr, nullptr, 0, HW, c, dadd, true, n->R);
+    launch(naf_ln_bwd_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, x, dy, stats, mulrow, rstride, g, M, HW, c);
   }
 
   // g: d out on entry, d inp on return (in place); cur: the block's input
   void block_bwd(int bi, const float* cur, float* g, int h, int w) {
     const BlockL& b = n->blocks[bi];
-    const BlockSlots& s = tp.blk[bi];
+    const BlockDst& s = d.blk[bi];
     const int c = b.c, HW = h * w, M = tp.N * HW, ns = nstrips_of(HW);
     const size_t tot = (size_t)M * c;
-    const float* rw = r.rows + b.row_off;
+    const float* rw = rows + b.row_off;
     float *gt = F(tp.gt), *g2a = F(tp.g2a), *g2b = F(tp.g2b), *dr = F(tp.drows) + b.row_off;
     float* sm = F(tp.small);
     float *ds = sm, *pooled = sm + (size_t)tp.N * c, *dpool = sm + 2 * (size_t)tp.N * c;
     // out = y + conv5(g4) gamma
-    r.gemm(b.conv5, F(s.g4), gt, h, w, EPI_BIAS);
+    gemm(b.conv5, s.g4, gt, h, w, EPI_BIAS);
     dot(g, gt, nullptr, 1, HW, c, G(b.gamma), false, 0);
-    wgrad(b.conv5, F(s.g4), g, h, w, PRO_NONE, nullptr, nullptr, nullptr, 0, P(b.off_gamma));
-    r.gemm_l(n->tgemms[b.conv5], g, gt, h, w, EPI_BIAS, PRO_MUL, P(b.off_gamma), nullptr, 0);
-    hipLaunchKernelGGL(naf_gate_bwd_kernel, dim3(nb(tot)), dim3(256), 0, st, gt, F(s.p4), g2a, c, tot);
-    r.check();
-    wgrad(b.conv4, F(s.y), g2a, h, w, PRO_LN, F(s.st2), rw + 3 * c, rw + 2 * c, r.rstride);
-    r.gemm_l(n->tgemms[b.conv4], g2a, gt, h, w, EPI_BIAS);
-    ln_bwd(F(s.y), gt, F(s.st2), rw + 3 * c, g, HW, c, dr + 3 * c, dr + 2 * c);
+    wgrad(b.conv5, s.g4, g, h, w, PRO_NONE, nullptr, nullptr, nullptr, 0, P(b.off_gamma));
+    gemm_l(n->tgemms[b.conv5], g, gt, h, w, EPI_BIAS, PRO_MUL, P(b.off_gamma), nullptr, 0);
+    launch(naf_gate_bwd_kernel, dim3(nb(tot)), dim3(256), 0, gt, s.p4, g2a, c, tot);
+    wgrad(b.conv4, s.y, g2a, h, w, PRO_LN, s.st2, rw + 3 * c, rw + 2 * c, rstride);
+    gemm_l(n->tgemms[b.conv4], g2a, gt, h, w, EPI_BIAS);
+    ln_bwd(s.y, gt, s.st2, rw + 3 * c, g, HW, c, dr + 3 * c, dr + 2 * c);
     // y = inp + conv3(t2 sca) beta
-    r.gemm(b.conv3, F(s.t2), gt, h, w, EPI_BIAS, PRO_MUL, F(s.sca), nullptr, c);
+    gemm(b.conv3, s.t2, gt, h, w, EPI_BIAS, PRO_MUL, s.sca, nullptr, c);
     dot(g, gt, nullptr, 1, HW, c, G(b.beta), false, 0);
-    wgrad(b.conv3, F(s.t2), g, h, w, PRO_MUL, nullptr, F(s.sca), nullptr, c, P(b.off_beta));
-    r.gemm_l(n->tgemms[b.conv3], g, gt, h, w, EPI_BIAS, PRO_MUL, P(b.off_beta), nullptr, 0);
-    dot(gt, F(s.t2), nullptr, 1, HW, c, ds, true, c);
-    dot(F(s.t2), nullptr, nullptr, 0, HW, c, pooled, true, c, 1.f / (float)HW);
-    hipLaunchKernelGGL(naf_sca_bwd_w_kernel, dim3(nb((size_t)c * c)), dim3(256), 0, st, ds, pooled, G(b.scaw), G(b.scab), tp.N, c);
-    r.check();
-    hipLaunchKernelGGL(naf_sca_bwd_x_kernel, dim3(nb((size_t)tp.N * c)), dim3(256), 0, st, ds, P(b.off_scaw), dpool, tp.N, c, 1.f / (float)HW);
-    r.check();
-    hipLaunchKernelGGL(naf_dwgate_bwd_kernel, dim3(nb(tot)), dim3(256), 0, st, F(s.t1), P(b.off_dww), P(b.off_dwb), gt, F(s.sca), dpool, g2a, h, w, c, tot);
-    r.check();
-    hipLaunchKernelGGL(naf_dw_bwd_kernel, dim3((unsigned)ns, (unsigned)((2 * c + 63) / 64), (unsigned)tp.N), dim3(256), 0, st, F(s.t1), P(b.off_dww), g2a,
-                       g2b, F(tp.part), h, w, 2 * c, ns);
-    r.check();
-    hipLaunchKernelGGL(naf_dw_finish_kernel, dim3(nb((size_t)20 * c)), dim3(256), 0, st, F(tp.part), tp.N * ns, 2 * c, G(b.dww), G(b.dwb));
-    r.check();
-    wgrad(b.conv1, cur, g2b, h, w, PRO_LN, F(s.st1), rw + c, rw, r.rstride);
-    r.gemm_l(n->tgemms[b.conv1], g2b, gt, h, w, EPI_BIAS);
-    ln_bwd(cur, gt, F(s.st1), rw + c, g, HW, c, dr + c, dr);
+    wgrad(b.conv3, s.t2, g, h, w, PRO_MUL, nullptr, s.sca, nullptr, c, P(b.off_beta));
+    gemm_l(n->tgemms[b.conv3], g, gt, h, w, EPI_BIAS, PRO_MUL, P(b.off_beta), nullptr, 0);
+    dot(gt, s.t2, nullptr, 1, HW, c, ds, true, c);
+    dot(s.t2, nullptr, nullptr, 0, HW, c, pooled, true, c, 1.f / (float)HW);
+    launch(naf_sca_bwd_w_kernel, dim3(nb((size_t)c * c)), dim3(256), 0, ds, pooled, G(b.scaw), G(b.scab), tp.N, c);
+    launch(naf_sca_bwd_x_kernel, dim3(nb((size_t)tp.N * c)), dim3(256), 0, ds, P(b.off_scaw), dpool, tp.N, c, 1.f / (float)HW);
+    launch(naf_dwgate_bwd_kernel, dim3(nb(tot)), dim3(256), 0, s.t1, P(b.off_dww), P(b.off_dwb), gt, s.sca, dpool, g2a, h, w, c, tot);
+    launch(naf_dw_bwd_kernel, dim3((unsigned)ns, (unsigned)((2 * c + 63) / 64), (unsigned)tp.N), dim3(256), 0, s.t1, P(b.off_dww), g2a, g2b,
+           d.part, h, w, 2 * c, ns);
+    launch(naf_dw_finish_kernel, dim3(nb((size_t)20 * c)), dim3(256), 0, d.part, tp.N * ns, 2 * c, G(b.dww), G(b.dwb));
+    wgrad(b.conv1, cur, g2b, h, w, PRO_LN, s.st1, rw + c, rw, rstride);
+    gemm_l(n->tgemms[b.conv1], g2b, gt, h, w, EPI_BIAS);
+    ln_bwd(cur, gt, s.st1, rw + c, g, HW, c, dr + c, dr);
   }
 
   void chain_bwd(const std::vector<int>& list, const float* first, float* g, int h, int w) {
@@ -849,16 +794,13 @@ struct TrainRun {
     const int wd = n->wd, L = n->L;
     int h = tp.Hp, w = tp.Wp, c = wd;
     float *g = F(tp.gx), *gt = F(tp.gt), *gu = F(tp.gu);
-    const float* last = chain_out(n->dec[L - 1], F(tp.up[L - 1]));
-    wgrad(n->g_ending, last, F(tp.deps), h, w);
-    r.gemm_l(n->tgemms[n->g_ending], F(tp.deps), g, h, w, EPI_BIAS);
+    wgrad(n->g_ending, d.dec[L - 1], F(tp.deps), h, w);
+    gemm_l(n->tgemms[n->g_ending], F(tp.deps), g, h, w, EPI_BIAS);
     for (int i = L - 1; i >= 0; --i) {
-      chain_bwd(n->dec[i], F(tp.up[i]), g, h, w);
+      chain_bwd(n->dec[i], d.up[i], g, h, w);
       // ups[i]: g is d (shuffle(conv(x)) + skip).  The skip's share is g itself; the convolution's is a 2x2 stride-2 gather of g.
-      const size_t bytes = (size_t)tp.N * h * w * c * sizeof(float);
-      (void)hipMemcpyAsync(F(tp.dskip[L - 1 - i]), g, bytes, hipMemcpyDeviceToDevice, st);
-      r.check();
-      const float* x = i == 0 ? chain_out(n->mid, mid_in()) : chain_out(n->dec[i - 1], F(tp.up[i - 1]));
+      copy(F(tp.dskip[L - 1 - i]), g, (size_t)tp.N * h * w * c);
+      const float* x = i ? d.dec[i - 1] : d.mid;   // ups[i]'s forward input
       const GemmL& t = n->tgemms[n->ups[i]];
       const GemmL& gf = n->gemms[n->ups[i]];
       {
@@ -868,18 +810,16 @@ struct TrainRun {
         a.K = t.K(); a.Keff = a.K; a.ldy = t.cout;
         wgrad_launch(a, PRO_NONE, 1, 4, G(gf.w), nullptr);
       }
-      r.gemm_l(t, F(tp.dskip[L - 1 - i]), g, h, w, EPI_BIAS);
+      gemm_l(t, F(tp.dskip[L - 1 - i]), g, h, w, EPI_BIAS);
       h /= 2; w /= 2; c *= 2;
     }
-    chain_bwd(n->mid, mid_in(), g, h, w);
+    chain_bwd(n->mid, d.down[L - 1], g, h, w);
     for (int i = L - 1; i >= 0; --i) {
       // downs[i]: g is d out at level i + 1
-      const float* x = chain_out(n->enc[i], enc_in(i));
-      wgrad(n->downs[i], x, g, 2 * h, 2 * w);
-      r.gemm_l(n->tgemms[n->downs[i]], g, gt, h, w, EPI_PSHUF, PRO_NONE, nullptr, nullptr, 0, F(tp.dskip[i]));
+      wgrad(n->downs[i], d.skip[i], g, 2 * h, 2 * w);
+      gemm_l(n->tgemms[n->downs[i]], g, gt, h, w, EPI_PSHUF, PRO_NONE, nullptr, nullptr, 0, nullptr, F(tp.dskip[i]));
       h *= 2; w *= 2; c /= 2;
-      (void)hipMemcpyAsync(g, gt, (size_t)tp.N * h * w * c * sizeof(float), hipMemcpyDeviceToDevice, st);
-      r.check();
+      copy(g, gt, (size_t)tp.N * h * w * c);
       chain_bwd(n->enc[i], enc_in(i), g, h, w);
     }
     // enh = x0 + (r a + x0), a = CA(mean r)
@@ -888,46 +828,34 @@ struct TrainRun {
     float* sm = F(tp.small);
     float *da = sm, *dz2 = sm + (size_t)tp.N * wd, *pooled = sm + 2 * (size_t)tp.N * wd, *dpool = sm + 3 * (size_t)tp.N * wd,
           *dz1 = sm + 4 * (size_t)tp.N * wd, *hid = dz1 + (size_t)tp.N * cs;
-    dot(g, F(tp.r), nullptr, 1, HW, wd, da, true, wd);
-    hipLaunchKernelGGL(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)tp.N), dim3(256), 0, st, F(tp.r), F(tp.part), HW, wd, ns);
-    r.check();
-    hipLaunchKernelGGL(naf_ca_bwd_kernel, dim3((unsigned)tp.N), dim3(256), (3 * wd + 256 + 2 * cs) * sizeof(float), st, F(tp.part), ns, HW, P(n->off_ca1w),
-                       P(n->off_ca1b), P(n->off_ca2w), F(tp.ca), da, dz2, dz1, hid, pooled, dpool, wd, cs);
-    r.check();
-    hipLaunchKernelGGL(naf_linear_w_kernel, dim3(nb((size_t)wd * cs)), dim3(256), 0, st, dz2, hid, G(n->ca2w), G(n->ca2b), tp.N, wd, cs);
-    r.check();
-    hipLaunchKernelGGL(naf_linear_w_kernel, dim3(nb((size_t)wd * cs)), dim3(256), 0, st, dz1, pooled, G(n->ca1w), G(n->ca1b), tp.N, cs, wd);
-    r.check();
-    hipLaunchKernelGGL(naf_scale_add_kernel, dim3(nb(tot)), dim3(256), 0, st, g, F(tp.ca), dpool, gt, HW, wd, tot);
-    r.check();
-    wgrad(n->g_rcab2, F(tp.r1), gt, h, w);
-    r.gemm_l(n->tgemms[n->g_rcab2], gt, gu, h, w, EPI_BIAS);
-    hipLaunchKernelGGL(naf_relu_mask_kernel, dim3(nb(tot)), dim3(256), 0, st, gu, F(tp.r1), tot);
-    r.check();
-    wgrad(n->g_rcab0, F(tp.x0), gu, h, w);
-    r.gemm_l(n->tgemms[n->g_rcab0], gu, gt, h, w, EPI_BIAS);
-    hipLaunchKernelGGL(naf_twice_plus_kernel, dim3(nb(tot)), dim3(256), 0, st, g, gt, tot);
-    r.check();
-    wgrad(n->g_intro, F(tp.xin), g, h, w);
+    dot(g, d.r, nullptr, 1, HW, wd, da, true, wd);
+    launch(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)tp.N), dim3(256), 0, d.r, d.part, HW, wd, ns);
+    launch(naf_ca_bwd_kernel, dim3((unsigned)tp.N), dim3(256), (3 * wd + 256 + 2 * cs) * sizeof(float), d.part, ns, HW, P(n->off_ca1w),
+           P(n->off_ca1b), P(n->off_ca2w), d.ca, da, dz2, dz1, hid, pooled, dpool, wd, cs);
+    launch(naf_linear_w_kernel, dim3(nb((size_t)wd * cs)), dim3(256), 0, dz2, hid, G(n->ca2w), G(n->ca2b), tp.N, wd, cs);
+    launch(naf_linear_w_kernel, dim3(nb((size_t)wd * cs)), dim3(256), 0, dz1, pooled, G(n->ca1w), G(n->ca1b), tp.N, cs, wd);
+    launch(naf_scale_add_kernel, dim3(nb(tot)), dim3(256), 0, g, d.ca, dpool, gt, HW, wd, tot);
+    wgrad(n->g_rcab2, d.r1, gt, h, w);
+    gemm_l(n->tgemms[n->g_rcab2], gt, gu, h, w, EPI_BIAS);
+    launch(naf_relu_mask_kernel, dim3(nb(tot)), dim3(256), 0, gu, d.r1, tot);
+    wgrad(n->g_rcab0, d.intro, gu, h, w);
+    gemm_l(n->tgemms[n->g_rcab0], gu, gt, h, w, EPI_BIAS);
+    launch(naf_twice_plus_kernel, dim3(nb(tot)), dim3(256), 0, g, gt, tot);
+    wgrad(n->g_intro, d.xin, g, h, w);
   }
 
   // the rows back through every block's Linear, SimpleGate and time_mlp
   void time_bwd() {
     const int wd = n->wd, K2 = 2 * wd, R = n->R, N = tp.N;
-    hipLaunchKernelGGL(naf_rows_bwd_kernel, dim3(nb(R)), dim3(256), 0, st, F(tp.tg), P(n->off_rowsw), P(n->off_rowsb), P(n->off_rowsmul), n->d_rowmap,
-                       F(tp.drows), n->d_grad, N, K2, R);
-    r.check();
-    hipLaunchKernelGGL(naf_dtg_kernel, dim3((unsigned)K2, (unsigned)N), dim3(256), 0, st, F(tp.drows), P(n->off_rowsw), F(tp.dtg), K2, R);
-    r.check();
+    launch(naf_rows_bwd_kernel, dim3(nb(R)), dim3(256), 0, d.tg, P(n->off_rowsw), P(n->off_rowsb), P(n->off_rowsmul), n->d_rowmap, F(tp.drows),
+           n->d_grad, N, K2, R);
+    launch(naf_dtg_kernel, dim3((unsigned)K2, (unsigned)N), dim3(256), 0, F(tp.drows), P(n->off_rowsw), F(tp.dtg), K2, R);
     float* sm = F(tp.small);
     float *dh2 = sm, *g1 = sm + (size_t)N * 4 * wd, *dh1 = sm + (size_t)N * 8 * wd, *emb = sm + (size_t)N * 16 * wd;
-    hipLaunchKernelGGL(naf_time_bwd_kernel, dim3((unsigned)N), dim3(256), 21 * wd * sizeof(float), st, F(tp.tf), P(n->off_freq), P(n->off_t1w), P(n->off_t1b),
-                       P(n->off_t2w), P(n->off_t2b), F(tp.dtg), dh2, g1, dh1, emb, wd);
-    r.check();
-    hipLaunchKernelGGL(naf_linear_w_kernel, dim3(nb((size_t)16 * wd * wd)), dim3(256), 0, st, dh2, g1, G(n->t2w), G(n->t2b), N, 4 * wd, 4 * wd);
-    r.check();
-    hipLaunchKernelGGL(naf_linear_w_kernel, dim3(nb((size_t)8 * wd * wd)), dim3(256), 0, st, dh1, emb, G(n->t1w), G(n->t1b), N, 8 * wd, wd);
-    r.check();
+    launch(naf_time_bwd_kernel, dim3((unsigned)N), dim3(256), 21 * wd * sizeof(float), F(tp.tf), P(n->off_freq), P(n->off_t1w), P(n->off_t1b),
+           P(n->off_t2w), P(n->off_t2b), F(tp.dtg), dh2, g1, dh1, emb, wd);
+    launch(naf_linear_w_kernel, dim3(nb((size_t)16 * wd * wd)), dim3(256), 0, dh2, g1, G(n->t2w), G(n->t2b), N, 4 * wd, 4 * wd);
+    launch(naf_linear_w_kernel, dim3(nb((size_t)8 * wd * wd)), dim3(256), 0, dh1, emb, G(n->t1w), G(n->t1b), N, 8 * wd, wd);
   }
 };
 
@@ -956,7 +884,7 @@ int fdsr_nafnet_set_thetas_cumsum(fdsr_nafnet n, int T, const float* thetas_cums
 int fdsr_nafnet_train_workspace_bytes(fdsr_nafnet n, int batch, int height, int width, size_t* bytes) {
   if (!n || !bytes || batch < 1 || height < 1 || width < 1)
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_train_workspace_bytes: bad arguments (B %d, %dx%d)", batch, height, width);
-  *bytes = make_train_plan(n, batch, height, width).bytes;
+  *bytes = train_plan_bytes(n, batch, height, width);
   return FDSR_OK;
 }
 
@@ -968,48 +896,34 @@ int fdsr_nafnet_train_grads(fdsr_nafnet n, const float* state_nchw, const float*
     return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, batch, height, width);
   if (loss_type & FDSR_NAFNET_LOSS_WEIGHTED) return fail(nullptr, FDSR_E_INVALID, "%s: is_weighted is not supported (the reference passes no weights)", fn);
   if (loss_type != FDSR_NAFNET_LOSS_L1 && loss_type != FDSR_NAFNET_LOSS_L2) return fail(nullptr, FDSR_E_INVALID, "%s: loss_type %d (l1 = 0, l2 = 1)", fn, loss_type);
-  if ((size_t)batch * round_up(height, 1 << n->L) * round_up(width, 1 << n->L) * 2 * n->wd >= (1ull << 31) || batch > 65535)
-    return fail(nullptr, FDSR_E_INVALID, "%s: B %d at %dx%d exceeds the 32-bit pixel indexing of the kernels", fn, batch, height, width);
-  for (const WT& w : n->wts)
-    if (!w.loaded) return fail(nullptr, FDSR_E_STATE, "%s: tensor '%s' is missing", fn, w.key.c_str());
+  int rc = check_args(n, fn, batch, height, width, workspace, workspace_bytes, train_plan_bytes);
+  if (rc) return rc;
   if (n->prec != FDSR_PREC_F32)
     return fail(nullptr, FDSR_E_INVALID, "%s: training runs in FDSR_PREC_F32 only, the object is in f16x3 (fdsr_nafnet_set_precision)", fn);
   if (n->T < 1 || n->cum_T != n->T) return fail(nullptr, FDSR_E_STATE, "%s: no schedule (fdsr_nafnet_set_sde, fdsr_nafnet_set_thetas_cumsum)", fn);
-  const TrainPlan tp = make_train_plan(n, batch, height, width);
-  if (workspace_bytes < tp.bytes || (reinterpret_cast<uintptr_t>(workspace) & 255))
-    return fail(nullptr, FDSR_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes) or not 256-byte aligned", fn, workspace_bytes, tp.bytes);
-  int rc = finalize(n);
-  if (rc) return rc;
   if ((rc = ensure_train(n))) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  Plan pl{};
-  pl.N = batch; pl.H = height; pl.W = width; pl.Hp = tp.Hp; pl.Wp = tp.Wp;
-  TrainRun t{n, tp, Run{n, pl, static_cast<char*>(workspace), st, nullptr, n->R}, static_cast<char*>(workspace), st};
+  char* ws = static_cast<char*>(workspace);
+  const TrainPlan tp = make_train_plan(n, batch, height, width);
+  TrainRun t{{n, train_dst(n, tp, ws), st, nullptr, n->R}, tp, ws};
   HIPCHK(nullptr, hipMemsetAsync(n->d_grad, 0, n->P * sizeof(float), st));
   HIPCHK(nullptr, hipMemsetAsync(t.F(tp.deps), 0, (size_t)batch * tp.Hp * tp.Wp * 3 * sizeof(float), st));
-  hipLaunchKernelGGL(naf_i2f_kernel, dim3(TrainRun::nb(batch)), dim3(256), 0, st, timesteps_dev, t.F(tp.tf), batch);
-  t.r.check();
-  t.r.time_rows(t.F(tp.tf), batch, t.F(tp.tg), t.F(tp.trow));
-  t.r.rows = t.F(tp.trow);
-  {
-    const size_t total = (size_t)batch * tp.Hp * tp.Wp;
-    hipLaunchKernelGGL(naf_prep_kernel, dim3(TrainRun::nb(total)), dim3(256), 0, st, state_nchw, cond_nchw, t.F(tp.xin), height, width, tp.Hp, tp.Wp, total);
-    t.r.check();
-  }
-  t.net_fwd();
+  t.launch(naf_i2f_kernel, dim3(Run::nb(batch)), dim3(256), 0, timesteps_dev, t.F(tp.tf), batch);
+  t.time_rows(t.F(tp.tf), batch, t.d.tg, t.d.trow);
+  t.rows = t.d.trow;
+  t.prep(state_nchw, cond_nchw);
+  t.net();
   {
     LossTables tb{n->d_sde, n->d_sde + (n->T + 1), n->d_sde + 2 * (n->T + 1), n->d_cum, n->dt, n->T};
     const int HW = height * width, nblk = (HW + 1023) / 1024;
     const float gscale = weight / ((float)batch * 3.f * (float)HW);
-    hipLaunchKernelGGL(naf_loss_kernel, dim3((unsigned)nblk, (unsigned)batch), dim3(256), 0, st, t.F(tp.eps), state_nchw, cond_nchw, gt_nchw, timesteps_dev,
-                       tb, loss_type == FDSR_NAFNET_LOSS_L2 ? 1 : 0, gscale, t.F(tp.deps), t.F(tp.losspart), height, width, tp.Hp, tp.Wp);
-    t.r.check();
-    hipLaunchKernelGGL(naf_loss_finish_kernel, dim3(1), dim3(64), 0, st, t.F(tp.losspart), nblk, batch, 1.f / (3.f * (float)HW), weight, loss_out_dev);
-    t.r.check();
+    t.launch(naf_loss_kernel, dim3((unsigned)nblk, (unsigned)batch), dim3(256), 0, t.d.eps, state_nchw, cond_nchw, gt_nchw, timesteps_dev, tb,
+             loss_type == FDSR_NAFNET_LOSS_L2 ? 1 : 0, gscale, t.F(tp.deps), t.F(tp.losspart), height, width, tp.Hp, tp.Wp);
+    t.launch(naf_loss_finish_kernel, dim3(1), dim3(64), 0, t.F(tp.losspart), nblk, batch, 1.f / (3.f * (float)HW), weight, loss_out_dev);
   }
   t.net_bwd();
   t.time_bwd();
-  return t.r.err;
+  return t.err;
 }
 
 int fdsr_nafnet_grad_buffer(fdsr_nafnet n, float** device_ptr, size_t* count) {
@@ -1045,9 +959,9 @@ int fdsr_nafnet_optim_step(fdsr_nafnet n, int kind, double lr, double beta1, dou
   const double bc1 = 1.0 - std::pow(beta1, (double)n->opt_step), bc2 = 1.0 - std::pow(beta2, (double)n->opt_step);
   o.step_size = (float)(lr / bc1);
   o.bc2_sqrt = (float)std::sqrt(bc2);
-  hipLaunchKernelGGL(naf_optim_kernel, dim3(TrainRun::nb(n->P)), dim3(256), 0, st, n->d_master, n->d_grad, n->d_m, n->d_v, o, n->P);
+  hipLaunchKernelGGL(naf_optim_kernel, dim3(Run::nb(n->P)), dim3(256), 0, st, n->d_master, n->d_grad, n->d_m, n->d_v, o, n->P);
   HIPCHK(nullptr, hipGetLastError());
-  hipLaunchKernelGGL(naf_repack_kernel, dim3(TrainRun::nb(n->arena_floats)), dim3(256), 0, st, n->d_arena, n->d_master, n->d_map, n->arena_floats);
+  hipLaunchKernelGGL(naf_repack_kernel, dim3(Run::nb(n->arena_floats)), dim3(256), 0, st, n->d_arena, n->d_master, n->d_map, n->arena_floats);
   HIPCHK(nullptr, hipGetLastError());
   n->host_stale = true;
   n->table_valid = false;

@@ -180,3 +180,42 @@ def test_abi_refusals_without_a_gpu():
         assert lib.fdsr_upscale_bicubic_f32(fake, fake, 1, 3, 8, 8, 0, None) == FDSR_E_INVALID
     finally:
         lib.fdsr_nafnet_destroy(h)
+
+
+EMPTY_SETTING = dict(width=16, enc_blk_nums=[1, 0], middle_blk_num=0, dec_blk_nums=[0, 1])      # empty encoder, middle and decoder lists
+# (setting, (B, H, W)): (fdsr_nafnet_workspace_bytes, fdsr_nafnet_train_workspace_bytes), recorded from the library before the
+# sampling and the training forward became one walk over two destination tables: the plans' offsets and totals did not move
+WORKSPACE_BYTES = {
+    ('test', (1, 33, 33)): (1129728, 8948224),
+    ('test', (2, 48, 48)): (2258944, 17235712),
+    ('test', (3, 36, 44)): (3388416, 25525248),
+    ('test', (16, 256, 256)): (507984896, 3779138816),
+    ('shipped', (1, 33, 33)): (4225792, 98427392),
+    ('shipped', (2, 48, 48)): (8451584, 187938816),
+    ('shipped', (3, 36, 44)): (12677376, 277451264),
+    ('shipped', (16, 256, 256)): (1893724160, 40736108800),
+    ('empty', (1, 33, 33)): (598272, 2733568),
+    ('empty', (2, 48, 48)): (2123008, 9616384),
+    ('empty', (3, 36, 44)): (2190848, 9919744),
+    ('empty', (16, 256, 256)): (482622464, 2177958144),
+}
+
+
+def test_workspace_sizes_are_pinned():
+    lib, L = _lib()
+    settings = {'test': TEST_SETTING, 'shipped': SHIPPED_SETTING, 'empty': EMPTY_SETTING}
+    for (name, shape), want in WORKSPACE_BYTES.items():
+        s = settings[name]
+        c = L.FdsrNafnetConfig()
+        c.img_channel, c.width, c.n_levels, c.middle_blk_num = 3, s['width'], len(s['enc_blk_nums']), s['middle_blk_num']
+        for i, (e, d) in enumerate(zip(s['enc_blk_nums'], s['dec_blk_nums'])):
+            c.enc_blk_nums[i], c.dec_blk_nums[i] = e, d
+        h = C.c_void_p()
+        assert lib.fdsr_nafnet_create(C.byref(c), C.byref(h)) == 0
+        try:
+            fwd, train = C.c_size_t(), C.c_size_t()
+            assert lib.fdsr_nafnet_workspace_bytes(h, *shape, C.byref(fwd)) == 0
+            assert lib.fdsr_nafnet_train_workspace_bytes(h, *shape, C.byref(train)) == 0
+            assert (fwd.value, train.value) == want, (name, shape)
+        finally:
+            lib.fdsr_nafnet_destroy(h)

@@ -181,6 +181,53 @@ def test_properties_bitwise(net):
     assert not torch.equal(drawn, m.sample(state, cond, noise=None, seed=seed + 1))
 
 
+# Empty block lists: encoder level 1, the middle and decoder step 0 have no block, so each of the walk's copy rules runs (the skip
+# of level 1, the middle's and the decoder step's result are wanted somewhere their chain did not end).  18 x 26 pads to 20 x 28.
+EMPTY_SETTING = dict(width=16, enc_blk_nums=[1, 0], middle_blk_num=0, dec_blk_nums=[0, 1])
+
+
+@pytest.fixture(scope='module')
+def empty_net():
+    return _model(EMPTY_SETTING)
+
+
+def test_empty_block_lists_layerwise_and_forward(empty_net):
+    from fastdiffsr_amd.ediffsr.arch import tap_names
+    m, sd = empty_net
+    assert len(sd) == 58 and len(tap_names(m.cfg)) == 9
+    x, cond = _inputs(24, 2, 18, 26)
+    t32, t64 = {}, {}
+    with torch.no_grad():
+        y32 = R.forward(sd, x, cond, 37, t32)
+        y64 = R.forward(R.cast_sd(sd, torch.float64), x.double(), cond.double(), 37, t64)
+    fails = [name for name in tap_names(m.cfg)
+             if not _judge(name, m.debug_tensor(name, x.to(DEV), cond.to(DEV), 37), t64[name], t32[name])[0]]
+    ok, _ = _judge('output', m(x.to(DEV), cond.to(DEV), 37), y64, y32)
+    assert ok and not fails, fails
+
+
+def test_empty_block_lists_graph_equals_eager(empty_net):
+    from fastdiffsr_amd.ediffsr.sde import IRSDE
+    m, sd = empty_net
+    T, hw = 4, (18, 26)
+    s = IRSDE(max_sigma=50, T=T, schedule='cosine', eps=0.5, device='cpu')
+    s.set_model(m)
+    state, cond = _inputs(43, 2, *hw)
+    noise = torch.randn(T, 2, 3, *hw, generator=torch.Generator().manual_seed(44))
+    state, cond, noise = state.to(DEV), cond.to(DEV), noise.to(DEV)
+    outs = {}
+    for ode in (False, True):
+        a, ta = m.sample(state, cond, noise=noise, ode=ode, trajectory=True)
+        b, tb = m.sample(state, cond, noise=noise, ode=ode, trajectory=True)
+        assert torch.isfinite(a).all()
+        assert torch.equal(a, b) and torch.equal(ta, tb), 'rerun'
+        g, tg = m.sample(state, cond, noise=noise, ode=ode, trajectory=True, graph=True)
+        assert torch.equal(a, g) and torch.equal(ta, tg), 'graph == eager'
+        assert torch.equal(a, m.sample(state, cond, noise=noise, ode=ode, graph=True)), 'graph replay'
+        outs[ode] = a
+    assert not torch.equal(outs[False], outs[True])
+
+
 @pytest.mark.parametrize('scale,hw', [(4, (9, 7)), (8, (5, 11)), (4, (64, 64))])
 def test_upscale_bicubic(scale, hw):
     from fastdiffsr_amd.ediffsr.model import upscale

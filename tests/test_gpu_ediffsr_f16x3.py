@@ -61,6 +61,22 @@ def test_layerwise_and_forward(net, hw):
     assert ok and not fails, fails
 
 
+def test_empty_block_lists_layerwise_and_forward():
+    """the setting of test_gpu_ediffsr.py whose empty block lists make the walk copy"""
+    from fastdiffsr_amd.ediffsr.arch import tap_names
+    from test_gpu_ediffsr import EMPTY_SETTING
+    m, sd = _model(EMPTY_SETTING)
+    m.set_precision('f16x3')
+    x, cond = _inputs(24, 2, 18, 26)
+    (y32, y64, yem), (t32, t64, tem) = _three(sd, x, cond, 37, taps=True)
+    assert len(tap_names(m.cfg)) == 9
+    fails = [name for name in tap_names(m.cfg)
+             if not _judge(name, m.debug_tensor(name, x.to(DEV), cond.to(DEV), 37), t64[name], t32[name], tem[name])]
+    ok = _judge('output', m(x.to(DEV), cond.to(DEV), 37), y64, y32, yem)
+    m.check_saturation()
+    assert ok and not fails, fails
+
+
 def test_forward_per_image_float_times(net):
     m, sd = net
     x, cond = _inputs(22, 3, 36, 44)

@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 
 TEST_SETTING = dict(width=16, enc_blk_nums=[2, 1, 1, 1], middle_blk_num=1, dec_blk_nums=[1, 1, 1, 1])
 SHIPPED_SETTING = dict(width=64, enc_blk_nums=[14, 1, 1, 1], middle_blk_num=1, dec_blk_nums=[1, 1, 1, 1])
+EMPTY_SETTING = dict(width=16, enc_blk_nums=[1, 0], middle_blk_num=0, dec_blk_nums=[0, 1])
 DEV = 'cuda'
 SDE = dict(max_sigma=50, T=100, schedule='cosine', eps=0.005)
 
@@ -77,6 +78,7 @@ CASES = {
     'b': (TEST_SETTING, 3, 32, 32, [7, 50, 93], 'l2'),
     'c': (TEST_SETTING, 2, 64, 64, [23, 71], 'l1'),
     'd': (SHIPPED_SETTING, 2, 32, 32, [12, 88], 'l1'),
+    'e': (EMPTY_SETTING, 2, 18, 26, [3, 64], 'l1'),      # empty block lists; pads to 20 x 28
 }
 
 
