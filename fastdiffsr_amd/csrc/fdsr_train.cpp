@@ -8,7 +8,7 @@
 // a = swish(gn(x)) or a = x, x = cat(x0, x1):
 //   * d res  += dy                                  (identity residual; a 1x1 res_conv shares the buffer)
 //   * S[n][c] = sum_p dy                            -> bias gradient, and the noise-embedding gradient of the block
-//   * dW      = wgrad(dy, a)                        (fdsr_train.hip, exact fp32 MFMA)
+//   * dW      = wgrad(dy, a)                        (fdsr_wgrad.hip, exact fp32 MFMA)
 //   * dA      = conv(dy; W transposed, taps flipped) on the FORWARD kernel (stride 2: zero-inserted dy;
 //               upsample: 2x2 sum-pool afterwards)
 //   * dx0/dx1 += GroupNorm+Swish backward(dA)       or += dA where the conv reads its input raw

@@ -1,4 +1,4 @@
-// Launch interfaces of the training-step kernels (fdsr_train.hip): the backward pass of the FastDiffSR UNet,
+// Launch interfaces of the training-step kernels (fdsr_train.hip, fdsr_wgrad.hip): the backward pass of the FastDiffSR UNet,
 // the loss, Adam and the device-side re-packing of updated weights.  Internal header (not the C ABI).
 //
 // Reference: DDPM.optimize_parameters (model/model.py:47-57) = zero_grad, l_pix = netG(data) (p_losses,
@@ -84,6 +84,7 @@ hipError_t launch_gn_bwd(const GnBwdParams& p, hipStream_t s);
 // dW[co][ci][tap] = sum_{n,p} dy[n][p][co] * a[n][p (+) tap][ci], a = the conv's (virtually concatenated,
 // optionally GroupNorm+Swish-activated, optionally nearest-x2 upsampled) input exactly as the forward staged it.
 // Exact fp32 on v_mfma_f32_32x32x2_f32; the pixel range is split over workgroups, slices are summed in order.
+// Kernels, slice plan, scratch sizing and launchers: fdsr_wgrad.hip.
 struct WgradParams {
   const float* dy;                 // [N][Hout][Wout][Cout_s]  (Cout_s = channel stride of dy, >= Cout)
   const float* x0; const float* x1;
@@ -99,13 +100,16 @@ struct WgradParams {
   float* colsum;                   // launch_wgrad_h only, when wgrad_h_fuses_colsum(): S [N][Cout_s] = per-image column sums of dy
   float* colsum_part;              // (set by the launcher: per-slice partial sums in the scratch)
 };
+// room for every form a layer of this geometry may run in (either precision, every debug option); from the launchers' slice plan
 size_t wgrad_scratch_floats(ConvKind kind, int N, int Hout, int Wout, int Cin, int Cout);
+// what a launch of that layer writes to the scratch under the options in force (host tests hold it against the bound above)
+size_t wgrad_launch_floats(ConvKind kind, int N, int Hout, int Wout, int Cin, int Cout, bool gn_plain, bool f16x3);
 // true when launch_wgrad_h(kind, p) will also write p.colsum (the bias / noise-shift gradient sums launch_colsum computes)
 bool wgrad_h_fuses_colsum(ConvKind kind, const WgradParams& p);
 hipError_t launch_wgrad(ConvKind kind, const WgradParams& p, hipStream_t s);
 // the same in the split-f16 form (three f16 MFMAs per product, fp32 accumulate): FDSR_PREC_F16X3 training steps
 hipError_t launch_wgrad_h(ConvKind kind, const WgradParams& p, hipStream_t s);
-hipError_t train_kernels_init();
+hipError_t train_kernels_init();   // raises the weight-gradient kernels' dynamic-LDS limits
 
 // ---- CLAM / SLAM backward (unet.py:123-173) -----------------------------------------------------------------
 // forward: gate = sigmoid(fc2 relu(fc1 avg) + fc2 relu(fc1 max)), y = x*gate, m = [mean_c y, max_c y],
