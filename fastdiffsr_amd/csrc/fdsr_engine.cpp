@@ -438,11 +438,10 @@ int run_unet(fdsr_handle h, int N, int H, int W, char* ws, const float* nl_dev, 
           p.Cin_pad = w.h_cin_pad;
           p.Cout_pad = w.h_cout_pad;
           if (prec_wform(h->prec) == PREC_F16X3) p.w_inv_scale_dev = h->d_hscale + 2 * (size_t)op.w + 1;
-          const bool no_up2 = !g_tun.up2;
-          // (after optimiser steps the sub-pixel forms lag until fdsr_sync_weight_forms: training forwards use the generic kernel)
-          const bool up2_dev = prec_wform(h->prec) == PREC_F16X3 && h->up2_dev_fresh;   // re-packed on the device by the last optimiser step
-          if (op.ck == CONV3_UP && !no_up2 && !op.force_generic && (!h->h_forms_stale || up2_dev)) {
-            p.w_inv_scale_dev = up2_dev ? h->d_up2_inv + op.w : nullptr;
+          // (a sub-pixel form that lags, or has two scale sources after a single-tensor load: the generic kernel)
+          const fdsr_forms::Up2 up2 = fdsr_forms::up2_form(h->forms, h->prec);
+          if (op.ck == CONV3_UP && g_tun.up2 && !op.force_generic && up2 != fdsr_forms::UP2_GENERIC) {
+            p.w_inv_scale_dev = up2 == fdsr_forms::UP2_DEVICE_SCALE ? h->d_up2_inv + op.w : nullptr;
             p.wq = h->d_wq + w.up2_off[prec_wform(h->prec)];
             p.w_inv_scale = w.up2_inv_scale[prec_wform(h->prec)];
             if (gsum_on && p.part_out && GSUM(op.dst) && conv_h_gsum_ok(CONV3_UP, h->prec, p, true)) {
@@ -516,126 +515,6 @@ int run_unet(fdsr_handle h, int N, int H, int W, char* ws, const float* nl_dev, 
   return FDSR_OK;
 }
 
-inline uint16_t f32_to_bf16_rn(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-inline uint16_t f32_to_f16_rn(float f) {
-  _Float16 hv = (_Float16)f;
-  uint16_t b;
-  memcpy(&b, &hv, 2);
-  return b;
-}
-
-// Repack a Conv2d weight [Cout][Cin][ks][ks] into MFMA B-fragment order for the 16-bit kernels:
-// [cot][kc][wn][tap][plane][lane] x 8 halves, element j of lane l = W[co = cot*BN + wn*32 + (l&31)]
-// [k = kc*16 + 8*(l>>5) + j][tap]   (v_mfma_f32_32x32x16 B operand map).
-// f16x3: plane 0 = hi = f16(w*s), plane 1 = lo = f16(w*s - hi), s = 2^e chosen so that max|w*s| < 2^15
-// (keeps lo out of the f16 subnormal range for all but tiny weights); bf16: one plane, s = 1.
-int pack_weights_h(fdsr_handle h, WeightEntry& w, const float* host) {
-  const int Cout = (int)w.shape[0], Cin = (int)w.shape[1], ks = w.ks, T = ks * ks;
-  const int WN = w.h_WN, BN = 32 * WN, ncot = w.h_cout_pad / BN, nk = w.h_cin_pad / 16;
-  float amax = 0.f;
-  for (size_t i = 0; i < numel(w.shape); ++i) amax = std::max(amax, std::fabs(host[i]));
-  int e = 12;
-  if (amax > 0.f) e = std::min(12, (int)std::floor(std::log2(32768.0 / (double)amax)));
-  const float scale = std::ldexp(1.0f, e);
-  w.h_inv_scale[PREC_F16X3] = std::ldexp(1.0f, -e);
-  w.h_inv_scale[PREC_BF16] = 1.0f;
-  const size_t nfrag = (size_t)ncot * nk * WN * T * 64;   // 16-byte fragments per plane set
-  std::vector<uint16_t> q3(nfrag * 2 * 8, 0), qb(nfrag * 8, 0);
-  for (int cot = 0; cot < ncot; ++cot)
-    for (int kc = 0; kc < nk; ++kc)
-      for (int wn = 0; wn < WN; ++wn)
-        for (int t = 0; t < T; ++t)
-          for (int l = 0; l < 64; ++l) {
-            const int co = cot * BN + wn * 32 + (l & 31);
-            const size_t f3 = (((((size_t)cot * nk + kc) * WN + wn) * T + t) * 2) * 64 + l;
-            const size_t fb = (((((size_t)cot * nk + kc) * WN + wn) * T + t) * 1) * 64 + l;
-            for (int j = 0; j < 8; ++j) {
-              const int k = kc * 16 + 8 * (l >> 5) + j;
-              float v = 0.f;
-              if (co < Cout && k < Cin) v = host[((size_t)co * Cin + k) * T + t];
-              const float vs = v * scale;
-              const uint16_t hi = f32_to_f16_rn(vs);
-              _Float16 hif;
-              memcpy(&hif, &hi, 2);
-              const uint16_t lo = f32_to_f16_rn(vs - (float)hif);
-              q3[f3 * 8 + j] = hi;
-              q3[(f3 + 64) * 8 + j] = lo;
-              qb[fb * 8 + j] = f32_to_bf16_rn(v);
-            }
-          }
-  {
-    const float sc2[2] = {scale, w.h_inv_scale[PREC_F16X3]};
-    const size_t widx = (size_t)(&w - h->weights.data());
-    HIPCHK(h, hipMemcpy(h->d_hscale + 2 * widx, sc2, sizeof sc2, hipMemcpyHostToDevice));
-  }
-  HIPCHK(h, hipMemcpy(h->d_wq + w.hq_off[PREC_F16X3], q3.data(), q3.size() * 2, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(h->d_wq + w.hq_off[PREC_BF16], qb.data(), qb.size() * 2, hipMemcpyHostToDevice));
-  if (w.ck != CONV3_UP) return FDSR_OK;
-
-  // Sub-pixel form of Upsample(nearest x2)+Conv3x3 (unet.py:66-74): W2[py][px][a][b] = sum of the 3x3 taps
-  // that land on source offset (a, b) for output parity (py, px); R(0,0)={0} R(0,1)={1,2} R(1,0)={0,1} R(1,1)={2}.
-  auto tapset = [](int par, int a, int* lo, int* hi) {
-    if (par == 0) { if (a == 0) { *lo = 0; *hi = 0; } else { *lo = 1; *hi = 2; } }
-    else          { if (a == 0) { *lo = 0; *hi = 1; } else { *lo = 2; *hi = 2; } }
-  };
-  std::vector<float> w2((size_t)Cout * Cin * 16, 0.f);   // [co][ci][py][px][a][b]
-  float amax2 = 0.f;
-  for (int co = 0; co < Cout; ++co)
-    for (int ci = 0; ci < Cin; ++ci)
-      for (int py = 0; py < 2; ++py)
-        for (int px = 0; px < 2; ++px)
-          for (int a = 0; a < 2; ++a)
-            for (int b = 0; b < 2; ++b) {
-              int y0, y1, x0, x1;
-              tapset(py, a, &y0, &y1);
-              tapset(px, b, &x0, &x1);
-              float acc = 0.f;
-              for (int ky = y0; ky <= y1; ++ky)
-                for (int kx = x0; kx <= x1; ++kx) acc += host[((size_t)co * Cin + ci) * 9 + ky * 3 + kx];
-              w2[((size_t)co * Cin + ci) * 16 + ((py * 2 + px) * 2 + a) * 2 + b] = acc;
-              amax2 = std::max(amax2, std::fabs(acc));
-            }
-  int e2 = 12;
-  if (amax2 > 0.f) e2 = std::min(12, (int)std::floor(std::log2(32768.0 / (double)amax2)));
-  const float scale2 = std::ldexp(1.0f, e2);
-  w.up2_inv_scale[PREC_F16X3] = std::ldexp(1.0f, -e2);
-  w.up2_inv_scale[PREC_BF16] = 1.0f;
-  const size_t nfrag2 = (size_t)ncot * nk * WN * 16 * 64;
-  std::vector<uint16_t> u3(nfrag2 * 2 * 8, 0), ub(nfrag2 * 8, 0);
-  for (int cot = 0; cot < ncot; ++cot)
-    for (int kc = 0; kc < nk; ++kc)
-      for (int wn = 0; wn < WN; ++wn)
-        for (int py = 0; py < 2; ++py)
-          for (int slot = 0; slot < 8; ++slot)
-            for (int l = 0; l < 64; ++l) {
-              const int px = slot >> 2, a = (slot >> 1) & 1, b = slot & 1;
-              const int co = cot * BN + wn * 32 + (l & 31);
-              const size_t fidx = ((((size_t)cot * nk + kc) * WN + wn) * 2 + py) * 8 + slot;
-              for (int j = 0; j < 8; ++j) {
-                const int k = kc * 16 + 8 * (l >> 5) + j;
-                float v = 0.f;
-                if (co < Cout && k < Cin) v = w2[((size_t)co * Cin + k) * 16 + ((py * 2 + px) * 2 + a) * 2 + b];
-                const float vs = v * scale2;
-                const uint16_t hi = f32_to_f16_rn(vs);
-                _Float16 hif;
-                memcpy(&hif, &hi, 2);
-                u3[((fidx * 2 + 0) * 64 + l) * 8 + j] = hi;
-                u3[((fidx * 2 + 1) * 64 + l) * 8 + j] = f32_to_f16_rn(vs - (float)hif);
-                ub[(fidx * 64 + l) * 8 + j] = f32_to_bf16_rn(v);
-              }
-            }
-  HIPCHK(h, hipMemcpy(h->d_wq + w.up2_off[PREC_F16X3], u3.data(), u3.size() * 2, hipMemcpyHostToDevice));
-  HIPCHK(h, hipMemcpy(h->d_wq + w.up2_off[PREC_BF16], ub.data(), ub.size() * 2, hipMemcpyHostToDevice));
-  return FDSR_OK;
-}
-
 int fill_temb(fdsr_handle h, float* temb, int N, const float* nl_dev, float nl_scalar, hipStream_t st) {
   auto P = [&](int widx) -> const float* { return widx >= 0 ? h->d_params + h->weights[widx].dev_off : nullptr; };
   TembParams tp;
@@ -661,8 +540,7 @@ int fill_temb(fdsr_handle h, float* temb, int N, const float* nl_dev, float nl_s
 
 // Row t of the table is what the per-step kernel would produce for noise level t: same kernel,
 // same arithmetic, evaluated for all T levels in one launch.
-int ensure_temb_table(fdsr_handle h, hipStream_t st) {
-  if (h->temb_table_valid) return FDSR_OK;
+int build_temb_table(fdsr_handle h, hipStream_t st) {
   if (h->d_temb_table) { (void)hipFree(h->d_temb_table); h->d_temb_table = nullptr; }
   if (h->d_nl) { (void)hipFree(h->d_nl); h->d_nl = nullptr; }
   HIPCHK(h, hipMalloc(&h->d_temb_table, (size_t)h->T * h->TE * sizeof(float)));
@@ -673,7 +551,6 @@ int ensure_temb_table(fdsr_handle h, hipStream_t st) {
   int rc = fill_temb(h, h->d_temb_table, h->T, h->d_nl, 0.f, st);
   if (rc) return rc;
   HIPCHK(h, hipStreamSynchronize(st));
-  h->temb_table_valid = true;
   return FDSR_OK;
 }
 
@@ -756,23 +633,30 @@ void drop_step_graphs(fdsr_handle h) {
   h->step_graphs.clear();
 }
 
+void drop_sample_graphs(fdsr_handle h) {
+  for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
+  h->graphs.clear();
+}
+
+void drop_captures(fdsr_handle h) {
+  drop_sample_graphs(h);
+  drop_step_graphs(h);
+}
+
 StepRecord* step_rec(fdsr_handle h) { return reinterpret_cast<StepRecord*>(reinterpret_cast<char*>(h->d_step_ctl) + 256); }
 
-int ensure_step_state(fdsr_handle h) {
+int upload_step_sched(fdsr_handle h) {
   if (!h->d_step_ctl) {
     HIPCHK(h, hipMalloc(&h->d_step_ctl, 256 + sizeof(StepRecord)));
     HIPCHK(h, hipMemset(h->d_step_ctl, 0, 256 + sizeof(StepRecord)));
     HIPCHK(h, hipMalloc(&h->d_step_row, (size_t)h->TE * sizeof(float)));
   }
-  if (h->step_sched_valid && h->step_sched_T == h->T) return FDSR_OK;
   if (h->d_step_sched) { (void)hipFree(h->d_step_sched); h->d_step_sched = nullptr; }
   HIPCHK(h, hipMalloc(&h->d_step_sched, (size_t)5 * h->T * sizeof(float)));
   std::vector<float> s;
   s.reserve((size_t)5 * h->T);
   for (const auto* v : {&h->s_recip, &h->s_recipm1, &h->s_c1, &h->s_c2, &h->s_sigma}) s.insert(s.end(), v->begin(), v->end());
   HIPCHK(h, hipMemcpy(h->d_step_sched, s.data(), s.size() * sizeof(float), hipMemcpyHostToDevice));
-  h->step_sched_T = h->T;
-  h->step_sched_valid = true;
   return FDSR_OK;
 }
 
@@ -861,8 +745,7 @@ int fdsr_create(const fdsr_config* cfg, fdsr_handle* out) {
 
 void fdsr_destroy(fdsr_handle h) {
   if (!h) return;
-  for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
-  drop_step_graphs(h);
+  drop_captures(h);
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
   if (h->d_params) (void)hipFree(h->d_params);
   if (h->d_wq) (void)hipFree(h->d_wq);
@@ -911,31 +794,10 @@ int fdsr_load_weight(fdsr_handle h, const char* key, const float* host, const in
   if (!w.live) { w.loaded = true; return FDSR_OK; }   // never executed (unet.py:212): schema only
   int rc = ensure_device(h);
   if (rc) return rc;
-  float* dst = h->d_params + w.dev_off;
   HIPCHK(h, hipMemcpy(h->d_master + h->master_off[it->second], host, numel(w.shape) * sizeof(float), hipMemcpyHostToDevice));
-  if (w.sink == WeightEntry::CONV_PACK) {
-    const int Cout = (int)w.shape[0], Cin = (int)w.shape[1], ks = w.ks;
-    std::vector<float> pk((size_t)ks * ks * w.cout_pad * w.cin_pad, 0.f);
-    for (int co = 0; co < Cout; ++co)
-      for (int ci = 0; ci < Cin; ++ci)
-        for (int t = 0; t < ks * ks; ++t)
-          pk[((size_t)t * w.cout_pad + co) * w.cin_pad + ci] = host[((size_t)co * Cin + ci) * ks * ks + t];
-    HIPCHK(h, hipMemcpy(dst, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (w.h_ok) {
-      int rc2 = pack_weights_h(h, w, host);
-      if (rc2) return rc2;
-    }
-  } else {
-    HIPCHK(h, hipMemcpy(dst, host, numel(w.shape) * sizeof(float), hipMemcpyHostToDevice));
-  }
+  if ((rc = pack_weight_host(h, w, host))) return rc;
   w.loaded = true;
-  h->wt_valid = false;
-  h->up2_dev_fresh = false;   // this tensor's sub-pixel form is host-packed again (own scale)
-  h->temb_table_valid = false;
-  for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);   // weights are baked by address only, but be safe
-  h->graphs.clear();
-  drop_step_graphs(h);
-  return FDSR_OK;
+  return apply_plan(h, fdsr_forms::on_load(h->forms), nullptr);
 }
 
 int fdsr_weights_complete(fdsr_handle h) {
@@ -952,12 +814,7 @@ int fdsr_set_schedule(fdsr_handle h, const fdsr_schedule* s) {
   auto cp = [&](std::vector<float>& v, const float* p) { v.assign(p, p + s->n_timestep); };
   cp(h->s_nl, s->noise_level); cp(h->s_recip, s->sqrt_recip); cp(h->s_recipm1, s->sqrt_recipm1);
   cp(h->s_c1, s->coef1); cp(h->s_c2, s->coef2); cp(h->s_sigma, s->sigma);
-  h->temb_table_valid = false;
-  h->step_sched_valid = false;
-  for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
-  h->graphs.clear();
-  drop_step_graphs(h);
-  return FDSR_OK;
+  return apply_plan(h, fdsr_forms::on_schedule(h->forms), nullptr);
 }
 
 int fdsr_workspace_bytes(fdsr_handle h, int batch, int height, int width, size_t* bytes) {
@@ -979,7 +836,7 @@ int fdsr_unet_forward(fdsr_handle h, const float* x_nchw, const float* noise_lev
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   char* ws = reinterpret_cast<char*>(workspace);
   float* xin = reinterpret_cast<float*>(ws + h->plan.tensor_off[h->t_in]);
-  if (h->prec != PREC_F32 && h->h_forms_stale && !h->training && (rc = fdsr_sync_weight_forms(h))) return rc;
+  if ((rc = apply_plan(h, fdsr_forms::need_forward(h->forms, h->prec, h->training), st))) return rc;
   if (h->prec == PREC_F16X3 && g_tun.sat_guard) HIPCHK(h, hipMemsetAsync(h->d_sat, 0, sizeof(int), st));
   HIPCHK(h, launch_nchw_to_nhwc(x_nchw, xin, batch, h->cfg.in_channel, height, width, h->CP, 0, 1, st));
   if ((rc = run_unet(h, batch, height, width, ws, noise_level, 0.f, st))) return rc;
@@ -999,17 +856,15 @@ int fdsr_sample(fdsr_handle h, const float* cond_nchw, const float* noise, float
   if ((rc = check_ws(h, workspace, workspace_bytes))) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   char* ws = reinterpret_cast<char*>(workspace);
-  if ((rc = ensure_temb_table(h, st))) return rc;
+  if ((rc = apply_plan(h, fdsr_forms::need_sample(h->forms, h->prec, false), st))) return rc;   // optimiser steps moved the master copy
   if (!noise && (rc = ensure_rng(h))) return rc;
-  if (h->prec != PREC_F32 && h->h_forms_stale && (rc = fdsr_sync_weight_forms(h))) return rc;   // optimiser steps moved the master copy
   if ((flags & FDSR_SAMPLE_GRAPH) && st == nullptr)
     return fail(h, FDSR_E_INVALID, "FDSR_SAMPLE_GRAPH needs a non-default stream (stream capture cannot run on the NULL stream)");
   const bool use_graph = (flags & FDSR_SAMPLE_GRAPH) && !h->profiling;
   if (!use_graph) return sample_body(h, cond_nchw, noise, out_nchw, traj_nchw, batch, height, width, ws, st);
 
   if (h->graphs_epoch != g_tun.epoch) {   // graphs captured under other launcher options
-    for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
-    h->graphs.clear();
+    drop_sample_graphs(h);
     h->graphs_epoch = g_tun.epoch;
   }
   for (auto& g : h->graphs)
@@ -1051,9 +906,7 @@ int fdsr_sample_stepwise(fdsr_handle h, const float* cond_nchw, const float* noi
   if ((rc = check_ws(h, workspace, workspace_bytes))) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   char* ws = reinterpret_cast<char*>(workspace);
-  if (h->prec != PREC_F32 && h->h_forms_stale && (rc = fdsr_sync_weight_forms(h))) return rc;
-  if ((rc = ensure_temb_table(h, st))) return rc;
-  if ((rc = ensure_step_state(h))) return rc;
+  if ((rc = apply_plan(h, fdsr_forms::need_sample(h->forms, h->prec, true), st))) return rc;
   if (!noise && (rc = ensure_rng(h))) return rc;
   if ((flags & FDSR_SAMPLE_GRAPH) && st == nullptr)
     return fail(h, FDSR_E_INVALID, "FDSR_SAMPLE_GRAPH needs a non-default stream (stream capture cannot run on the NULL stream)");
@@ -1245,25 +1098,8 @@ int fdsr_set_precision(fdsr_handle h, int mode) {
         return fail(h, FDSR_E_INVALID, "the 16-bit storage modes need channel counts that are multiples of 16 (layer %s)", op.name.c_str());
     }
   }
-  if (mode == PREC_F32 && h->f32_forms_stale) {   // f16x3 training steps refreshed only the fp32 forms they read
-    // the optimiser step that left them stale may still be queued on a non-blocking stream the NULL stream does not order after
-    HIPCHK(h, hipDeviceSynchronize());
-    int rc = ensure_f32_forms(h, nullptr);
-    if (rc) return rc;
-    HIPCHK(h, hipDeviceSynchronize());
-  }
-  // The 16-bit forms that lag behind optimiser steps are refreshed when the mode is SWITCHED to (here) and by the calls that read them
-  // in eval mode (fdsr_sample, fdsr_unet_forward) -- not when a training loop merely re-states its precision before every step: that
-  // used to cost a host re-pack of every weight per step.
-  if (mode != PREC_F32 && mode != h->prec && h->h_forms_stale) {
-    int rc = fdsr_sync_weight_forms(h);
-    if (rc) return rc;
-  }
-  if (h->prec != mode) {
-    for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
-    h->graphs.clear();
-    drop_step_graphs(h);
-  }
+  int rc = apply_plan(h, fdsr_forms::on_precision(h->forms, h->prec, mode), nullptr);
+  if (rc) return rc;
   h->prec = mode;
   return FDSR_OK;
 }

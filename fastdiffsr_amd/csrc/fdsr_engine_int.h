@@ -1,5 +1,6 @@
 // Internal types of the engine shared by fdsr_plan.cpp (the static plan: ops, tensors, weight schema), fdsr_engine.cpp
-// (workspace planning, forward, sampling, C ABI) and fdsr_train.cpp (backward pass, Adam).  Not part of the C ABI (include/fdsr.h).
+// (workspace planning, forward, sampling, C ABI), fdsr_forms.cpp (weight forms: freshness record and packing) and fdsr_train.cpp
+// (backward pass, Adam).  Not part of the C ABI (include/fdsr.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "../../include/fdsr.h"
+#include "fdsr_forms.h"
 #include "fdsr_kernels.h"
 
 namespace fdsr_int {
@@ -103,7 +105,16 @@ struct StepGraphEntry {
   hipGraphExec_t head, body, rem;   // rem: null when chunk divides T
 };
 
-void drop_step_graphs(fdsr_handle h);   // destroys the captured fdsr_sample_stepwise graphs
+// One transposed form of a conv weight (input-gradient convolutions): towards one concat source, or towards all input channels
+// at once where the input is GroupNorm'ed.  Channels [c_off, c_off + rows) of the weight's Cin.
+struct WtSlot {
+  int c_off = 0, rows = 0;
+  size_t wt_off = 0;            // float offset into d_wt
+  size_t wtq_off = SIZE_MAX;    // byte offset into d_wtq (SIZE_MAX: this conv's input gradient stays on the fp32 kernel)
+};
+struct WtSlots { int n = 0; WtSlot s[2]; };
+// padded dimensions of a transposed form of `rows` produced channels over K channels of dy: fp32 kernel, then f16x3 kernels
+struct TDims { int rows_pad, cols_pad, WN, rows_pad_h, K_pad_h; };
 
 }  // namespace fdsr_int
 
@@ -142,7 +153,7 @@ struct fdsr_engine {
   int* d_sat = nullptr;            // f16x3 range guard: sticky flag raised by the raw-input staging paths
   float* d_temb_table = nullptr;
   float* d_nl = nullptr;
-  bool temb_table_valid = false;
+  fdsr_forms::Forms forms;   // which weight forms follow d_master, and who packed them
   size_t wq_bytes = 0;
   int prec = PREC_F32;
   bool kernels_ready = false;
@@ -164,8 +175,6 @@ struct fdsr_engine {
   int* d_step_ctl = nullptr;        // step counter, then (256 bytes on) the current StepRecord
   float* d_step_row = nullptr;      // [TE]: the current step's noise-embedding row
   float* d_step_sched = nullptr;    // [5][T]: device copy of the posterior scalars
-  int step_sched_T = 0;
-  bool step_sched_valid = false;
   std::vector<StepGraphEntry> step_graphs;
   unsigned step_graphs_epoch = 0;
   // ---- training state (fdsr_train.cpp) ----
@@ -178,24 +187,19 @@ struct fdsr_engine {
   int adam_t = 0;
   float* d_wt = nullptr;              // transposed, tap-flipped fp32 conv weights (input-gradient convolutions)
   size_t wt_floats = 0;
-  std::vector<size_t> wt_off0, wt_off1;   // per weight entry: offsets into d_wt for concat source 0 / 1 (SIZE_MAX: none)
+  std::vector<WtSlots> wt_slots;      // per weight entry: its slots in d_wt and d_wtq (n == 0: no input gradient)
   float* d_hscale = nullptr;          // per weight entry: {2^e, 2^-e} of its f16x3 forms (read by the kernels after device re-packs)
   unsigned* d_hamax = nullptr;        // scratch of the scale computation: max|w| per weight entry (float bits)
   unsigned char* d_wtq = nullptr;     // transposed, tap-flipped f16x3 fragment forms (input-gradient convolutions in f16x3)
   size_t wtq_bytes = 0;
-  std::vector<size_t> wtq_off0, wtq_off1;   // per weight entry (SIZE_MAX: this conv's input gradient stays on the fp32 kernel)
   float* d_zero = nullptr;            // zeros (bias of the input-gradient convolutions)
   bool train_ready = false;
-  bool wt_valid = false;              // d_wt matches d_master
   bool training = false;              // .train(): Dropout(p) of block2 is live (unet.py:89-101); fp32 kernels only
   int n_drop_slots = 0;
   unsigned long long drop_seed = 0;   // key of the dropout masks (fdsr_set_seed / fdsr_set_dropout_seed)
   unsigned drop_step = 0;             // forward passes made in training mode: part of the mask's Philox counter
   bool keep_stats = false;            // forward also stores per-(image, group) mean / rstd of every GroupNorm
-  bool h_forms_stale = false;         // 16-bit weight forms lag behind the master copy (after an optimiser step)
   float* d_up2_inv = nullptr;         // per weight entry: un-scaling of its device-packed sub-pixel (upsample) form
-  bool up2_dev_fresh = false;         // the f16x3 sub-pixel forms were re-packed on the device after the last optimiser step
-  bool f32_forms_stale = false;       // fp32 conv forms (d_params packs, d_wt) lag: f16x3 training steps refresh only what they read
   unsigned long long* d_copy_tab = nullptr;   // {src offset, dst offset, count} triples: master -> d_params for the non-conv tensors
   int n_copy_tab = 0;
   size_t copy_tab_max = 0;                // elements of the largest entry of that table
@@ -221,11 +225,18 @@ int check_ws(fdsr_handle h, void* ws, size_t bytes);
 int ensure_rng(fdsr_handle h);
 int run_unet(fdsr_handle h, int N, int H, int W, char* ws, const float* nl_dev, float nl_scalar, hipStream_t st,
              const float* temb_row = nullptr);
-int pack_weights_h(fdsr_handle h, WeightEntry& w, const float* host);
-int ensure_f32_forms(fdsr_handle h, hipStream_t st);   // fdsr_train.cpp: fp32 conv forms left behind by lazy f16x3 training steps
+int build_temb_table(fdsr_handle h, hipStream_t st);   // pass TEMB_TABLE
+int upload_step_sched(fdsr_handle h);                  // pass STEP_SCHED
+void drop_captures(fdsr_handle h);                     // destroys the captured sampling graphs of both entry points
+// fdsr_forms.cpp
+int apply_plan(fdsr_handle h, const fdsr_forms::Plan& p, hipStream_t st);   // runs the passes in order (device passes on st), then drops the captures
+int pack_weight_host(fdsr_handle h, WeightEntry& w, const float* host);
+int prepare_train_forms(fdsr_handle h);
+TDims t_dims(ConvKind ck, int K, int rows);
 // fdsr_train.cpp
 int train_workspace_extra(fdsr_handle h, int N, int H, int W, size_t* bytes);
 
+inline int conv_K(fdsr_handle h, const Op& op) { return op.dst == h->t_eps ? 8 : op.Cout; }   // channels of dy as stored
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
 inline size_t numel(const std::vector<int64_t>& s) {

@@ -1,5 +1,5 @@
 // Training step of the FastDiffSR UNet on the device: forward in "keep" mode, loss, backward
-// pass, Adam, re-packing of the updated weights.  Reference: DDPM.optimize_parameters (model/model.py:47-57),
+// pass, Adam (the re-packing of the updated weights: fdsr_forms.cpp).  Reference: DDPM.optimize_parameters (model/model.py:47-57),
 // GaussianDiffusion.p_losses (model/fastdiffsr_modules/diffusion.py:242-270), UNet.forward (unet.py:299-323).
 // The siblings' plans (ddpm_modules, tesr_modules, gdp_modules) walk the same loop; their own ops -- the
 // attention core, GDP's pooled / upsampled ResBlocks and scale-shift GroupNorms -- are cases of it below.
@@ -102,17 +102,6 @@ int make_train_plan(fdsr_handle h, int N, int H, int W, TrainPlan* tp) {
   return FDSR_OK;
 }
 
-// transposed weights: per conv weight, per concat source (fdsr_train.hip: pack_conv_f32_t)
-struct WtDims { int rows_pad, cols_pad; };
-WtDims wt_dims(ConvKind ck, int K, int Csub) {
-  int KC, BN;
-  const ConvKind k = ck == CONV1 ? CONV1 : CONV3_S1;     // the transposed conv always runs at stride 1
-  conv_tile_config(k, K, 0, Csub, &KC, &BN);
-  return WtDims{round_up(Csub, BN), round_up(K, KC)};
-}
-
-int conv_K(fdsr_handle h, const Op& op) { return op.dst == h->t_eps ? 8 : op.Cout; }   // channels of dy as stored
-
 int train_prepare(fdsr_handle h) {
   if (h->train_ready) return FDSR_OK;
   // FastDiffSR; the two siblings built from the same blocks plus SelfAttention: SR3 (ddpm_modules: integer time, Swish in front of the
@@ -128,152 +117,15 @@ int train_prepare(fdsr_handle h) {
   HIPCHK(h, hipMemset(h->d_adam_m, 0, nb));
   HIPCHK(h, hipMemset(h->d_adam_v, 0, nb));
   h->adam_t = 0;
-  // transposed-weight arena
-  h->wt_off0.assign(h->weights.size(), SIZE_MAX);
-  h->wt_off1.assign(h->weights.size(), SIZE_MAX);
-  size_t off = 0;
   int maxC = 8;
-  for (const Op& op : h->ops) {
-    if (op.kind != Op::CONV || op.src0 == h->t_in) continue;
-    const int T = op.ck == CONV1 ? 1 : 9, K = conv_K(h, op);
-    maxC = std::max(maxC, op.C0 + op.C1);
-    const bool whole = op.gn_slot >= 0;                   // GroupNorm'ed input: one transposed conv over all input channels
-    if (whole || op.C1 == 0) {
-      const WtDims d = wt_dims(op.ck, K, op.C0 + op.C1);
-      h->wt_off0[op.w] = off;
-      off += align_up((size_t)T * d.rows_pad * d.cols_pad, 64);
-    } else {                                              // raw concat input: one transposed conv per source
-      const WtDims d0 = wt_dims(op.ck, K, op.C0), d1 = wt_dims(op.ck, K, op.C1);
-      h->wt_off0[op.w] = off;  off += align_up((size_t)T * d0.rows_pad * d0.cols_pad, 64);
-      h->wt_off1[op.w] = off;  off += align_up((size_t)T * d1.rows_pad * d1.cols_pad, 64);
-    }
-  }
-  h->wt_floats = off;
-  // the same forms as f16x3 MFMA fragments, for the convs whose transposed shape the 16-bit kernels take
-  // (16-channel K chunks: K % 16 == 0 and the produced channel count % 16 == 0)
-  h->wtq_off0.assign(h->weights.size(), SIZE_MAX);
-  h->wtq_off1.assign(h->weights.size(), SIZE_MAX);
-  size_t qoff = 0;
-  for (const Op& op : h->ops) {
-    if (op.kind != Op::CONV || op.src0 == h->t_in) continue;
-    const int T = op.ck == CONV1 ? 1 : 9, K = conv_K(h, op);
-    if (K % 16 || op.C0 % 16 || op.C1 % 16) continue;
-    auto frag_bytes = [&](int rows) {
-      int TH, WN;
-      conv_h_config(op.ck == CONV1 ? CONV1 : CONV3_S1, rows, &TH, &WN);
-      return align_up((size_t)(round_up(rows, 32 * WN) / 32) * (round_up(K, 16) / 16) * T * 64 * 16 * 2, 256);
-    };
-    if (op.gn_slot >= 0 || op.C1 == 0) {
-      h->wtq_off0[op.w] = qoff;  qoff += frag_bytes(op.C0 + op.C1);
-    } else {
-      h->wtq_off0[op.w] = qoff;  qoff += frag_bytes(op.C0);
-      h->wtq_off1[op.w] = qoff;  qoff += frag_bytes(op.C1);
-    }
-  }
-  h->wtq_bytes = qoff;
-  HIPCHK(h, hipMalloc((void**)&h->d_wtq, std::max<size_t>(qoff, 256)));
-  HIPCHK(h, hipMalloc((void**)&h->d_hamax, h->weights.size() * sizeof(unsigned)));
-  HIPCHK(h, hipMalloc((void**)&h->d_up2_inv, h->weights.size() * sizeof(float)));
-  HIPCHK(h, hipMalloc((void**)&h->d_wt, std::max<size_t>(off, 4) * sizeof(float)));
+  for (const Op& op : h->ops)
+    if (op.kind == Op::CONV && op.src0 != h->t_in) maxC = std::max(maxC, op.C0 + op.C1);
   HIPCHK(h, hipMalloc((void**)&h->d_zero, (size_t)round_up(maxC, 64) * sizeof(float)));
   HIPCHK(h, hipMemset(h->d_zero, 0, (size_t)round_up(maxC, 64) * sizeof(float)));
-  {   // the non-conv tensors (GroupNorm affine, biases, MLPs ...) follow the master copy through ONE table-driven copy
-    std::vector<unsigned long long> tab;
-    for (int i = 0; i < h->n_schema; ++i) {
-      const WeightEntry& w = h->weights[i];
-      if (!w.live || w.sink == WeightEntry::CONV_PACK) continue;
-      tab.push_back(h->master_off[i]);
-      tab.push_back(w.dev_off);
-      tab.push_back(numel(w.shape));
-      h->copy_tab_max = std::max<size_t>(h->copy_tab_max, numel(w.shape));
-    }
-    h->n_copy_tab = (int)(tab.size() / 3);
-    HIPCHK(h, hipMalloc((void**)&h->d_copy_tab, std::max<size_t>(tab.size(), 3) * sizeof(unsigned long long)));
-    if (!tab.empty()) HIPCHK(h, hipMemcpy(h->d_copy_tab, tab.data(), tab.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
-  }
+  int rc = prepare_train_forms(h);   // the transposed arenas and what the device packing passes need
+  if (rc) return rc;
   HIPCHK(h, train_kernels_init());
   h->train_ready = true;
-  return FDSR_OK;
-}
-
-// (re-)build every device form the fp32 kernels read from the master copy: after load and after each Adam step
-int repack_from_master(fdsr_handle h, hipStream_t st, bool forward_forms, bool all_f32_forms) {
-  // In f16x3 mode a step reads the fp32 conv forms only where the 16-bit kernels cannot run (the packed-input conv, odd
-  // shapes): the others are refreshed when something asks for them (ensure_f32_forms: fp32 mode, fp32 sampling).
-  const bool lazy = h->prec == PREC_F16X3 && !all_f32_forms;
-  bool skipped = false;
-  if (forward_forms) {
-    for (int i = 0; i < h->n_schema; ++i) {
-      WeightEntry& w = h->weights[i];
-      if (!w.live || w.sink != WeightEntry::CONV_PACK) continue;
-      if (lazy && w.h_ok) { skipped = true; continue; }
-      HIPCHK(h, launch_pack_conv_f32(h->d_master + h->master_off[i], h->d_params + w.dev_off, (int)w.shape[0], (int)w.shape[1], w.ks,
-                                     w.cout_pad, w.cin_pad, st));
-    }
-    HIPCHK(h, launch_copy_table(h->d_master, h->d_params, h->d_copy_tab, h->n_copy_tab, st, h->copy_tab_max));
-  }
-  for (const Op& op : h->ops) {
-    if (op.kind != Op::CONV || op.src0 == h->t_in) continue;
-    if (lazy && h->wtq_off0[op.w] != SIZE_MAX) { skipped = true; continue; }
-    const WeightEntry& w = h->weights[op.w];
-    const float* src = h->d_master + h->master_off[op.w];
-    const int K = conv_K(h, op), Cout = (int)w.shape[0], Cin = (int)w.shape[1];
-    if (h->wt_off1[op.w] == SIZE_MAX) {
-      const WtDims d = wt_dims(op.ck, K, op.C0 + op.C1);
-      HIPCHK(h, launch_pack_conv_f32_t(src, h->d_wt + h->wt_off0[op.w], Cout, Cin, w.ks, 0, op.C0 + op.C1, d.rows_pad, d.cols_pad, st));
-    } else {
-      const WtDims d0 = wt_dims(op.ck, K, op.C0), d1 = wt_dims(op.ck, K, op.C1);
-      HIPCHK(h, launch_pack_conv_f32_t(src, h->d_wt + h->wt_off0[op.w], Cout, Cin, w.ks, 0, op.C0, d0.rows_pad, d0.cols_pad, st));
-      HIPCHK(h, launch_pack_conv_f32_t(src, h->d_wt + h->wt_off1[op.w], Cout, Cin, w.ks, op.C0, op.C1, d1.rows_pad, d1.cols_pad, st));
-    }
-  }
-  // f16x3 forms (forward + transposed), packed on the device with a per-tensor power-of-two scale
-  HIPCHK(h, hipMemsetAsync(h->d_hamax, 0, h->weights.size() * sizeof(unsigned), st));
-  for (int i = 0; i < h->n_schema; ++i) {
-    const WeightEntry& w = h->weights[i];
-    if (w.live && w.sink == WeightEntry::CONV_PACK && w.h_ok)
-      HIPCHK(h, launch_hamax(h->d_master + h->master_off[i], numel(w.shape), h->d_hamax + i, st));
-  }
-  // every slot gets a scale; the slots that are not f16x3 conv weights (amax 0 -> e = 12) are never read
-  HIPCHK(h, launch_hscale_all(h->d_hamax, h->d_hscale, (int)h->weights.size(), st));
-  for (int i = 0; i < h->n_schema; ++i) {
-    WeightEntry& w = h->weights[i];
-    if (!w.live || w.sink != WeightEntry::CONV_PACK || !w.h_ok) continue;
-    const float* src = h->d_master + h->master_off[i];
-    float* sc2 = h->d_hscale + 2 * (size_t)i;
-    if (forward_forms) {
-      HIPCHK(h, launch_pack_conv_h(src, h->d_wq + w.hq_off[PREC_F16X3], sc2, (int)w.shape[0], (int)w.shape[1], w.ks, w.h_WN,
-                                   w.h_cout_pad, w.h_cin_pad, 0, 0, 0, st));
-      if (w.ck == CONV3_UP)   // and the sub-pixel form the upsample convs run on
-        HIPCHK(h, launch_pack_conv_up2_h(src, h->d_wq + w.up2_off[PREC_F16X3], sc2, h->d_up2_inv + i, (int)w.shape[0], (int)w.shape[1],
-                                         w.h_WN, w.h_cout_pad, w.h_cin_pad, st));
-    }
-  }
-  if (forward_forms) {
-    h->up2_dev_fresh = true;
-    h->h_forms_stale = true;   // the sampling forms (bf16, the host-packed sub-pixel forms) now differ from what this pass wrote: the next
-                               // eval-mode sample / forward, or a switch of the precision, re-packs them on the host
-  }
-  for (const Op& op : h->ops) {
-    if (op.kind != Op::CONV || op.src0 == h->t_in || h->wtq_off0[op.w] == SIZE_MAX) continue;
-    const WeightEntry& w = h->weights[op.w];
-    const float* src = h->d_master + h->master_off[op.w];
-    const float* sc2 = h->d_hscale + 2 * (size_t)op.w;
-    const int K = conv_K(h, op), Cout = (int)w.shape[0], Cin = (int)w.shape[1];
-    auto pack_t = [&](size_t qo, int c_off, int rows) -> hipError_t {
-      int TH, WN;
-      conv_h_config(op.ck == CONV1 ? CONV1 : CONV3_S1, rows, &TH, &WN);
-      return launch_pack_conv_h(src, h->d_wtq + qo, sc2, Cout, Cin, w.ks, WN, round_up(rows, 32 * WN), round_up(K, 16), 1, c_off, rows, st);
-    };
-    if (h->wtq_off1[op.w] == SIZE_MAX) {
-      HIPCHK(h, pack_t(h->wtq_off0[op.w], 0, op.C0 + op.C1));
-    } else {
-      HIPCHK(h, pack_t(h->wtq_off0[op.w], 0, op.C0));
-      HIPCHK(h, pack_t(h->wtq_off1[op.w], op.C0, op.C1));
-    }
-  }
-  h->temb_table_valid = false;
-  h->f32_forms_stale = all_f32_forms ? false : (h->f32_forms_stale || skipped);
   return FDSR_OK;
 }
 
@@ -281,7 +133,7 @@ int repack_from_master(fdsr_handle h, hipStream_t st, bool forward_forms, bool a
 int launch_dgrad(fdsr_handle h, ConvKind ck, const float* dy, int K, int Hs, int Ws, const float* wt, int Csub, float* out,
                  bool accumulate, int N, hipStream_t st) {
   const ConvKind k = ck == CONV1 ? CONV1 : CONV3_S1;
-  const WtDims d = wt_dims(ck, K, Csub);
+  const TDims d = t_dims(ck, K, Csub);
   ConvParams p{};
   p.x0 = dy; p.w = wt; p.bias = h->d_zero; p.out = out; p.res = accumulate ? out : nullptr;
   p.N = N; p.Hin = Hs; p.Win = Ws; p.Hout = Hs; p.Wout = Ws;
@@ -297,12 +149,11 @@ int launch_dgrad(fdsr_handle h, ConvKind ck, const float* dy, int K, int Hs, int
 int launch_dgrad_h(fdsr_handle h, const Op& op, const float* dy, int K, int Hs, int Ws, size_t qoff, int Csub, float* out,
                    bool accumulate, int N, hipStream_t st, const ConvParams* gb = nullptr, int* gb_tiles = nullptr) {
   const ConvKind k = op.ck == CONV1 ? CONV1 : CONV3_S1;
-  int TH, WN;
-  conv_h_config(k, Csub, &TH, &WN);
+  const TDims d = t_dims(op.ck, K, Csub);
   ConvParams p{};
   p.x0 = dy; p.bias = h->d_zero; p.out = out; p.res = accumulate ? out : nullptr;
   p.N = N; p.Hin = Hs; p.Win = Ws; p.Hout = Hs; p.Wout = Ws;
-  p.C0 = K; p.C1 = 0; p.Cout = Csub; p.Cin_pad = round_up(K, 16); p.Cout_pad = round_up(Csub, 32 * WN);
+  p.C0 = K; p.C1 = 0; p.Cout = Csub; p.Cin_pad = d.K_pad_h; p.Cout_pad = d.rows_pad_h;
   p.wq = h->d_wtq + qoff;
   p.w_inv_scale = 1.0f;
   p.w_inv_scale_dev = h->d_hscale + 2 * (size_t)op.w + 1;
@@ -331,11 +182,6 @@ int train_workspace_extra(fdsr_handle h, int N, int H, int W, size_t* bytes) {
   if (rc) return rc;
   *bytes = tp.bytes;
   return FDSR_OK;
-}
-// the fp32 conv forms a lazy f16x3 step left behind (see repack_from_master)
-int ensure_f32_forms(fdsr_handle h, hipStream_t st) {
-  if (!h->f32_forms_stale || !h->train_ready) return FDSR_OK;
-  return repack_from_master(h, st, true, true);
 }
 }  // namespace fdsr_int
 
@@ -383,14 +229,7 @@ int train_grads_impl(fdsr_handle h, const float* x_nchw, const float* hr_nchw, c
     return fail(h, FDSR_E_WORKSPACE, "training workspace too small or misaligned: %zu < %zu bytes", workspace_bytes, tp.bytes);
   char* ws = reinterpret_cast<char*>(workspace);
   ShapePlan& sp = h->plan;
-  // the transposed forms follow the master copy
-  if (h->prec == PREC_F32 && (rc = ensure_f32_forms(h, st))) return rc;
-  if (!h->wt_valid) {
-    // f16x3: the forward forms are re-packed on the device here too, as every optimiser step will: a run resumed from a checkpoint
-    // (host-packed at load) then steps on the same bits as the uninterrupted run (the two packers round the sub-pixel forms differently)
-    if ((rc = repack_from_master(h, st, h->prec == PREC_F16X3, false))) return rc;
-    h->wt_valid = true;
-  }
+  if ((rc = apply_plan(h, fdsr_forms::need_train(h->forms, h->prec), st))) return rc;   // the transposed forms follow the master copy
 
   // ---- forward, keeping every activation and the GroupNorm statistics ----
   float* xin = reinterpret_cast<float*>(ws + sp.tensor_off[h->t_in]);
@@ -550,10 +389,10 @@ int train_grads_impl(fdsr_handle h, const float* x_nchw, const float* hr_nchw, c
                                  (size_t)op.Cout * sizeof(float), N, hipMemcpyDeviceToDevice, st));
     if (op.src0 == h->t_in) continue;                     // no gradient w.r.t. the network input
     // input gradient: on the f16x3 kernels in that mode (where the transposed shape fits them), else exact fp32
-    auto dgrad = [&](const float* dyp, int Hs, int Ws, int src, int Csub, float* outp, bool acc) -> int {
-      const size_t qo = src == 0 ? h->wtq_off0[op.w] : h->wtq_off1[op.w];
-      if (h->prec == PREC_F16X3 && qo != SIZE_MAX) return launch_dgrad_h(h, op, dyp, K, Hs, Ws, qo, Csub, outp, acc, N, st);
-      return launch_dgrad(h, op.ck, dyp, K, Hs, Ws, h->d_wt + (src == 0 ? h->wt_off0[op.w] : h->wt_off1[op.w]), Csub, outp, acc, N, st);
+    const WtSlot* slots = h->wt_slots[op.w].s;
+    auto dgrad = [&](const float* dyp, int Hs, int Ws, const WtSlot& s, float* outp, bool acc) -> int {
+      if (h->prec == PREC_F16X3 && s.wtq_off != SIZE_MAX) return launch_dgrad_h(h, op, dyp, K, Hs, Ws, s.wtq_off, s.rows, outp, acc, N, st);
+      return launch_dgrad(h, op.ck, dyp, K, Hs, Ws, h->d_wt + s.wt_off, s.rows, outp, acc, N, st);
     };
     if (op.gn_slot >= 0) {
       GnBwdParams g{};
@@ -563,7 +402,7 @@ int train_grads_impl(fdsr_handle h, const float* x_nchw, const float* hr_nchw, c
       // of the launch that produces dA, where that launch is a 16x16x32 kernel
       int gb_tiles = 0;
       {
-        const size_t qo = h->wtq_off0[op.w];
+        const size_t qo = slots[0].wtq_off;
         if (h->prec == PREC_F16X3 && qo != SIZE_MAX && !up) {
           ConvParams gb{};
           gb.gb_x0 = TP(op.src0); gb.gb_x1 = TP(op.src1); gb.gb_C0 = op.C0; gb.gb_G = G; gb.gb_plain = op.gn_plain ? 1 : 0;
@@ -576,7 +415,7 @@ int train_grads_impl(fdsr_handle h, const float* x_nchw, const float* hr_nchw, c
           }
           gb.part_out = gn_bwd_tile_part(dbl);
           if ((rc = launch_dgrad_h(h, op, dy, K, Ho, Wo, qo, Cin, tmpA, false, N, st, &gb, &gb_tiles))) return rc;
-        } else if ((rc = dgrad(dy, Ho, Wo, 0, Cin, tmpA, false))) return rc;
+        } else if ((rc = dgrad(dy, Ho, Wo, slots[0], tmpA, false))) return rc;
       }
       if (up) HIPCHK(h, launch_pool2_add(tmpA, tmpZ, N, Hi, Wi, Cin, true, st));
       if (gb_tiles > 0) { g.g_part = gn_bwd_tile_part(dbl); g.g_nt = gb_tiles; }
@@ -603,13 +442,13 @@ int train_grads_impl(fdsr_handle h, const float* x_nchw, const float* hr_nchw, c
       HIPCHK(h, launch_gn_bwd(g, st));
     } else if (op.ck == CONV3_S2) {
       HIPCHK(h, launch_zero_insert(dy, tmpZ, N, Ho, Wo, K, st));
-      if ((rc = dgrad(tmpZ, Hi, Wi, 0, op.C0, GT(op.src0), !first(op.src0)))) return rc;
+      if ((rc = dgrad(tmpZ, Hi, Wi, slots[0], GT(op.src0), !first(op.src0)))) return rc;
     } else if (op.ck == CONV3_UP) {
-      if ((rc = dgrad(dy, Ho, Wo, 0, op.C0, tmpA, false))) return rc;
+      if ((rc = dgrad(dy, Ho, Wo, slots[0], tmpA, false))) return rc;
       HIPCHK(h, launch_pool2_add(tmpA, GT(op.src0), N, Hi, Wi, op.C0, first(op.src0), st));
     } else {
-      if ((rc = dgrad(dy, Ho, Wo, 0, op.C0, GT(op.src0), !first(op.src0)))) return rc;
-      if (op.C1 > 0 && (rc = dgrad(dy, Ho, Wo, 1, op.C1, GT(op.src1), !first(op.src1)))) return rc;
+      if ((rc = dgrad(dy, Ho, Wo, slots[0], GT(op.src0), !first(op.src0)))) return rc;
+      if (op.C1 > 0 && (rc = dgrad(dy, Ho, Wo, slots[1], GT(op.src1), !first(op.src1)))) return rc;
     }
   }
 
@@ -680,14 +519,7 @@ int fdsr_adam_step(fdsr_handle h, float lr, float beta1, float beta2, float eps,
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   h->adam_t += 1;
   HIPCHK(h, launch_adam(h->d_master, h->d_grad, h->d_adam_m, h->d_adam_v, h->master_floats, lr, beta1, beta2, eps, h->adam_t, st));
-  int rc = repack_from_master(h, st, true, false);
-  if (rc) return rc;
-  h->wt_valid = true;
-  h->h_forms_stale = true;
-  for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
-  h->graphs.clear();
-  drop_step_graphs(h);
-  return FDSR_OK;
+  return apply_plan(h, fdsr_forms::on_step(h->forms, h->prec), st);
 }
 
 static int find_weight(fdsr_handle h, const char* key) {
@@ -754,25 +586,6 @@ int fdsr_grad_arena(fdsr_handle h, float** dev_ptr, size_t* count) {
   }
   *dev_ptr = h->d_grad;
   *count = h->master_floats;
-  return FDSR_OK;
-}
-
-// Bring the 16-bit weight forms (f16x3 / bf16 sampling) in line with the master copy after optimiser steps.
-int fdsr_sync_weight_forms(fdsr_handle h) {
-  if (!h) return FDSR_E_INVALID;
-  if (!h->h_forms_stale) return FDSR_OK;
-  HIPCHK(h, hipDeviceSynchronize());
-  std::vector<float> host;
-  for (int i = 0; i < h->n_schema; ++i) {
-    WeightEntry& w = h->weights[i];
-    if (!w.live || w.sink != WeightEntry::CONV_PACK || !w.h_ok) continue;
-    host.resize(numel(w.shape));
-    HIPCHK(h, hipMemcpy(host.data(), h->d_master + h->master_off[i], host.size() * sizeof(float), hipMemcpyDeviceToHost));
-    int rc = pack_weights_h(h, w, host.data());
-    if (rc) return rc;
-  }
-  h->h_forms_stale = false;
-  h->up2_dev_fresh = false;   // the host-packed sub-pixel forms (own scale) are current again
   return FDSR_OK;
 }
 
