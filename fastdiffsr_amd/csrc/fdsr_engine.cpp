@@ -1,6 +1,6 @@
 // Host side of libfdsr_hip.so: checkpoint repacking, workspace planning, running
-// the plan of the UNet, the 20-step sampling loop and the C ABI (include/fdsr.h).
-// The static plan itself (ops, tensors, weight schema) is built in fdsr_plan.cpp.
+// the plan of the UNet and the C ABI (include/fdsr.h).  The static plan itself (ops,
+// tensors, weight schema) is built in fdsr_plan.cpp, the sampling loop in fdsr_sample.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -254,8 +254,6 @@ double conv_flops(const Op& op, int N, int H, int W) {
 }
 
 // One UNet forward over the plan; input already packed in tensor t_in.
-int fill_temb(fdsr_handle h, float* temb, int N, const float* nl_dev, float nl_scalar, hipStream_t st);
-
 int run_unet(fdsr_handle h, int N, int H, int W, char* ws, const float* nl_dev, float nl_scalar, hipStream_t st,
              const float* temb_row) {
   ShapePlan& sp = h->plan;
@@ -515,45 +513,6 @@ int run_unet(fdsr_handle h, int N, int H, int W, char* ws, const float* nl_dev, 
   return FDSR_OK;
 }
 
-int fill_temb(fdsr_handle h, float* temb, int N, const float* nl_dev, float nl_scalar, hipStream_t st) {
-  auto P = [&](int widx) -> const float* { return widx >= 0 ? h->d_params + h->weights[widx].dev_off : nullptr; };
-  TembParams tp;
-  tp.freq = P(h->w_freq);
-  tp.w1 = P(h->w_mlp[0]);
-  tp.b1 = P(h->w_mlp[1]);
-  tp.w2 = P(h->w_mlp[2]);
-  tp.b2 = P(h->w_mlp[3]);
-  tp.wn = h->d_params + h->noise_w_off;   // all 22 noise_func Linear layers, concatenated by rows
-  tp.bn = h->d_params + h->noise_b_off;
-  tp.nl_dev = nl_dev;
-  tp.nl_scalar = nl_scalar;
-  tp.temb = temb;
-  tp.inner = h->cfg.inner_channel;
-  tp.TE = h->TE;
-  tp.N = N;
-  tp.swish_block = (h->sr3 || h->gdp) ? 1 : 0;
-  tp.enc_dim = tp.hid_dim = tp.t_dim = tp.cos_first = 0;
-  if (h->gdp) { tp.enc_dim = h->cfg.inner_channel; tp.hid_dim = tp.t_dim = 4 * h->cfg.inner_channel; tp.cos_first = 1; }
-  HIPCHK(h, launch_temb(tp, st));
-  return FDSR_OK;
-}
-
-// Row t of the table is what the per-step kernel would produce for noise level t: same kernel,
-// same arithmetic, evaluated for all T levels in one launch.
-int build_temb_table(fdsr_handle h, hipStream_t st) {
-  if (h->d_temb_table) { (void)hipFree(h->d_temb_table); h->d_temb_table = nullptr; }
-  if (h->d_nl) { (void)hipFree(h->d_nl); h->d_nl = nullptr; }
-  HIPCHK(h, hipMalloc(&h->d_temb_table, (size_t)h->T * h->TE * sizeof(float)));
-  HIPCHK(h, hipMalloc(&h->d_nl, (size_t)h->T * sizeof(float)));
-  std::vector<float> nl(h->T);
-  for (int t = 0; t < h->T; ++t) nl[t] = (h->sr3 || h->gdp) ? (float)t : h->s_nl[t];
-  HIPCHK(h, hipMemcpy(h->d_nl, nl.data(), nl.size() * sizeof(float), hipMemcpyHostToDevice));
-  int rc = fill_temb(h, h->d_temb_table, h->T, h->d_nl, 0.f, st);
-  if (rc) return rc;
-  HIPCHK(h, hipStreamSynchronize(st));
-  return FDSR_OK;
-}
-
 int check_ready(fdsr_handle h, bool need_schedule) {
   for (const auto& w : h->weights)
     if (w.live && !w.loaded) return fail(h, FDSR_E_STATE, "weight '%s' has not been loaded", w.key.c_str());
@@ -561,155 +520,14 @@ int check_ready(fdsr_handle h, bool need_schedule) {
   return FDSR_OK;
 }
 
-int check_ws(fdsr_handle h, void* ws, size_t bytes) {
+// the weights are loaded (and a schedule set), the plan is the one of (N,H,W), and the workspace holds it
+int plan_ready(fdsr_handle h, bool need_schedule, int N, int H, int W, void* ws, size_t bytes) {
+  int rc = check_ready(h, need_schedule);
+  if (rc) return rc;
+  if ((rc = get_plan(h, N, H, W))) return rc;
   if (!ws || (reinterpret_cast<uintptr_t>(ws) & 255)) return fail(h, FDSR_E_WORKSPACE, "workspace must be a 256-byte aligned device pointer");
   if (bytes < h->plan.bytes) return fail(h, FDSR_E_WORKSPACE, "workspace too small: %zu < %zu bytes", bytes, h->plan.bytes);
   return FDSR_OK;
-}
-
-int ensure_rng(fdsr_handle h) {
-  if (h->d_rng) return FDSR_OK;
-  HIPCHK(h, hipMalloc(&h->d_rng, 2 * sizeof(unsigned long long)));
-  const unsigned long long init[2] = {h->rng_seed, 0ull};
-  HIPCHK(h, hipMemcpy(h->d_rng, init, sizeof(init), hipMemcpyHostToDevice));
-  return FDSR_OK;
-}
-
-int sample_body(fdsr_handle h, const float* cond, const float* noise, float* out, float* traj, int N, int H, int W,
-                char* ws, hipStream_t st) {
-  float* xin = reinterpret_cast<float*>(ws + h->plan.tensor_off[h->t_in]);
-  float* eps = reinterpret_cast<float*>(ws + h->plan.tensor_off[h->t_eps]);
-  const size_t img = (size_t)N * 3 * H * W;
-  // x_in = cond, img = randn(shape)                                       diffusion.py:204-208
-  // packed input: cat([cond, x_t]) (diffusion.py:173); GDP: cat([x_t, cond]) (gdp_modules/diffusion.py:191)
-  const int x_off = h->gdp ? 0 : 3, c_off = h->gdp ? 3 : 0;
-  // the f16x3 range flag speaks for THIS call only (a captured loop clears it at every replay)
-  if (h->prec == PREC_F16X3 && g_tun.sat_guard) HIPCHK(h, hipMemsetAsync(h->d_sat, 0, sizeof(int), st));
-  HIPCHK(h, launch_nchw_to_nhwc(cond, xin, N, 3, H, W, h->CP, c_off, 1, st));
-  if (noise) {
-    HIPCHK(h, launch_nchw_to_nhwc(noise, xin, N, 3, H, W, h->CP, x_off, 0, st));
-  } else {   // the engine draws: a new call counter per sample (also under graph replay), plane 0 = x_T
-    HIPCHK(h, launch_rng_advance(h->d_rng, st));
-    HIPCHK(h, launch_randn_xin(h->d_rng, xin, N, H * W, h->CP, st, x_off));
-  }
-  for (int k = 0; k < h->T; ++k) {                                        // for i in reversed(range(T))  :209
-    const int t = h->T - 1 - k;
-    h->prof_step = (k % 4) == 0;
-    // FastDiffSR: the network sees the noise level sqrt(alpha_bar) (:169-170); SR3: the integer time
-    // (probe "bf16_f16x3_steps": this step on the fp32-grade kernels; the plan, the workspace and both 16-bit weight forms serve either mode,
-    // x_t and the network output cross a step as fp32)
-    const int base_prec = h->prec, fs = g_tun.bf16_f16x3_steps;
-    if (base_prec == PREC_BF16 && ((fs > 0 && k < fs) || (fs < 0 && k >= h->T + fs))) h->prec = PREC_F16X3;
-    int rc = run_unet(h, N, H, W, ws, nullptr, 0.f, st, h->d_temb_table + (size_t)t * h->TE);
-    h->prec = base_prec;
-    if (rc) return rc;
-    PosteriorParams pp{};
-    pp.eps = eps;
-    pp.xin = xin;
-    pp.noise = (t > 0 && noise) ? noise + (size_t)(k + 1) * img : nullptr;   // zeros at t == 0  :189
-    pp.rng = (t > 0 && !noise) ? h->d_rng : nullptr;
-    pp.rng_plane = k + 1;
-    pp.traj = traj ? traj + (size_t)k * img : nullptr;
-    pp.out = t == 0 ? out : nullptr;
-    pp.N = N; pp.HW = H * W; pp.CP = h->CP;
-    pp.c_recip = h->s_recip[t]; pp.c_recipm1 = h->s_recipm1[t];
-    pp.coef1 = h->s_c1[t]; pp.coef2 = h->s_c2[t]; pp.sigma = h->s_sigma[t];
-    pp.x_off = x_off; pp.x0_pred = h->gdp ? 1 : 0;
-    pp.plain_out = h->plain_out ? 1 : 0;                                        // ddpm_modules: ret_img[-1] is x_0 itself
-    HIPCHK(h, launch_posterior(pp, st));
-  }
-  h->prof_step = true;
-  return FDSR_OK;
-}
-
-// ---- fdsr_sample_stepwise: the same loop with its per-step inputs on the device ------------------------------------------
-void destroy_step_graph(const StepGraphEntry& g) {
-  for (hipGraphExec_t x : {g.head, g.body, g.rem})
-    if (x) (void)hipGraphExecDestroy(x);
-}
-
-void drop_step_graphs(fdsr_handle h) {
-  for (auto& g : h->step_graphs) destroy_step_graph(g);
-  h->step_graphs.clear();
-}
-
-void drop_sample_graphs(fdsr_handle h) {
-  for (auto& g : h->graphs) (void)hipGraphExecDestroy(g.exec);
-  h->graphs.clear();
-}
-
-void drop_captures(fdsr_handle h) {
-  drop_sample_graphs(h);
-  drop_step_graphs(h);
-}
-
-StepRecord* step_rec(fdsr_handle h) { return reinterpret_cast<StepRecord*>(reinterpret_cast<char*>(h->d_step_ctl) + 256); }
-
-int upload_step_sched(fdsr_handle h) {
-  if (!h->d_step_ctl) {
-    HIPCHK(h, hipMalloc(&h->d_step_ctl, 256 + sizeof(StepRecord)));
-    HIPCHK(h, hipMemset(h->d_step_ctl, 0, 256 + sizeof(StepRecord)));
-    HIPCHK(h, hipMalloc(&h->d_step_row, (size_t)h->TE * sizeof(float)));
-  }
-  if (h->d_step_sched) { (void)hipFree(h->d_step_sched); h->d_step_sched = nullptr; }
-  HIPCHK(h, hipMalloc(&h->d_step_sched, (size_t)5 * h->T * sizeof(float)));
-  std::vector<float> s;
-  s.reserve((size_t)5 * h->T);
-  for (const auto* v : {&h->s_recip, &h->s_recipm1, &h->s_c1, &h->s_c2, &h->s_sigma}) s.insert(s.end(), v->begin(), v->end());
-  HIPCHK(h, hipMemcpy(h->d_step_sched, s.data(), s.size() * sizeof(float), hipMemcpyHostToDevice));
-  return FDSR_OK;
-}
-
-// everything before step 0: the packed input, the range flag, the call counter of the engine's noise, and k = 0
-int stepwise_head(fdsr_handle h, const float* cond, const float* noise, int N, int H, int W, char* ws, hipStream_t st) {
-  float* xin = reinterpret_cast<float*>(ws + h->plan.tensor_off[h->t_in]);
-  const int x_off = h->gdp ? 0 : 3, c_off = h->gdp ? 3 : 0;
-  if (h->prec == PREC_F16X3 && g_tun.sat_guard) HIPCHK(h, hipMemsetAsync(h->d_sat, 0, sizeof(int), st));
-  HIPCHK(h, launch_nchw_to_nhwc(cond, xin, N, 3, H, W, h->CP, c_off, 1, st));
-  if (noise) {
-    HIPCHK(h, launch_nchw_to_nhwc(noise, xin, N, 3, H, W, h->CP, x_off, 0, st));
-  } else {
-    HIPCHK(h, launch_rng_advance(h->d_rng, st));
-    HIPCHK(h, launch_randn_xin(h->d_rng, xin, N, H * W, h->CP, st, x_off));
-  }
-  HIPCHK(h, hipMemsetAsync(h->d_step_ctl, 0, sizeof(int), st));
-  return FDSR_OK;
-}
-
-// one reverse step k (whichever the counter holds): identical launches for every k
-int stepwise_step(fdsr_handle h, const float* noise, float* out, float* traj, int N, int H, int W, char* ws, hipStream_t st,
-                  int traj_every) {
-  StepPrologueParams sp{};
-  sp.counter = h->d_step_ctl;
-  sp.sched = h->d_step_sched;
-  sp.temb_table = h->d_temb_table;
-  sp.temb_row = h->d_step_row;
-  sp.rec = step_rec(h);
-  sp.T = h->T; sp.TE = h->TE; sp.traj_every = traj_every;
-  HIPCHK(h, launch_step_prologue(sp, st));
-  int rc = run_unet(h, N, H, W, ws, nullptr, 0.f, st, h->d_step_row);
-  if (rc) return rc;
-  PosteriorStepParams pp{};
-  pp.rec = step_rec(h);
-  pp.eps = reinterpret_cast<const float*>(ws + h->plan.tensor_off[h->t_eps]);
-  pp.xin = reinterpret_cast<float*>(ws + h->plan.tensor_off[h->t_in]);
-  pp.noise = noise;
-  pp.rng = noise ? nullptr : h->d_rng;
-  pp.traj = traj;
-  pp.out = out;
-  pp.N = N; pp.HW = H * W; pp.CP = h->CP;
-  pp.x_off = h->gdp ? 0 : 3; pp.x0_pred = h->gdp ? 1 : 0;
-  pp.plain_out = h->plain_out ? 1 : 0;
-  HIPCHK(h, launch_posterior_step(pp, st));
-  return FDSR_OK;
-}
-
-// default chunk: T itself up to 32 steps, else the largest divisor of T in [16, 32] (T = 1000 / 2000: 25), else 32 + a remainder
-int default_chunk(int T) {
-  if (T <= 32) return T;
-  for (int c = 32; c >= 16; --c)
-    if (T % c == 0) return c;
-  return 32;
 }
 
 }  // namespace fdsr_int
@@ -829,10 +647,8 @@ int fdsr_workspace_bytes(fdsr_handle h, int batch, int height, int width, size_t
 int fdsr_unet_forward(fdsr_handle h, const float* x_nchw, const float* noise_level, float* eps_nchw, int batch, int height,
                       int width, void* workspace, size_t workspace_bytes, void* hip_stream) {
   if (!h || !x_nchw || !noise_level || !eps_nchw) return fail(h, FDSR_E_INVALID, "null argument");
-  int rc = check_ready(h, false);
+  int rc = plan_ready(h, false, batch, height, width, workspace, workspace_bytes);
   if (rc) return rc;
-  if ((rc = get_plan(h, batch, height, width))) return rc;
-  if ((rc = check_ws(h, workspace, workspace_bytes))) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   char* ws = reinterpret_cast<char*>(workspace);
   float* xin = reinterpret_cast<float*>(ws + h->plan.tensor_off[h->t_in]);
@@ -842,151 +658,6 @@ int fdsr_unet_forward(fdsr_handle h, const float* x_nchw, const float* noise_lev
   if ((rc = run_unet(h, batch, height, width, ws, noise_level, 0.f, st))) return rc;
   const float* eps = reinterpret_cast<const float*>(ws + h->plan.tensor_off[h->t_eps]);
   HIPCHK(h, launch_nhwc_to_nchw(eps, eps_nchw, batch, h->cfg.out_channel, height, width, h->cfg.out_channel, st));
-  return FDSR_OK;
-}
-
-int fdsr_sample(fdsr_handle h, const float* cond_nchw, const float* noise, float* out_nchw, float* traj_nchw, int batch,
-                int height, int width, void* workspace, size_t workspace_bytes, void* hip_stream, int flags) {
-  if (!h || !cond_nchw || !out_nchw) return fail(h, FDSR_E_INVALID, "null argument");
-  if (h->cfg.in_channel != 6 || h->cfg.out_channel != 3)
-    return fail(h, FDSR_E_INVALID, "conditional sampling needs in_channel=6, out_channel=3");
-  int rc = check_ready(h, true);
-  if (rc) return rc;
-  if ((rc = get_plan(h, batch, height, width))) return rc;
-  if ((rc = check_ws(h, workspace, workspace_bytes))) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  char* ws = reinterpret_cast<char*>(workspace);
-  if ((rc = apply_plan(h, fdsr_forms::need_sample(h->forms, h->prec, false), st))) return rc;   // optimiser steps moved the master copy
-  if (!noise && (rc = ensure_rng(h))) return rc;
-  if ((flags & FDSR_SAMPLE_GRAPH) && st == nullptr)
-    return fail(h, FDSR_E_INVALID, "FDSR_SAMPLE_GRAPH needs a non-default stream (stream capture cannot run on the NULL stream)");
-  const bool use_graph = (flags & FDSR_SAMPLE_GRAPH) && !h->profiling;
-  if (!use_graph) return sample_body(h, cond_nchw, noise, out_nchw, traj_nchw, batch, height, width, ws, st);
-
-  if (h->graphs_epoch != g_tun.epoch) {   // graphs captured under other launcher options
-    drop_sample_graphs(h);
-    h->graphs_epoch = g_tun.epoch;
-  }
-  for (auto& g : h->graphs)
-    if (g.cond == cond_nchw && g.noise == noise && g.out == out_nchw && g.traj == traj_nchw && g.ws == workspace &&
-        g.N == batch && g.H == height && g.W == width) {
-      HIPCHK(h, hipGraphLaunch(g.exec, st));
-      return FDSR_OK;
-    }
-  // capture the whole T-step loop once (all per-step scalars are kernel arguments)
-  hipGraph_t graph = nullptr;
-  HIPCHK(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-  rc = sample_body(h, cond_nchw, noise, out_nchw, traj_nchw, batch, height, width, ws, st);
-  hipError_t e = hipStreamEndCapture(st, &graph);
-  if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-  if (e != hipSuccess) return fail(h, FDSR_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-  GraphEntry ge{cond_nchw, noise, out_nchw, traj_nchw, workspace, batch, height, width, nullptr};
-  e = hipGraphInstantiate(&ge.exec, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  if (e != hipSuccess) return fail(h, FDSR_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-  if (h->graphs.size() >= 8) { (void)hipGraphExecDestroy(h->graphs.front().exec); h->graphs.erase(h->graphs.begin()); }
-  h->graphs.push_back(ge);
-  HIPCHK(h, hipGraphLaunch(ge.exec, st));
-  return FDSR_OK;
-}
-
-int fdsr_sample_stepwise(fdsr_handle h, const float* cond_nchw, const float* noise, float* out_nchw, float* traj_nchw, int batch,
-                         int height, int width, void* workspace, size_t workspace_bytes, void* hip_stream, int flags,
-                         const fdsr_sample_opts* opts) {
-  if (!h || !cond_nchw || !out_nchw) return fail(h, FDSR_E_INVALID, "null argument");
-  if (h->cfg.in_channel != 6 || h->cfg.out_channel != 3)
-    return fail(h, FDSR_E_INVALID, "conditional sampling needs in_channel=6, out_channel=3");
-  const int chunk_opt = opts ? opts->chunk_steps : 0, every = opts ? opts->traj_every : 1;
-  if (chunk_opt < 0 || every < 1) return fail(h, FDSR_E_INVALID, "fdsr_sample_opts: chunk_steps >= 0 and traj_every >= 1");
-  if (g_tun.bf16_f16x3_steps != 0)
-    return fail(h, FDSR_E_INVALID, "fdsr_sample_stepwise: the bf16_f16x3_steps probe makes the precision step-dependent; use fdsr_sample");
-  int rc = check_ready(h, true);
-  if (rc) return rc;
-  if ((rc = get_plan(h, batch, height, width))) return rc;
-  if ((rc = check_ws(h, workspace, workspace_bytes))) return rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  char* ws = reinterpret_cast<char*>(workspace);
-  if ((rc = apply_plan(h, fdsr_forms::need_sample(h->forms, h->prec, true), st))) return rc;
-  if (!noise && (rc = ensure_rng(h))) return rc;
-  if ((flags & FDSR_SAMPLE_GRAPH) && st == nullptr)
-    return fail(h, FDSR_E_INVALID, "FDSR_SAMPLE_GRAPH needs a non-default stream (stream capture cannot run on the NULL stream)");
-  const bool use_graph = (flags & FDSR_SAMPLE_GRAPH) && !h->profiling;
-  if (use_graph && h->training && h->n_drop_slots > 0)   // a replayed chunk would repeat its dropout masks
-    return fail(h, FDSR_E_INVALID, "fdsr_sample_stepwise: FDSR_SAMPLE_GRAPH with live dropout (train mode); sample eagerly");
-  const int T = h->T;
-  if (!use_graph) {
-    if ((rc = stepwise_head(h, cond_nchw, noise, batch, height, width, ws, st))) return rc;
-    for (int k = 0; k < T; ++k) {
-      h->prof_step = (k % 4) == 0;
-      rc = stepwise_step(h, noise, out_nchw, traj_nchw, batch, height, width, ws, st, every);
-      if (rc) break;
-    }
-    h->prof_step = true;
-    return rc;
-  }
-
-  const int chunk = chunk_opt > 0 ? std::min(chunk_opt, T) : default_chunk(T);
-  if (h->step_graphs_epoch != g_tun.epoch) {   // graphs captured under other launcher options
-    drop_step_graphs(h);
-    h->step_graphs_epoch = g_tun.epoch;
-  }
-  const StepGraphEntry* hit = nullptr;
-  for (auto& g : h->step_graphs)
-    if (g.cond == cond_nchw && g.noise == noise && g.out == out_nchw && g.traj == traj_nchw && g.ws == workspace &&
-        g.temb_table == h->d_temb_table && g.sched == h->d_step_sched && g.N == batch && g.H == height && g.W == width &&
-        g.chunk == chunk && g.every == every)
-      hit = &g;
-  if (!hit) {
-    // three single-stream captures: head, `chunk` steps, T % chunk steps
-    StepGraphEntry ge{cond_nchw, noise, out_nchw, traj_nchw, workspace, h->d_temb_table, h->d_step_sched,
-                      batch, height, width, chunk, every, nullptr, nullptr, nullptr};
-    auto capture = [&](int steps, hipGraphExec_t* exec) -> int {
-      hipGraph_t graph = nullptr;
-      HIPCHK(h, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-      int r = steps < 0 ? stepwise_head(h, cond_nchw, noise, batch, height, width, ws, st) : FDSR_OK;
-      for (int k = 0; k < steps && !r; ++k) r = stepwise_step(h, noise, out_nchw, traj_nchw, batch, height, width, ws, st, every);
-      hipError_t e = hipStreamEndCapture(st, &graph);
-      if (r) { if (graph) (void)hipGraphDestroy(graph); return r; }
-      if (e != hipSuccess) return fail(h, FDSR_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-      e = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      if (e != hipSuccess) return fail(h, FDSR_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-      return FDSR_OK;
-    };
-    rc = capture(-1, &ge.head);
-    if (!rc) rc = capture(chunk, &ge.body);
-    if (!rc && T % chunk) rc = capture(T % chunk, &ge.rem);
-    if (rc) { destroy_step_graph(ge); return rc; }
-    if (h->step_graphs.size() >= 8) {
-      destroy_step_graph(h->step_graphs.front());
-      h->step_graphs.erase(h->step_graphs.begin());
-    }
-    h->step_graphs.push_back(ge);
-    hit = &h->step_graphs.back();
-  }
-  HIPCHK(h, hipGraphLaunch(hit->head, st));
-  for (int c = 0; c < T / chunk; ++c) HIPCHK(h, hipGraphLaunch(hit->body, st));
-  if (hit->rem) HIPCHK(h, hipGraphLaunch(hit->rem, st));
-  return FDSR_OK;
-}
-
-int fdsr_set_seed(fdsr_handle h, uint64_t seed) {
-  if (!h) return FDSR_E_INVALID;
-  h->rng_seed = seed;
-  h->drop_seed = seed;   // one seed call covers both generators unless fdsr_set_dropout_seed overrides it
-  h->drop_step = 0;
-  if (h->d_rng) {
-    const unsigned long long init[2] = {seed, 0ull};
-    HIPCHK(h, hipMemcpy(h->d_rng, init, sizeof(init), hipMemcpyHostToDevice));
-  }
-  return FDSR_OK;
-}
-
-int fdsr_randn(fdsr_handle h, float* dst_nchw, int batch, int height, int width, int plane, void* hip_stream) {
-  if (!h || !dst_nchw || batch < 1 || height < 1 || width < 1 || plane < 0) return fail(h, FDSR_E_INVALID, "bad fdsr_randn arguments");
-  int rc = ensure_rng(h);
-  if (rc) return rc;
-  HIPCHK(h, launch_randn_plane(h->d_rng, dst_nchw, batch, height * width, plane, reinterpret_cast<hipStream_t>(hip_stream)));
   return FDSR_OK;
 }
 

@@ -1,9 +1,10 @@
 // Internal types of the engine shared by fdsr_plan.cpp (the static plan: ops, tensors, weight schema), fdsr_engine.cpp
-// (workspace planning, forward, sampling, C ABI), fdsr_forms.cpp (weight forms: freshness record and packing) and fdsr_train.cpp
-// (backward pass, Adam).  Not part of the C ABI (include/fdsr.h).
+// (workspace planning, forward, C ABI), fdsr_sample.cpp (the sampling loop and its captured graphs), fdsr_forms.cpp (weight forms:
+// freshness record and packing) and fdsr_train.cpp (backward pass, Adam).  Not part of the C ABI (include/fdsr.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -92,17 +93,12 @@ struct ShapePlan {
   std::vector<char> gsum_wanted[4];   // per precision, per tensor: some GroupNorm'd conv that reads it would form its statistics itself at this shape
 };
 
-struct GraphEntry {
-  const void *cond, *noise, *out, *traj, *ws;
-  int N, H, W;
-  hipGraphExec_t exec;
-};
-
-// fdsr_sample_stepwise under FDSR_SAMPLE_GRAPH: the prologue, one chunk of `chunk` steps and the T % chunk remainder
-struct StepGraphEntry {
+// One captured sampling call.  fdsr_sample (chunk == 0): the whole T-step loop in exec[0].  fdsr_sample_stepwise: the prologue, one
+// chunk of `chunk` steps and the T % chunk remainder (null when chunk divides T).
+struct SampleGraph {
   const void *cond, *noise, *out, *traj, *ws, *temb_table, *sched;
   int N, H, W, chunk, every;
-  hipGraphExec_t head, body, rem;   // rem: null when chunk divides T
+  hipGraphExec_t exec[3];
 };
 
 // One transposed form of a conv weight (input-gradient convolutions): towards one concat source, or towards all input channels
@@ -169,14 +165,12 @@ struct fdsr_engine {
   std::vector<hipEvent_t> ev_pool;
   size_t ev_used = 0;
   double prof_flops = 0, prof_bytes = 0;
-  std::vector<GraphEntry> graphs;
-  unsigned graphs_epoch = 0;
+  std::vector<SampleGraph> graphs, step_graphs;   // captured by fdsr_sample / fdsr_sample_stepwise
+  unsigned graphs_epoch = 0;                       // fdsr::g_tun.epoch they were captured under
   // fdsr_sample_stepwise: device-resident step state, allocated on first use (not part of the workspace)
   int* d_step_ctl = nullptr;        // step counter, then (256 bytes on) the current StepRecord
   float* d_step_row = nullptr;      // [TE]: the current step's noise-embedding row
   float* d_step_sched = nullptr;    // [5][T]: device copy of the posterior scalars
-  std::vector<StepGraphEntry> step_graphs;
-  unsigned step_graphs_epoch = 0;
   // ---- training state (fdsr_train.cpp) ----
   float* d_master = nullptr;          // every live checkpoint tensor in checkpoint layout, concatenated in schema order
   std::vector<size_t> master_off;     // per weight entry: float offset into d_master (SIZE_MAX: dead / synthetic)
@@ -221,13 +215,17 @@ int build_plan(fdsr_handle h);   // ops, tensors and weight schema from h->cfg (
 // fdsr_engine.cpp
 int get_plan(fdsr_handle h, int N, int H, int W);
 int check_ready(fdsr_handle h, bool need_schedule);
-int check_ws(fdsr_handle h, void* ws, size_t bytes);
-int ensure_rng(fdsr_handle h);
+int plan_ready(fdsr_handle h, bool need_schedule, int N, int H, int W, void* ws, size_t bytes);   // check_ready, get_plan, then the workspace checks
 int run_unet(fdsr_handle h, int N, int H, int W, char* ws, const float* nl_dev, float nl_scalar, hipStream_t st,
              const float* temb_row = nullptr);
+// fdsr_sample.cpp
+int ensure_rng(fdsr_handle h);
+int fill_temb(fdsr_handle h, float* temb, int N, const float* nl_dev, float nl_scalar, hipStream_t st);
 int build_temb_table(fdsr_handle h, hipStream_t st);   // pass TEMB_TABLE
 int upload_step_sched(fdsr_handle h);                  // pass STEP_SCHED
 void drop_captures(fdsr_handle h);                     // destroys the captured sampling graphs of both entry points
+// captures body()'s launches on st into *exec; h may be null (errors then go to the global message)
+int capture_exec(fdsr_handle h, hipStream_t st, const std::function<int()>& body, hipGraphExec_t* exec);
 // fdsr_forms.cpp
 int apply_plan(fdsr_handle h, const fdsr_forms::Plan& p, hipStream_t st);   // runs the passes in order (device passes on st), then drops the captures
 int pack_weight_host(fdsr_handle h, WeightEntry& w, const float* host);

@@ -1387,16 +1387,8 @@ int fdsr_nafnet_sample(fdsr_nafnet n, const float* state_nchw, const float* cond
   if (!(g.exec && g.cond == cond_nchw && g.noise == noise && g.out == out_nchw && g.traj == traj && g.ws == workspace && g.N == batch &&
         g.H == height && g.W == width && g.flags == flags && g.seed == seed && g.first == first_image)) {
     drop_graph(n);
-    hipGraph_t graph = nullptr;
-    HIPCHK(nullptr, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    rc = step();
-    const hipError_t e = hipStreamEndCapture(st, &graph);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    if (e != hipSuccess) return fail(nullptr, FDSR_E_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
     hipGraphExec_t exec = nullptr;
-    const hipError_t e2 = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (e2 != hipSuccess) return fail(nullptr, FDSR_E_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e2));
+    if ((rc = capture_exec(nullptr, st, step, &exec))) return rc;
     g.cond = cond_nchw; g.noise = noise; g.out = out_nchw; g.traj = traj; g.ws = workspace;
     g.N = batch; g.H = height; g.W = width; g.flags = flags; g.seed = seed; g.first = first_image; g.exec = exec;
   }

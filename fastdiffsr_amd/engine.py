@@ -215,20 +215,19 @@ class Engine:
             entry = lambda *a: self.lib.fdsr_sample_stepwise(*a, C.byref(opts))   # noqa: E731
         else:
             entry = self.lib.fdsr_sample
+        st = cur
         if graph and cur.cuda_stream == 0:
             # stream capture cannot run on the NULL stream: replay on a stream of our own, ordered after and
             # before the caller's current stream
             if self._gstream is None or self._gstream.device != cond.device:
                 self._gstream = torch.cuda.Stream(cond.device)
-            self._gstream.wait_stream(cur)
-            _lib.check(self.h, entry(*args, C.c_void_p(self._gstream.cuda_stream), flags))
-            cur.wait_stream(self._gstream)
-            self._keep = (cond, noise, out, traj)
-            self._saturation_check(self._gstream.cuda_stream)
-        else:
-            _lib.check(self.h, entry(*args, C.c_void_p(cur.cuda_stream), flags))
-            self._keep = (cond, noise, out, traj)
-            self._saturation_check(cur.cuda_stream)
+            st = self._gstream
+            st.wait_stream(cur)
+        _lib.check(self.h, entry(*args, C.c_void_p(st.cuda_stream), flags))
+        if st is not cur:
+            cur.wait_stream(st)
+        self._keep = (cond, noise, out, traj)
+        self._saturation_check(st.cuda_stream)
         return (out, traj) if want_traj else out
 
     def set_seed(self, seed):
