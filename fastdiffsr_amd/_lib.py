@@ -31,6 +31,7 @@ class FdsrSampleOpts(C.Structure):
 
 FDSR_NAFNET_MAX_LEVELS = 8
 FDSR_NAFNET_ODE = 2
+FDSR_NAF_STORE_F32, FDSR_NAF_STORE_F16 = 0, 1
 FDSR_NAFNET_LOSS_WEIGHTED = 256
 
 
@@ -139,6 +140,7 @@ SYMBOLS = {
     'fdsr_nafnet_optim_set_state': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64]),
     'fdsr_nafnet_destroy': (None, [C.c_void_p]),
     'fdsr_nafnet_set_precision': (C.c_int, [C.c_void_p, C.c_int]),
+    'fdsr_nafnet_set_storage': (C.c_int, [C.c_void_p, C.c_int]),
     'fdsr_nafnet_check_saturation': (C.c_int, [C.c_void_p, C.c_void_p]),
     'fdsr_set_debug': (C.c_int, [C.c_void_p, C.c_int]),
     'fdsr_debug_option': (C.c_int, [C.c_char_p, C.c_longlong]),

@@ -12,6 +12,8 @@
 // kernel on v_mfma_f32_32x32x2_f32: exact fp32, a k-ordered chain per output, no split-K, no atomics.  Pools are per-strip partial
 // sums added in a fixed order.  Every output element has one summation order that depends neither on B nor on the image's place
 // in the batch: reruns are bitwise identical.  LayerNorm: over channels per pixel, biased variance (two passes), eps 1e-5.
+// Two opt-in sampling modes pick other kernels in the same walk: FDSR_PREC_F16X3 (fdsr_nafnet_h3.h: the GEMMs on an fp32-grade f16 split)
+// and FDSR_NAF_STORE_F16 (fdsr_nafnet_h1.h: f16 activations in memory, one f16 MFMA per product).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -58,6 +60,8 @@ struct GemmArgs {
   const uint4* wq;
   float winv;
   int* sat;
+  // FDSR_NAF_STORE_F16 (naf_gemm_h1_kernel): x (but for intro's fp32 xin), res and out are f16; o32: out is fp32 (ending's eps)
+  int o32;
 };
 
 // One workgroup: BM output pixels x BN packed output columns; 4 waves, each 32 pixels x 64 columns (two 32x32 accumulators, so the
@@ -220,6 +224,7 @@ __global__ void __launch_bounds__(NT) naf_gemm_kernel(GemmArgs p) {
 }
 
 #include "fdsr_nafnet_h3.h"
+#include "fdsr_nafnet_h1.h"
 
 // LayerNorm statistics: (mean, 1 / sqrt(var + eps)) per pixel over C channels, biased variance, two passes.  16 lanes per pixel,
 // a butterfly of commutative adds: every lane ends with the same bits.
@@ -618,6 +623,7 @@ struct fdsr_nafnet_obj {
   bool dirty = true;
   // FDSR_PREC_F16X3: hi / lo planes of the forward GEMMs' weights (built by finalize in that mode) and the range flag
   int prec = FDSR_PREC_F32;
+  int store = FDSR_NAF_STORE_F32;   // FDSR_NAF_STORE_F16: f16 activations, the hi planes of d_wq, the same flag (fdsr_nafnet_h1.h)
   size_t hfrags = 0;
   uint4* d_wq = nullptr;
   int *d_sat = nullptr, *h_sat = nullptr;
@@ -905,7 +911,7 @@ int finalize(fdsr_nafnet n) {
   if (!n->d_arena) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_arena), a.size() * sizeof(float)));
   HIPCHK(nullptr, hipDeviceSynchronize());   // nothing in flight reads the old forms
   HIPCHK(nullptr, hipMemcpy(n->d_arena, a.data(), a.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (n->prec == FDSR_PREC_F16X3) {
+  if (n->prec == FDSR_PREC_F16X3 || n->store == FDSR_NAF_STORE_F16) {
     const std::vector<uint16_t> q = split_weights(n, a);
     if (!n->d_wq) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_wq), q.size() * sizeof(uint16_t)));
     HIPCHK(nullptr, hipMemcpy(n->d_wq, q.data(), q.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
@@ -998,7 +1004,13 @@ NetDst sample_dst(fdsr_nafnet n, int N, int H, int W, void* workspace) {
 }
 
 typedef void (*GemmFn)(GemmArgs);
-template <int PRO, bool VEC> GemmFn gemm_fn(bool h3) { return h3 ? naf_gemm_h3_kernel<PRO, VEC> : naf_gemm_kernel<PRO, VEC>; }
+enum { FORM_F32 = 0, FORM_H3 = 1, FORM_H1 = 2 };
+template <int PRO, bool VEC> GemmFn gemm_fn(int form) {
+  return form == FORM_H1 ? naf_gemm_h1_kernel<PRO, VEC> : form == FORM_H3 ? naf_gemm_h3_kernel<PRO, VEC> : naf_gemm_kernel<PRO, VEC>;
+}
+// an activation slot under FDSR_NAF_STORE_F16: the first half of the fp32 slot, as f16
+inline _Float16* H(float* p) { return reinterpret_cast<_Float16*>(p); }
+inline const _Float16* H(const float* p) { return reinterpret_cast<const _Float16*>(p); }
 
 struct Run {
   fdsr_nafnet n;
@@ -1022,8 +1034,9 @@ struct Run {
     hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
     check();
   }
-  void copy(float* dst, const float* src, size_t floats) {
-    (void)hipMemcpyAsync(dst, src, floats * sizeof(float), hipMemcpyDeviceToDevice, st);
+  bool h1() const { return n->store == FDSR_NAF_STORE_F16; }
+  void copy(float* dst, const float* src, size_t elems) {   // an activation: f16 elements under h1
+    (void)hipMemcpyAsync(dst, src, elems * (h1() ? sizeof(_Float16) : sizeof(float)), hipMemcpyDeviceToDevice, st);
     check();
   }
   bool tap(const std::string& name, const float* ptr, int h, int w, int c) {
@@ -1048,20 +1061,34 @@ struct Run {
     a.pstride = pstride; a.epi = epi;
     const int M = d.N * a.Hout * a.Wout;
     const dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(a.CoutPad / BN));
-    const bool h3 = n->prec == FDSR_PREC_F16X3;
-    if (h3) {
+    const int form = h1() ? FORM_H1 : n->prec == FDSR_PREC_F16X3 ? FORM_H3 : FORM_F32;
+    if (form != FORM_F32) {
       if (out2 || !g.split) {
-        if (err == FDSR_OK) err = fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet: this GEMM has no f16x3 form");
+        if (err == FDSR_OK) err = fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet: this GEMM has no f16 form");
         return;
       }
       a.wq = n->d_wq + g.hoff; a.winv = g.hinv; a.sat = n->d_sat;
+      a.o32 = out == d.eps;
     }
-    const GemmFn k = g.cin % 8 ? gemm_fn<PRO_NONE, false>(h3) : pro == PRO_LN ? gemm_fn<PRO_LN, true>(h3)
-                     : pro == PRO_MUL ? gemm_fn<PRO_MUL, true>(h3) : gemm_fn<PRO_NONE, true>(h3);
+    const GemmFn k = g.cin % 8 ? gemm_fn<PRO_NONE, false>(form) : pro == PRO_LN ? gemm_fn<PRO_LN, true>(form)
+                     : pro == PRO_MUL ? gemm_fn<PRO_MUL, true>(form) : gemm_fn<PRO_NONE, true>(form);
     launch(k, grid, dim3(NT), 0, a);
   }
 
-  void ln_stats(const float* x, float* stats, int M, int C) { launch(naf_ln_stats_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, x, stats, M, C); }
+  void ln_stats(const float* x, float* stats, int M, int C) {
+    if (h1()) launch(naf_ln_stats_h_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, H(x), stats, M, C);
+    else launch(naf_ln_stats_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, x, stats, M, C);
+  }
+  void dw_gate(const BlockL& b, const float* x, float* y, int h, int w, int ns) {
+    const int c = b.c;
+    if (h1()) {
+      int lp_shift = 3;   // 2^lp_shift lanes, two channels each, cover a pixel: 8 (c = 16) .. 64
+      while (lp_shift < 6 && (2 << lp_shift) < c) ++lp_shift;
+      launch(naf_dw_gate_h_kernel, dim3((unsigned)ns, (unsigned)((c + (2 << lp_shift) - 1) / (2 << lp_shift)), (unsigned)d.N), dim3(256), 0, H(x),
+             P(b.off_dww), P(b.off_dwb), H(y), d.part, h, w, c, ns, lp_shift, n->d_sat);
+    } else launch(naf_dw_gate_kernel, dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)d.N), dim3(256), 0, x, P(b.off_dww), P(b.off_dwb), y,
+                d.part, h, w, c, ns);
+  }
 
   void block(int bi, const float* cur, int h, int w) {
     const BlockL& b = n->blocks[bi];
@@ -1070,8 +1097,7 @@ struct Run {
     const float* rw = rows + b.row_off;
     ln_stats(cur, s.st1, M, c);
     gemm(b.conv1, cur, s.t1, h, w, EPI_BIAS, PRO_LN, rw + c, rw, rstride, s.st1);
-    launch(naf_dw_gate_kernel, dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)d.N), dim3(256), 0, s.t1, P(b.off_dww), P(b.off_dwb), s.t2,
-           d.part, h, w, c, ns);
+    dw_gate(b, s.t1, s.t2, h, w, ns);
     launch(naf_sca_kernel, dim3((unsigned)((c + 15) / 16), (unsigned)d.N), dim3(256), (c + 256) * sizeof(float), d.part, ns, HW, P(b.off_scaw),
            P(b.off_scab), s.sca, c);
     gemm(b.conv3, s.t2, s.y, h, w, EPI_RES, PRO_MUL, s.sca, nullptr, c, nullptr, cur, P(b.off_beta));
@@ -1100,11 +1126,13 @@ struct Run {
     gemm(n->g_rcab0, d.intro, d.r1, h, w, EPI_RELU);
     gemm(n->g_rcab2, d.r1, d.r, h, w, EPI_BIAS);
     const int HW = h * w, ns = nstrips_of(HW);
-    launch(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)d.N), dim3(256), 0, d.r, d.part, HW, wd, ns);
+    if (h1()) launch(naf_chansum_h_kernel, dim3((unsigned)ns, (unsigned)((wd + 127) / 128), (unsigned)d.N), dim3(256), 0, H(d.r), d.part, HW, wd, ns);
+    else launch(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)d.N), dim3(256), 0, d.r, d.part, HW, wd, ns);
     launch(naf_ca_kernel, dim3((unsigned)d.N), dim3(256), (wd + 256 + wd / 16) * sizeof(float), d.part, ns, HW, P(n->off_ca1w), P(n->off_ca1b),
            P(n->off_ca2w), P(n->off_ca2b), d.ca, wd, wd / 16);
     const size_t total = (size_t)d.N * HW * wd;
-    launch(naf_enhance_kernel, dim3(nb(total)), dim3(256), 0, d.intro, d.r, d.ca, d.enh, HW, wd, total);
+    if (h1()) launch(naf_enhance_h_kernel, dim3(nb(total / 8)), dim3(256), 0, H(d.intro), H(d.r), d.ca, H(d.enh), HW, wd, total / 8, n->d_sat);
+    else launch(naf_enhance_kernel, dim3(nb(total)), dim3(256), 0, d.intro, d.r, d.ca, d.enh, HW, wd, total);
     if (tap("enhance", d.enh, h, w, wd)) return;
     for (int i = 0; i < L; ++i) {
       if (!chain(n->enc[i], i ? d.down[i - 1] : d.enh, d.skip[i], h, w, c)) return;
@@ -1264,6 +1292,9 @@ int fdsr_nafnet_weights_complete(fdsr_nafnet n) {
 int fdsr_nafnet_set_precision(fdsr_nafnet n, int mode) {
   if (!n || (mode != FDSR_PREC_F32 && mode != FDSR_PREC_F16X3))
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_set_precision: mode must be FDSR_PREC_F32 (0) or FDSR_PREC_F16X3 (1), not %d", mode);
+  if (mode == FDSR_PREC_F16X3 && n->store == FDSR_NAF_STORE_F16)
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_set_precision: FDSR_PREC_F16X3 while the storage is FDSR_NAF_STORE_F16: set the storage back "
+                                         "first (fdsr_nafnet_set_storage)");
   if (mode == n->prec) return FDSR_OK;
   // the device forms are rebuilt from the fp32 master through pack_forms by the next call that runs (finalize); after optimizer
   // steps the master is on the device
@@ -1275,17 +1306,35 @@ int fdsr_nafnet_set_precision(fdsr_nafnet n, int mode) {
   return FDSR_OK;
 }
 
+int fdsr_nafnet_set_storage(fdsr_nafnet n, int mode) {
+  if (!n || (mode != FDSR_NAF_STORE_F32 && mode != FDSR_NAF_STORE_F16))
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_set_storage: mode must be FDSR_NAF_STORE_F32 (0) or FDSR_NAF_STORE_F16 (1), not %d", mode);
+  if (mode == FDSR_NAF_STORE_F16 && n->prec == FDSR_PREC_F16X3)
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_set_storage: FDSR_NAF_STORE_F16 while the precision is FDSR_PREC_F16X3: set the precision "
+                                         "back first (fdsr_nafnet_set_precision)");
+  if (mode == n->store) return FDSR_OK;
+  const int rc = host_from_master(n);   // as a precision switch: the forms (here: the hi planes) are rebuilt by the next call that runs
+  if (rc) return rc;
+  n->store = mode;
+  n->dirty = true;
+  drop_graph(n);
+  return FDSR_OK;
+}
+
 int fdsr_nafnet_check_saturation(fdsr_nafnet n, void* hip_stream) {
   if (!n) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_check_saturation: null object");
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   HIPCHK(nullptr, hipStreamSynchronize(st));
-  if (n->prec != FDSR_PREC_F16X3 || !n->d_sat) return FDSR_OK;
+  if ((n->prec != FDSR_PREC_F16X3 && n->store != FDSR_NAF_STORE_F16) || !n->d_sat) return FDSR_OK;
   if (!n->h_sat) HIPCHK(nullptr, hipHostMalloc(reinterpret_cast<void**>(&n->h_sat), 64, hipHostMallocDefault));
   *n->h_sat = 0;
   HIPCHK(nullptr, hipMemcpyAsync(n->h_sat, n->d_sat, sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(nullptr, hipStreamSynchronize(st));
   if (!*n->h_sat) return FDSR_OK;
   HIPCHK(nullptr, hipMemsetAsync(n->d_sat, 0, sizeof(int), st));
+  if (n->store == FDSR_NAF_STORE_F16)
+    return fail(nullptr, FDSR_E_SATURATED, "f16 storage: an activation of the NAFNet exceeded the f16 range (+-65504) and was clamped; "
+                                           "re-run this call after fdsr_nafnet_set_storage(FDSR_NAF_STORE_F32)");
   return fail(nullptr, FDSR_E_SATURATED, "f16x3: a GEMM input of the NAFNet exceeded the f16 range (+-65504) and was clamped; "
                                          "re-run this call after fdsr_nafnet_set_precision(FDSR_PREC_F32)");
 }
@@ -1350,6 +1399,10 @@ int fdsr_nafnet_debug_tensor(fdsr_nafnet n, const char* name, const float* x_nch
   const size_t count = (size_t)batch * r.tap_h * r.tap_w * r.tap_c;
   if (count > capacity_floats) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_debug_tensor: '%s' needs %zu floats", name, count);
   dims3[0] = r.tap_h; dims3[1] = r.tap_w; dims3[2] = r.tap_c;
+  if (r.h1() && r.tap_ptr != r.d.eps) {   // the stored f16 values, widened
+    r.launch(naf_widen_h_kernel, dim3(Run::nb(count)), dim3(256), 0, H(r.tap_ptr), out_nhwc, count);
+    return r.err;
+  }
   HIPCHK(nullptr, hipMemcpyAsync(out_nhwc, r.tap_ptr, count * sizeof(float), hipMemcpyDeviceToDevice, r.st));
   return FDSR_OK;
 }

@@ -898,6 +898,8 @@ int fdsr_nafnet_train_grads(fdsr_nafnet n, const float* state_nchw, const float*
   if (loss_type != FDSR_NAFNET_LOSS_L1 && loss_type != FDSR_NAFNET_LOSS_L2) return fail(nullptr, FDSR_E_INVALID, "%s: loss_type %d (l1 = 0, l2 = 1)", fn, loss_type);
   int rc = check_args(n, fn, batch, height, width, workspace, workspace_bytes, train_plan_bytes);
   if (rc) return rc;
+  if (n->store != FDSR_NAF_STORE_F32)
+    return fail(nullptr, FDSR_E_INVALID, "%s: training runs on fp32 activations only, the object is in FDSR_NAF_STORE_F16, f16 storage (fdsr_nafnet_set_storage)", fn);
   if (n->prec != FDSR_PREC_F32)
     return fail(nullptr, FDSR_E_INVALID, "%s: training runs in FDSR_PREC_F32 only, the object is in f16x3 (fdsr_nafnet_set_precision)", fn);
   if (n->T < 1 || n->cum_T != n->T) return fail(nullptr, FDSR_E_STATE, "%s: no schedule (fdsr_nafnet_set_sde, fdsr_nafnet_set_thetas_cumsum)", fn);
@@ -948,6 +950,8 @@ int fdsr_nafnet_optim_step(fdsr_nafnet n, int kind, double lr, double beta1, dou
   if (!n || kind < FDSR_NAFNET_ADAM || kind > FDSR_NAFNET_LION || !(lr >= 0.) || !(beta1 >= 0. && beta1 < 1.) || !(beta2 >= 0. && beta2 < 1.) ||
       !(eps >= 0.) || !(weight_decay >= 0.))
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_optim_step: bad arguments (kind %d)", kind);
+  if (n->store != FDSR_NAF_STORE_F32)
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_optim_step: training runs on fp32 activations only, the object is in FDSR_NAF_STORE_F16, f16 storage");
   if (n->prec != FDSR_PREC_F32)   // the device-side re-pack below writes the fp32 forms only
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_optim_step: training runs in FDSR_PREC_F32 only, the object is in f16x3");
   if (!n->d_grad || !n->master_valid || n->dirty) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet_optim_step: no gradients (fdsr_nafnet_train_grads first)");

@@ -165,26 +165,38 @@ class ConditionalNAFNet(nn.Module):
         th, tw, tc = dims[0], dims[1], dims[2]
         return out[:b * th * tw * tc].view(b, th, tw, tc).permute(0, 3, 1, 2).contiguous()
 
-    # ---- precision of the GEMMs (include/fdsr.h: fdsr_nafnet_set_precision) ----
-    PRECISIONS = ('f32', 'f16x3')
+    # ---- precision of the GEMMs and storage of the activations (include/fdsr.h: fdsr_nafnet_set_precision, _set_storage) ----
+    PRECISIONS = ('f32', 'f16x3', 'f16')
 
     @property
     def precision(self):
         return getattr(self, '_precision', 'f32')
 
     def set_precision(self, mode):
-        """'f32' (exact, the default) or 'f16x3' (fp32-grade, three f16 MFMAs per product).  forward, debug_tensor and sample
-        follow the mode; training runs in 'f32' only."""
+        """'f32' (exact, the default), 'f16x3' (fp32-grade, three f16 MFMAs per product, fp32 activations) or 'f16' (PSNR-grade:
+        f16 activations in memory, one f16 MFMA per product, fp32 accumulators).  forward, debug_tensor and sample follow the
+        mode; training runs in 'f32' only: train_grads and optim_step raise what the engine says under 'f16x3' and 'f16'.
+        'f16x3' and 'f16' are two settings of one switch: 'f16' is not reached from 'f16x3' directly (ValueError, as the engine
+        refuses f16 storage under the f16x3 precision) but through 'f32'."""
         if mode not in self.PRECISIONS:
             raise ValueError('precision must be one of %s, not %r' % (self.PRECISIONS, mode))
+        if mode == 'f16' and self.precision == 'f16x3':
+            raise ValueError("precision 'f16' is not set over 'f16x3': set 'f32' first")
+        lib, h = _lib.load(), self._handle()
         dev = next(self.parameters()).device
         with torch.cuda.device(dev) if dev.type == 'cuda' else contextlib.nullcontext():
-            _lib.check(None, _lib.load().fdsr_nafnet_set_precision(self._handle(), _lib.PRECISIONS[mode]))
+            # two settings of one switch in the engine: 'f16' is f16 storage over the F32 GEMM precision
+            if mode != 'f16':
+                _lib.check(None, lib.fdsr_nafnet_set_storage(h, _lib.FDSR_NAF_STORE_F32))
+            _lib.check(None, lib.fdsr_nafnet_set_precision(h, _lib.PRECISIONS['f32' if mode == 'f16' else mode]))
+            if mode == 'f16':
+                _lib.check(None, lib.fdsr_nafnet_set_storage(h, _lib.FDSR_NAF_STORE_F16))
         self._precision = mode
 
     def check_saturation(self):
-        """f16x3 clamps GEMM inputs beyond +-65504 and raises a sticky flag: synchronises, reads and clears it.  Raises
-        _lib.FdsrSaturated when it was set (re-run the calls since the last check in 'f32'); a no-op in 'f32'."""
+        """f16x3 clamps GEMM inputs beyond +-65504 and raises a sticky flag, f16 does so for every value it stores or stages:
+        synchronises, reads and clears it.  Raises _lib.FdsrSaturated when it was set (re-run the calls since the last check
+        in 'f32'); a no-op in 'f32'."""
         dev = next(self.parameters()).device
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream

@@ -1,15 +1,16 @@
 """EDiffSR's config/sisr/test.py on the HIP engine, driven by the reference's own YAML options:
 
     python -m fastdiffsr_amd.ediffsr.test -opt setting_mfe_Test_x4.yml [--batch N] [--rng engine] [--seed S] [--graph]
-                                          [--precision f32|f16x3] [--results DIR] [--lpips BACKBONE.pth LIN.pth]
+                                          [--precision f32|f16x3|f16] [--results DIR] [--lpips BACKBONE.pth LIN.pth]
 
 Reads `sde`, `degradation.scale`, `datasets.test*` (dataroot_GT / dataroot_LQ), `network_G.setting`, `path.pretrain_model_G`.
 Per batch: LQ -> bicubic upscale on the device -> IRSDE.noise_state -> reverse_sde -> tensor2img (min_max (0, 1)) -> PSNR /
 SSIM (11x11 Gaussian) / ERGAS [/ LPIPS] through the device metrics -> one RGB PNG per image -> the reference's log lines.
 --rng engine draws x_T's noise and the per-step noise from the library's Philox stream at positions of the image's index in the
 dataset, so the per-image results do not depend on --batch; --rng torch (default) draws from torch's generator like the reference.
---precision f16x3 runs the network's GEMMs on the fp32-grade f16 split (include/fdsr.h: fdsr_nafnet_set_precision); the range
-guard is read once per batch, and a batch that raised it is run again in f32 with a warning.
+--precision f16x3 runs the network's GEMMs on the fp32-grade f16 split (include/fdsr.h: fdsr_nafnet_set_precision); --precision
+f16 keeps the activations as f16 in memory and takes one f16 MFMA per product (fdsr_nafnet_set_storage: PSNR-grade, not
+fp32-grade).  Under either the range guard is read once per batch, and a batch that raised it is run again in f32 with a warning.
 Single process.  Returns {dataset name: {'psnr', 'ssim', 'ergas', 'lpips', 'per_image', 'time'}}."""
 import argparse
 import logging
@@ -77,20 +78,21 @@ def run_dataset(opt, ds, net, sde, device, results, batch=1, rng='torch', seed=0
         else:
             state = sde.noise_state(mu)
         sde.set_mu(mu)
-        if net.precision == 'f16x3' and rng == 'torch':
+        mode = net.precision
+        if mode in ('f16x3', 'f16') and rng == 'torch':
             rng_state = torch.cuda.get_rng_state(device)      # a re-run in f32 draws the same per-step noise
         sr = sde.reverse_sde(state)
-        if net.precision == 'f16x3':
+        if mode in ('f16x3', 'f16'):
             try:
                 net.check_saturation()
             except _lib.FdsrSaturated:
                 logging.getLogger('fastdiffsr_amd.ediffsr').warning(
-                    'images %d..%d left the f16 range under --precision f16x3: running the batch again in f32', b0, b0 + len(part) - 1)
+                    'images %d..%d left the f16 range under --precision %s: running the batch again in f32', b0, b0 + len(part) - 1, mode)
                 net.set_precision('f32')
                 if rng == 'torch':
                     torch.cuda.set_rng_state(rng_state, device)
                 sr = sde.reverse_sde(state)
-                net.set_precision('f16x3')
+                net.set_precision(mode)
         sr_u8 = M.tensor2img_batch(sr, min_max=(0, 1))
         torch.cuda.synchronize(device)
         times.append((time.time() - tic) / len(part))
@@ -124,7 +126,7 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--graph', action='store_true', help='replay one captured step')
     ap.add_argument('--precision', choices=ConditionalNAFNet.PRECISIONS, default='f32',
-                    help='the GEMMs: exact fp32 (default) or the fp32-grade f16 split')
+                    help='the GEMMs: exact fp32 (default), the fp32-grade f16 split, or f16 activations with one f16 MFMA per product')
     ap.add_argument('--results', default=None, help='output folder (default: results/<name> next to the options\' own tree)')
     ap.add_argument('--lpips', nargs=2, default=None, metavar=('BACKBONE', 'LIN'), help='AlexNet features and LPIPS v0.1 heads')
     a = ap.parse_args(argv)

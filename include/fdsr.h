@@ -376,13 +376,40 @@ void fdsr_nafnet_destroy(fdsr_nafnet n);
  *                             do not change.  Any other mode: FDSR_E_INVALID.  A switch drops the cached graph and rebuilds the
  *                             device weight forms from the fp32 master (after optimizer steps: the trained weights) on the next
  *                             call.  fdsr_nafnet_forward / _debug_tensor / _sample follow the mode; fdsr_nafnet_train_grads and
- *                             fdsr_nafnet_optim_step run in FDSR_PREC_F32 only (FDSR_E_INVALID under f16x3).
+ *                             fdsr_nafnet_optim_step run in FDSR_PREC_F32 only (FDSR_E_INVALID under f16x3, and under f16 storage).
  *   fdsr_nafnet_check_saturation   f16x3 clamps a GEMM input beyond +-65504 to the f16 range and raises a sticky device flag (so does a NaN).
  *                             This call synchronises hip_stream, reads and clears the flag: FDSR_OK or FDSR_E_SATURATED (the
  *                             outputs since the last check are then not fp32-grade: re-run them in FDSR_PREC_F32, which has no
- *                             such limit).  Always FDSR_OK in FDSR_PREC_F32. */
+ *                             such limit).  FDSR_NAF_STORE_F16 raises the same flag from its stores too.  Always FDSR_OK in FDSR_PREC_F32
+ *                             with FDSR_NAF_STORE_F32. */
 int fdsr_nafnet_set_precision(fdsr_nafnet n, int mode);
 int fdsr_nafnet_check_saturation(fdsr_nafnet n, void* hip_stream);
+/* Storage of the NAFNet's activations: the 16-bit, PSNR-grade sampling mode (11 mantissa bits; not fp32-grade).
+ *   fdsr_nafnet_set_storage   FDSR_NAF_STORE_F32 (default) or FDSR_NAF_STORE_F16; any other value: FDSR_E_INVALID.  Storage and
+ *                             precision are two settings of one switch: FDSR_NAF_STORE_F16 while the precision is FDSR_PREC_F16X3,
+ *                             and fdsr_nafnet_set_precision(FDSR_PREC_F16X3) while the storage is F16, are FDSR_E_INVALID:
+ *                             leave one setting (back to F32) before taking the other.  A change
+ *                             drops the cached graph and rebuilds the device weight forms on the next call, as a precision switch
+ *                             does.  fdsr_nafnet_forward / _debug_tensor / _sample follow the mode (SDE and ODE, eager and graph,
+ *                             given and engine-drawn noise); fdsr_nafnet_train_grads and fdsr_nafnet_optim_step return
+ *                             FDSR_E_INVALID under F16 storage.  fdsr_nafnet_workspace_bytes does not change: an f16 tensor lies in
+ *                             the first half of its fp32 slot.  fdsr_nafnet_debug_tensor returns the stored values widened to fp32.
+ *     Arithmetic under FDSR_NAF_STORE_F16.  Stored as f16 (NHWC) between kernels: intro, the RCAB's two convolution outputs,
+ *       x + enhance(x), every block's conv1 output, depthwise + gate output, y, conv4's gate output and out, the skips, downs,
+ *       middle, ups and decoder results.  Kept in fp32: the 6-channel network input, ending's 3-channel output, LayerNorm statistics,
+ *       strip sums, SCA / CA vectors, time rows and their table, the SDE state, cond, noise, trajectory, and all of the prep, tail
+ *       and upscale kernels.  A kernel widens what it reads (exact), computes as the fp32 kernel does and rounds once, to nearest
+ *       even, where it stores; the strip sums a kernel forms beside its output come from the fp32 values before that rounding.
+ *       GEMMs: the staged operand -- fp32 after LN + FiLM or the SCA multiply, or the f16 input as it is -- is rounded to f16 once;
+ *       the weight is f16(w 2^e), the hi plane of the f16x3 split forms; every product is one v_mfma_f32_32x32x16_f16 into an fp32
+ *       accumulator, chunk after chunk in k order (no split-K, no atomics: the bitwise properties above hold); the epilogue -- bias,
+ *       ReLU, gate product, res + v evec with res read as f16, PixelShuffle + skip -- is the fp32 kernel's on acc 2^-e, rounded
+ *       once at the store.
+ *     Range: a value to be stored or staged beyond +-65504, or a NaN, is clamped and raises the sticky flag that
+ *       fdsr_nafnet_check_saturation reads (FDSR_E_SATURATED), in every kernel that stores f16: the mode does not saturate silently. */
+#define FDSR_NAF_STORE_F32 0
+#define FDSR_NAF_STORE_F16 1
+int fdsr_nafnet_set_storage(fdsr_nafnet n, int mode);
 
 /* EDiffSR training: one step of DenoisingModel.optimize_parameters (models/denoising_model.py) on the device, fp32.
  *   fdsr_nafnet_set_thetas_cumsum   IRSDE.thetas_cumsum [T+1] host fp32, after fdsr_nafnet_set_sde (which forgets it).

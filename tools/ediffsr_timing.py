@@ -1,6 +1,6 @@
 """EDiffSR sampling times on one GPU -> profiles/ediffsr_timing.txt (or --out).
 
-    python tools/ediffsr_timing.py [--out FILE] [--size 256] [--steps 100] [--baseline] [--precision f32|f16x3]
+    python tools/ediffsr_timing.py [--out FILE] [--size 256] [--steps 100] [--baseline] [--precision f32|f16x3|f16]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/ediffsr_timing.py --forward-only     # per-kernel split of forwards
 
 Shipped setting (width 64, enc [14,1,1,1]), synthetic weights, T = --steps, B = 1 and B = 16, eager and graph: ms per image,
@@ -60,7 +60,7 @@ def main():
     ap.add_argument('--batches', type=int, nargs='+', default=[1, 16])
     ap.add_argument('--baseline', action='store_true')
     ap.add_argument('--forward-only', action='store_true')
-    ap.add_argument('--precision', choices=('f32', 'f16x3'), default='f32')
+    ap.add_argument('--precision', choices=('f32', 'f16x3', 'f16'), default='f32')
     a = ap.parse_args()
     from fastdiffsr_amd.ediffsr import ConditionalNAFNet, IRSDE
     from fastdiffsr_amd.synth import synth_nafnet
@@ -74,7 +74,8 @@ def main():
     sde.set_model(net)
     lines = ['EDiffSR timing: %s, width 64 enc [14,1,1,1], %dx%d, T = %d, %s, engine-drawn noise'
              % (torch.cuda.get_device_name(0), a.size, a.size, a.steps,
-                'fp32 (exact-fp32 MFMA)' if a.precision == 'f32' else 'f16x3 (three f16 MFMAs per product, fp32 accumulate)')]
+                {'f32': 'fp32 (exact-fp32 MFMA)', 'f16x3': 'f16x3 (three f16 MFMAs per product, fp32 accumulate)',
+                 'f16': 'f16 (f16 activations in memory, one f16 MFMA per product, fp32 accumulate)'}[a.precision])]
     fl = conv1x1_flops(SETTING, a.size, a.size)
     for b in a.batches:
         g = torch.Generator().manual_seed(b)
@@ -99,7 +100,7 @@ def main():
                 med, lo, hi = timed(lambda: R.forward(dsd, state, cond, torch.full((1,), 50.0, device=dev)), 10)
             lines.append('baseline  B=%-2d forward  %8.3f ms/image (stock PyTorch, fp32, the restatement; x %d steps = %.1f ms/image)'
                          % (b, med / b, a.steps, med / b * a.steps))
-    if a.precision == 'f16x3':
+    if a.precision != 'f32':
         net.check_saturation()   # raises if any timed call left the f16 range
         lines.append('range guard: clear')
     text = '\n'.join(lines) + '\n'
