@@ -132,6 +132,12 @@ SYMBOLS = {
     'fdsr_nafnet_train_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
     'fdsr_nafnet_train_grads': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int,
                                           C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'fdsr_nafnet_forward_train': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_size_t, C.POINTER(C.c_int64), C.c_void_p]),
+    'fdsr_nafnet_backward': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
+    'fdsr_nafnet_copy_grads': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'fdsr_nafnet_set_weights_flat': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'fdsr_nafnet_grad_buffer': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     'fdsr_nafnet_read_grad': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p]),
     'fdsr_nafnet_optim_step': (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),

@@ -634,6 +634,9 @@ struct fdsr_nafnet_obj {
   bool host_stale = false;     // an optimizer step moved the weights on: the host copies are behind d_master
   long long opt_step = 0;
   int cum_T = 0;
+  // the autograd bridge (fdsr_nafnet_forward_train / _backward): the ticket of the activations a training workspace holds (0: none),
+  // the call they belong to, and what made the last ticket stale
+  struct { long long next = 0, live = 0; int N = 0, H = 0, W = 0; const void* ws = nullptr; const char* killer = "no fdsr_nafnet_forward_train yet"; } ticket;
   // IR-SDE
   int T = 0;
   std::vector<float> thetas, sigmas, sbars;
@@ -649,6 +652,12 @@ struct fdsr_nafnet_obj {
 };
 
 namespace {
+
+// the activations fdsr_nafnet_forward_train kept are overwritten, or no longer those of the weights: its ticket is stale from here on
+void kill_ticket(fdsr_nafnet n, const char* by) {
+  if (n->ticket.live) n->ticket.killer = by;
+  n->ticket.live = 0;
+}
 
 void drop_graph(fdsr_nafnet n) {
   if (n->graph.exec) (void)hipGraphExecDestroy(n->graph.exec);
@@ -763,7 +772,7 @@ void build_schema(fdsr_nafnet n) {
   n->off_rowsb = take(off, n->R);
   n->off_rowsadd = take(off, n->R);
   n->off_rowsmul = take(off, n->R);
-  // training: the transposed convolutions (cin == 0: no input gradient is needed -- intro reads data) and a zero bias for them
+  // training: the transposed convolutions (intro's, 64 -> 6, serves fdsr_nafnet_backward's d x / d cond only) and a zero bias for them
   int zmax = 64;
   for (const GemmL& g : n->gemms) {
     GemmL t;
@@ -771,11 +780,8 @@ void build_schema(fdsr_nafnet n) {
     else if (g.ks == 2) { t.cin = g.cout; t.cout = 4 * g.cin; }
     else if (g.b < 0) { t.cin = g.cout / 4; t.cout = g.cin; t.ks = 2; t.s = 2; }
     else { t.cin = g.cout; t.cout = g.cin; }
-    if (&g == &n->gemms[n->g_intro]) t.cin = 0;
-    if (t.cin) {
-      t.woff = take(off, (size_t)t.Kpad() * t.CoutPad());
-      zmax = std::max(zmax, t.CoutPad());
-    }
+    t.woff = take(off, (size_t)t.Kpad() * t.CoutPad());
+    zmax = std::max(zmax, t.CoutPad());
     n->tgemms.push_back(t);
   }
   n->off_zero = take(off, zmax);
@@ -849,7 +855,6 @@ void pack_forms(fdsr_nafnet n, S& s) {
   for (size_t gi = 0; gi < n->gemms.size(); ++gi) {
     const GemmL& g = n->gemms[gi];
     const GemmL& t = n->tgemms[gi];
-    if (t.cin == 0) continue;
     const int Cp = t.CoutPad();
     for (int co = 0; co < g.cout; ++co)
       for (int ci = 0; ci < g.cin; ++ci)
@@ -1278,6 +1283,7 @@ int fdsr_nafnet_load_weight(fdsr_nafnet n, const char* key, const float* host_f3
   w.loaded = true;
   n->dirty = true;
   n->table_valid = false;
+  kill_ticket(n, "fdsr_nafnet_load_weight (a weight load)");
   drop_graph(n);
   return FDSR_OK;
 }
@@ -1302,6 +1308,7 @@ int fdsr_nafnet_set_precision(fdsr_nafnet n, int mode) {
   if (rc) return rc;
   n->prec = mode;
   n->dirty = true;
+  kill_ticket(n, "fdsr_nafnet_set_precision (a precision switch)");
   drop_graph(n);
   return FDSR_OK;
 }
@@ -1317,6 +1324,7 @@ int fdsr_nafnet_set_storage(fdsr_nafnet n, int mode) {
   if (rc) return rc;
   n->store = mode;
   n->dirty = true;
+  kill_ticket(n, "fdsr_nafnet_set_storage (a storage switch)");
   drop_graph(n);
   return FDSR_OK;
 }

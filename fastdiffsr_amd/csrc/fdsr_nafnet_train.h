@@ -539,6 +539,37 @@ __global__ void naf_loss_finish_kernel(const float* __restrict__ part, int nblk,
   out[0] = weight * (tot / (float)N);
 }
 
+// The autograd bridge's two ends.  naf_dout_kernel: the caller's d out (NCHW, H x W) into the padded NHWC d eps slot, zero where
+// the forward's crop dropped the prediction -- the place naf_loss_kernel's d eps takes in a built-in step.
+__global__ void __launch_bounds__(256) naf_dout_kernel(const float* __restrict__ dout, float* __restrict__ deps, int H, int W, int Hp, int Wp,
+                                                       size_t total) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;   // (n, y, x) of the padded image
+  if (i >= total) return;
+  const int px = (int)(i % Wp), py = (int)((i / Wp) % Hp);
+  const size_t n = i / ((size_t)Wp * Hp);
+  const bool in = py < H && px < W;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) deps[i * 3 + c] = in ? dout[((n * 3 + c) * H + py) * W + px] : 0.f;
+}
+
+// naf_prep_kernel backwards: xin = cat[x - cond, cond], so d x = g[0:3] and d cond = g[3:6] - g[0:3]; the padding's gradient is
+// dropped.  g: padded NHWC [N][Hp][Wp][6]; dx, dcond: NCHW H x W, either may be null.
+__global__ void __launch_bounds__(256) naf_unprep_kernel(const float* __restrict__ g, float* __restrict__ dx, float* __restrict__ dcond, int H, int W,
+                                                         int Hp, int Wp, size_t total) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;   // (n, y, x) of the cropped image
+  if (i >= total) return;
+  const int px = (int)(i % W), py = (int)((i / W) % H);
+  const size_t n = i / ((size_t)W * H);
+  const float* gp = g + ((n * Hp + py) * Wp + px) * 6;
+  const size_t HW = (size_t)H * W, base = n * 3 * HW + (size_t)py * W + px;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float a = gp[c];
+    if (dx) dx[base + c * HW] = a;
+    if (dcond) dcond[base + c * HW] = __fsub_rn(gp[3 + c], a);
+  }
+}
+
 // every scalar is formed on the host in double, as Python forms it, and rounded once (torch hands its kernels such scalars)
 struct OptArgs { float lr, b1, b2, omb1, omb2, decay, eps, wd, step_size, bc2_sqrt; int kind; };
 
@@ -725,7 +756,7 @@ struct TrainRun : Run {
     const int M = a.N * a.Hout * a.Wout, nz = (M + WG_CHUNK - 1) / WG_CHUNK;
     const dim3 grid((unsigned)((a.Keff + 63) / 64), (unsigned)((a.Cout + 63) / 64), (unsigned)nz);
     if ((size_t)nz * grid.x * 64 * grid.y * 64 > tp.wg_floats) {
-      if (err == FDSR_OK) err = fail(nullptr, FDSR_E_WORKSPACE, "fdsr_nafnet_train_grads: weight-gradient scratch too small");
+      if (err == FDSR_OK) err = fail(nullptr, FDSR_E_WORKSPACE, "fdsr_nafnet: weight-gradient scratch too small");
       return;
     }
     launch(pro == PRO_LN ? naf_wgrad_kernel<PRO_LN> : pro == PRO_MUL ? naf_wgrad_kernel<PRO_MUL> : naf_wgrad_kernel<PRO_NONE>, grid, dim3(256), 0, a);
@@ -844,6 +875,14 @@ struct TrainRun : Run {
     wgrad(n->g_intro, d.xin, g, h, w);
   }
 
+  // past wgrad(g_intro): d xin through intro's transposed pack, then naf_prep_kernel backwards.  net_bwd() left d intro in gx; gt
+  // is free from there on and holds d xin [N][Hp][Wp][6].
+  void input_bwd(float* dx, float* dcond) {
+    gemm_l(n->tgemms[n->g_intro], F(tp.gx), F(tp.gt), tp.Hp, tp.Wp, EPI_BIAS);
+    const size_t total = (size_t)tp.N * tp.H * tp.W;
+    launch(naf_unprep_kernel, dim3(nb(total)), dim3(256), 0, F(tp.gt), dx, dcond, tp.H, tp.W, tp.Hp, tp.Wp, total);
+  }
+
   // the rows back through every block's Linear, SimpleGate and time_mlp
   void time_bwd() {
     const int wd = n->wd, K2 = 2 * wd, R = n->R, N = tp.N;
@@ -858,6 +897,17 @@ struct TrainRun : Run {
     launch(naf_linear_w_kernel, dim3(nb((size_t)8 * wd * wd)), dim3(256), 0, dh1, emb, G(n->t1w), G(n->t1b), N, 8 * wd, wd);
   }
 };
+
+// what train_grads, forward_train and backward check alike; the messages are train_grads'
+int check_train_call(fdsr_nafnet n, const char* fn, int batch, int height, int width, void* workspace, size_t workspace_bytes) {
+  const int rc = check_args(n, fn, batch, height, width, workspace, workspace_bytes, train_plan_bytes);
+  if (rc) return rc;
+  if (n->store != FDSR_NAF_STORE_F32)
+    return fail(nullptr, FDSR_E_INVALID, "%s: training runs on fp32 activations only, the object is in FDSR_NAF_STORE_F16, f16 storage (fdsr_nafnet_set_storage)", fn);
+  if (n->prec != FDSR_PREC_F32)
+    return fail(nullptr, FDSR_E_INVALID, "%s: training runs in FDSR_PREC_F32 only, the object is in f16x3 (fdsr_nafnet_set_precision)", fn);
+  return FDSR_OK;
+}
 
 int find_weight(fdsr_nafnet n, const char* fn, const char* key) {
   if (!n || !key) return fail(nullptr, FDSR_E_INVALID, "%s: null argument", fn);
@@ -896,14 +946,11 @@ int fdsr_nafnet_train_grads(fdsr_nafnet n, const float* state_nchw, const float*
     return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, batch, height, width);
   if (loss_type & FDSR_NAFNET_LOSS_WEIGHTED) return fail(nullptr, FDSR_E_INVALID, "%s: is_weighted is not supported (the reference passes no weights)", fn);
   if (loss_type != FDSR_NAFNET_LOSS_L1 && loss_type != FDSR_NAFNET_LOSS_L2) return fail(nullptr, FDSR_E_INVALID, "%s: loss_type %d (l1 = 0, l2 = 1)", fn, loss_type);
-  int rc = check_args(n, fn, batch, height, width, workspace, workspace_bytes, train_plan_bytes);
+  int rc = check_train_call(n, fn, batch, height, width, workspace, workspace_bytes);
   if (rc) return rc;
-  if (n->store != FDSR_NAF_STORE_F32)
-    return fail(nullptr, FDSR_E_INVALID, "%s: training runs on fp32 activations only, the object is in FDSR_NAF_STORE_F16, f16 storage (fdsr_nafnet_set_storage)", fn);
-  if (n->prec != FDSR_PREC_F32)
-    return fail(nullptr, FDSR_E_INVALID, "%s: training runs in FDSR_PREC_F32 only, the object is in f16x3 (fdsr_nafnet_set_precision)", fn);
   if (n->T < 1 || n->cum_T != n->T) return fail(nullptr, FDSR_E_STATE, "%s: no schedule (fdsr_nafnet_set_sde, fdsr_nafnet_set_thetas_cumsum)", fn);
   if ((rc = ensure_train(n))) return rc;
+  kill_ticket(n, fn);
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   char* ws = static_cast<char*>(workspace);
   const TrainPlan tp = make_train_plan(n, batch, height, width);
@@ -926,6 +973,90 @@ int fdsr_nafnet_train_grads(fdsr_nafnet n, const float* state_nchw, const float*
   t.net_bwd();
   t.time_bwd();
   return t.err;
+}
+
+int fdsr_nafnet_forward_train(fdsr_nafnet n, const float* x_nchw, const float* cond_nchw, const float* time_dev, float* out_nchw, int batch,
+                              int height, int width, void* workspace, size_t workspace_bytes, int64_t* ticket, void* hip_stream) {
+  const char* fn = "fdsr_nafnet_forward_train";
+  if (!n || !x_nchw || !cond_nchw || !time_dev || !out_nchw || !ticket || !workspace || batch < 1 || height < 1 || width < 1)
+    return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, batch, height, width);
+  int rc = check_train_call(n, fn, batch, height, width, workspace, workspace_bytes);
+  if (rc) return rc;
+  if ((rc = ensure_train(n))) return rc;
+  kill_ticket(n, "a second fdsr_nafnet_forward_train");
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  char* ws = static_cast<char*>(workspace);
+  const TrainPlan tp = make_train_plan(n, batch, height, width);
+  TrainRun t{{n, train_dst(n, tp, ws), st, nullptr, n->R}, tp, ws};
+  HIPCHK(nullptr, hipMemcpyAsync(t.F(tp.tf), time_dev, (size_t)batch * sizeof(float), hipMemcpyDeviceToDevice, st));   // time_bwd reads it
+  t.time_rows(t.F(tp.tf), batch, t.d.tg, t.d.trow);
+  t.rows = t.d.trow;
+  t.prep(x_nchw, cond_nchw);
+  t.net();
+  t.tail(0, out_nchw, nullptr, nullptr, nullptr, 0, 0);
+  if (t.err) return t.err;
+  n->ticket.live = ++n->ticket.next;
+  n->ticket.N = batch; n->ticket.H = height; n->ticket.W = width; n->ticket.ws = workspace;
+  *ticket = n->ticket.live;
+  return FDSR_OK;
+}
+
+int fdsr_nafnet_backward(fdsr_nafnet n, int64_t ticket, const float* d_out_nchw, float* d_x_nchw, float* d_cond_nchw, int batch, int height,
+                         int width, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  const char* fn = "fdsr_nafnet_backward";
+  if (!n || !d_out_nchw || !workspace || batch < 1 || height < 1 || width < 1)
+    return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, batch, height, width);
+  if (ticket < 1 || ticket != n->ticket.live)
+    return fail(nullptr, FDSR_E_STATE, "%s: ticket %lld is stale: %s came after its forward, and the activations it kept are not there any more", fn,
+                (long long)ticket, n->ticket.live ? "a second fdsr_nafnet_forward_train" : n->ticket.killer);
+  if (batch != n->ticket.N || height != n->ticket.H || width != n->ticket.W || workspace != n->ticket.ws)
+    return fail(nullptr, FDSR_E_INVALID, "%s: B %d at %dx%d and the workspace must be those of the ticket's forward (B %d at %dx%d)", fn, batch, height,
+                width, n->ticket.N, n->ticket.H, n->ticket.W);
+  int rc = check_train_call(n, fn, batch, height, width, workspace, workspace_bytes);
+  if (rc) return rc;
+  kill_ticket(n, "an earlier fdsr_nafnet_backward (it consumes the ticket)");
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  char* ws = static_cast<char*>(workspace);
+  const TrainPlan tp = make_train_plan(n, batch, height, width);
+  TrainRun t{{n, train_dst(n, tp, ws), st, nullptr, n->R}, tp, ws};
+  t.rows = t.d.trow;
+  HIPCHK(nullptr, hipMemsetAsync(n->d_grad, 0, n->P * sizeof(float), st));
+  const size_t total = (size_t)batch * tp.Hp * tp.Wp;
+  t.launch(naf_dout_kernel, dim3(Run::nb(total)), dim3(256), 0, d_out_nchw, t.F(tp.deps), height, width, tp.Hp, tp.Wp, total);
+  t.net_bwd();
+  if (d_x_nchw || d_cond_nchw) t.input_bwd(d_x_nchw, d_cond_nchw);
+  t.time_bwd();
+  return t.err;
+}
+
+int fdsr_nafnet_copy_grads(fdsr_nafnet n, float* dst_dev, size_t count, void* hip_stream) {
+  if (!n || !dst_dev) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_copy_grads: null argument");
+  if (!n->d_grad) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet_copy_grads: no gradients yet (fdsr_nafnet_train_grads, fdsr_nafnet_backward)");
+  if (count != n->P) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_copy_grads: count %zu is not the %zu floats of the flat gradient", count, n->P);
+  HIPCHK(nullptr, hipMemcpyAsync(dst_dev, n->d_grad, n->P * sizeof(float), hipMemcpyDeviceToDevice, reinterpret_cast<hipStream_t>(hip_stream)));
+  return FDSR_OK;
+}
+
+int fdsr_nafnet_set_weights_flat(fdsr_nafnet n, const float* src_dev, size_t count, void* hip_stream) {
+  const char* fn = "fdsr_nafnet_set_weights_flat";
+  if (!n || !src_dev) return fail(nullptr, FDSR_E_INVALID, "%s: null argument", fn);
+  if (count != n->P) return fail(nullptr, FDSR_E_INVALID, "%s: count %zu is not the %zu floats of all tensors", fn, count, n->P);
+  if (n->store != FDSR_NAF_STORE_F32)
+    return fail(nullptr, FDSR_E_INVALID, "%s: training runs on fp32 activations only, the object is in FDSR_NAF_STORE_F16, f16 storage", fn);
+  if (n->prec != FDSR_PREC_F32)   // the device-side re-pack below writes the fp32 forms only
+    return fail(nullptr, FDSR_E_INVALID, "%s: training runs in FDSR_PREC_F32 only, the object is in f16x3", fn);
+  int rc = finalize(n);   // the first upload is the host's (fdsr_nafnet_load_weight): it sets the constants of the arena
+  if (rc) return rc;
+  if ((rc = ensure_train(n))) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  HIPCHK(nullptr, hipMemcpyAsync(n->d_master, src_dev, n->P * sizeof(float), hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(naf_repack_kernel, dim3(Run::nb(n->arena_floats)), dim3(256), 0, st, n->d_arena, n->d_master, n->d_map, n->arena_floats);
+  HIPCHK(nullptr, hipGetLastError());
+  n->host_stale = true;
+  n->table_valid = false;
+  kill_ticket(n, fn);
+  drop_graph(n);
+  return FDSR_OK;
 }
 
 int fdsr_nafnet_grad_buffer(fdsr_nafnet n, float** device_ptr, size_t* count) {
@@ -956,6 +1087,7 @@ int fdsr_nafnet_optim_step(fdsr_nafnet n, int kind, double lr, double beta1, dou
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_optim_step: training runs in FDSR_PREC_F32 only, the object is in f16x3");
   if (!n->d_grad || !n->master_valid || n->dirty) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet_optim_step: no gradients (fdsr_nafnet_train_grads first)");
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  kill_ticket(n, "fdsr_nafnet_optim_step");
   n->opt_step += 1;
   OptArgs o{};
   o.kind = kind; o.lr = (float)lr; o.b1 = (float)beta1; o.b2 = (float)beta2; o.eps = (float)eps; o.wd = (float)weight_decay;

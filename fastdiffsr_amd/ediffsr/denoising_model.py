@@ -1,7 +1,9 @@
 """DenoisingModel (EDiffSR/codes/config/sisr/models/denoising_model.py) on the HIP engine: the reference's training surface
 around ConditionalNAFNet.  optimize_parameters is one engine call for the loss and the gradients and one for the optimizer; the
-learning-rate schedules are evaluated on the host.  Not here: the EMA copy, multi-rank training, 16-bit modes,
-is_weighted, DenoisingUNet_arch."""
+learning-rate schedules are evaluated on the host.  Not on this engine-only path: the EMA copy, multi-rank training,
+is_weighted, any loss other than l1 / l2.  All four are reached the other way round: the reference's own DenoisingModel around
+this package's ConditionalNAFNet with requires_grad_(True), whose forward is differentiable through torch autograd (model.py;
+INTEGRATION 6).  On neither path: 16-bit modes for training, DenoisingUNet_arch."""
 import math
 import os
 from collections import OrderedDict

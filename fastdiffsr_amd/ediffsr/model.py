@@ -1,12 +1,19 @@
 """ConditionalNAFNet on the HIP engine (include/fdsr.h: fdsr_nafnet_*): an nn.Module that owns the reference's parameters
 under the reference's names -- `latest_G.pth` loads with load_state_dict(strict=True) -- and whose forward runs the device
-kernels.  Training runs through train_grads / optim_step (denoising_model.DenoisingModel drives them); there is no
-torch-autograd bridge and no PyTorch fallback."""
+kernels.  Training runs two ways, both on the engine's own backward (there is no PyTorch fallback):
+  * train_grads / optim_step: the IR-SDE l1 / l2 loss head and Adam / AdamW / Lion built into the library
+    (denoising_model.DenoisingModel drives them);
+  * torch autograd: after model.requires_grad_(True), forward records a node (_NAFNetFunction) whose backward is
+    fdsr_nafnet_backward, so any loss, torch.optim, an EMA copy or DDP hooks stand around the network as they do around the
+    reference's.  One forward's activations are kept at a time: each forward wants its backward before the next forward
+    under grad, and a backward runs once (no retain_graph, no double backward); anything else raises the engine's
+    stale-ticket error.  Parameters are created with requires_grad=False, so nothing changes for callers who do not opt in."""
 import contextlib
 import ctypes as C
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from .. import _lib
 from .arch import NAFNetConfig, param_schema, tap_names
@@ -14,6 +21,41 @@ from .arch import NAFNetConfig, param_schema, tap_names
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
+
+
+class _NAFNetFunction(torch.autograd.Function):
+    """out = module(x, cond, time) with the activations kept (fdsr_nafnet_forward_train); backward is fdsr_nafnet_backward on
+    the current stream.  Inputs: the module (no tensor), x, cond, time [B] fp32, then every parameter in state_dict order --
+    the parameters are inputs only so that autograd routes their gradients; the engine reads its own copies."""
+
+    @staticmethod
+    def forward(ctx, module, x, cond, time, *params):
+        ctx.module = module
+        ctx.shape = tuple(x.shape)
+        out, ctx.ticket, ctx.ws = module._forward_train(x, cond, time)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        m, (b, _, h, w) = ctx.module, ctx.shape
+        need = ctx.needs_input_grad
+        dev = dout.device
+        dout = dout.float().contiguous()
+        lib, hd = _lib.load(), m._handle()
+        with torch.cuda.device(dev):
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            dx = torch.empty_like(dout) if need[1] else None
+            dc = torch.empty_like(dout) if need[2] else None
+            _lib.check(None, lib.fdsr_nafnet_backward(hd, ctx.ticket, _ptr(dout), _ptr(dx), _ptr(dc), b, h, w, _ptr(ctx.ws), ctx.ws.numel(), st))
+            pg = [None] * (len(need) - 4)
+            if any(need[4:]):
+                sizes = [p.numel() for _, p in m.named_reference_parameters()]
+                flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+                _lib.check(None, lib.fdsr_nafnet_copy_grads(hd, _ptr(flat), flat.numel(), st))
+                views = flat.split(sizes)
+                pg = [v.view(shape) if n else None for v, shape, n in zip(views, m.schema.values(), need[4:])]
+        return (None, dx, dc, None) + tuple(pg)
 
 
 class ConditionalNAFNet(nn.Module):
@@ -81,6 +123,16 @@ class ConditionalNAFNet(nn.Module):
             _lib._lib.fdsr_nafnet_destroy(h)
             self._h = None
 
+    def __getstate__(self):
+        """What copy.deepcopy and pickle carry: the parameters and the configuration.  The engine object and what belongs to
+        it stay behind -- the handle, the upload stamp, the workspaces, the graph stream, and the precision and schedule that
+        were set on that handle -- so a copy creates an engine of its own (in 'f32', without a schedule) on first use."""
+        d = dict(self.__dict__)
+        d['_h'], d['_uploaded'], d['_ws'] = None, None, {}
+        for k in ('_graph_stream', '_precision', '_sde_T'):
+            d.pop(k, None)
+        return d
+
     def engine_schema(self):
         """[(key, shape)] as the library lists them (fdsr_nafnet_weight_info)."""
         lib, h = _lib.load(), self._handle()
@@ -92,12 +144,23 @@ class ConditionalNAFNet(nn.Module):
         return out
 
     def sync_weights(self, device):
-        """Upload the parameters when they changed since the last upload (tensor versions, as unet.py does)."""
+        """Upload the parameters when they changed since the last upload (tensor versions, as unet.py does).  The first upload,
+        and any in a 16-bit mode, packs on the host.  Once the engine has the weights, a module that requires grad (a torch
+        optimizer steps its fp32 CUDA parameters in place) hands them over on the device: one torch.cat and
+        fdsr_nafnet_set_weights_flat, no host round trip."""
         params = [p for _, p in self.named_reference_parameters()]
         stamp = (str(device), tuple((p.data_ptr(), p._version) for p in params))
         if stamp == self._uploaded:
             return
         lib, h = _lib.load(), self._handle()
+        if (self._uploaded is not None and self._uploaded[0] == stamp[0] and self.precision == 'f32' and any(p.requires_grad for p in params)
+                and all(p.is_cuda and p.dtype == torch.float32 and str(p.device) == stamp[0] for p in params)):
+            with torch.cuda.device(device), torch.no_grad():
+                flat = torch.cat([p.detach().reshape(-1) for p in params])
+                st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+                _lib.check(None, lib.fdsr_nafnet_set_weights_flat(h, _ptr(flat), flat.numel(), st))
+            self._uploaded = stamp
+            return
         with torch.cuda.device(device):
             for k, p in zip(self._names, params):
                 a = p.detach().to('cpu', torch.float32).contiguous()
@@ -130,15 +193,36 @@ class ConditionalNAFNet(nn.Module):
             raise ValueError('time must be a scalar or one value per image')
         return t.contiguous()
 
+    def _train_ws(self, b, h, w, device):
+        need = C.c_size_t()
+        _lib.check(None, _lib.load().fdsr_nafnet_train_workspace_bytes(self._handle(), b, h, w, C.byref(need)))
+        key = ('train', str(device))
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need.value:
+            ws = self._ws[key] = torch.empty(need.value, dtype=torch.uint8, device=device)
+        return ws
+
+    def _forward_train(self, x, cond, t):
+        """(out, ticket, workspace) of fdsr_nafnet_forward_train: forward's out, with the activations kept for one backward."""
+        b, _, h, w = x.shape
+        with torch.cuda.device(x.device):
+            out = torch.empty_like(x)
+            ws = self._train_ws(b, h, w, x.device)
+            ticket = C.c_int64()
+            st = torch.cuda.current_stream(x.device).cuda_stream
+            _lib.check(None, _lib.load().fdsr_nafnet_forward_train(self._handle(), _ptr(x), _ptr(cond), _ptr(t), _ptr(out), b, h, w, _ptr(ws),
+                                                                   ws.numel(), C.byref(ticket), C.c_void_p(st)))
+        return out, ticket.value, ws
+
     def forward(self, inp, cond, time):
-        if torch.is_grad_enabled() and any(p.requires_grad for _, p in self.named_reference_parameters()):
-            raise NotImplementedError('ConditionalNAFNet.forward has no torch-autograd bridge: train through '
-                                      'fastdiffsr_amd.ediffsr.DenoisingModel (or train_grads / optim_step)')
         x, cond = self._check_pair(inp, cond)
         b, _, h, w = x.shape
         self.sync_weights(x.device)
+        params = [p for _, p in self.named_reference_parameters()]
         with torch.cuda.device(x.device):
             t = self._times(time, b, x.device)
+            if torch.is_grad_enabled() and (x.requires_grad or cond.requires_grad or any(p.requires_grad for p in params)):
+                return _NAFNetFunction.apply(self, x, cond, t, *params)
             out = torch.empty_like(x)
             ws = self.workspace(b, h, w, x.device)
             st = torch.cuda.current_stream(x.device).cuda_stream
@@ -236,12 +320,7 @@ class ConditionalNAFNet(nn.Module):
             t = torch.as_tensor(timesteps).to(x.device).reshape(-1).to(torch.int32).contiguous()
             if t.numel() != b:
                 raise ValueError('one timestep per image')
-            need = C.c_size_t()
-            _lib.check(None, lib.fdsr_nafnet_train_workspace_bytes(hd, b, h, w, C.byref(need)))
-            key = ('train', str(x.device))
-            ws = self._ws.get(key)
-            if ws is None or ws.numel() < need.value:
-                ws = self._ws[key] = torch.empty(need.value, dtype=torch.uint8, device=x.device)
+            ws = self._train_ws(b, h, w, x.device)
             out = torch.empty(1 + b, dtype=torch.float32, device=x.device)
             st = torch.cuda.current_stream(x.device).cuda_stream
             code = self.LOSSES[loss_type] | (_lib.FDSR_NAFNET_LOSS_WEIGHTED if is_weighted else 0)

@@ -433,7 +433,28 @@ int fdsr_nafnet_set_storage(fdsr_nafnet n, int mode);
  *   fdsr_nafnet_read_weight   the current value of one tensor, to host memory or (dst_on_device) stream-ordered to device memory.
  *   fdsr_nafnet_optim_get_state / _set_state   exp_avg, exp_avg_sq (either may be NULL) and the step count, per key; the step
  *                             count is one number for the whole object.
- * FDSR_E_STATE: weights, fdsr_nafnet_set_sde or fdsr_nafnet_set_thetas_cumsum missing; fdsr_nafnet_optim_step without gradients. */
+ * FDSR_E_STATE: weights, fdsr_nafnet_set_sde or fdsr_nafnet_set_thetas_cumsum missing; fdsr_nafnet_optim_step without gradients.
+ *
+ * The same walk opened to an upstream gradient of the caller's choosing (what a torch.autograd.Function needs; fp32 only, the
+ * training workspace, FDSR_E_INVALID under FDSR_PREC_F16X3 / FDSR_NAF_STORE_F16 with fdsr_nafnet_train_grads' messages):
+ *   fdsr_nafnet_forward_train out = model(x, cond, time), bit for bit fdsr_nafnet_forward's, with every tensor the backward reads
+ *                             kept in the workspace.  time_dev: fp32 [B].  *ticket names those activations.  No schedule needed.
+ *   fdsr_nafnet_backward      from d_out_nchw (the gradient of anything with respect to out): the gradient of every weight into the
+ *                             flat gradient buffer (zeroed first), and, where the pointer is not NULL, d x and d cond (NCHW) --
+ *                             the input gradient continues through intro's transposed, tap-flipped 3x3 pack (64 -> 6) and undoes
+ *                             cat[x - cond, cond]: d x = g[0:3], d cond = g[3:6] - g[0:3].  B, H, W and the workspace are those
+ *                             of the ticket's forward.  One order for every sum, as fdsr_nafnet_train_grads.
+ *     Tickets.  One is outstanding at most.  It goes stale with a second fdsr_nafnet_forward_train, fdsr_nafnet_train_grads,
+ *     fdsr_nafnet_optim_step, fdsr_nafnet_set_weights_flat, any fdsr_nafnet_load_weight and any precision or storage switch, and
+ *     fdsr_nafnet_backward consumes it (no second backward, no retain_graph).  A stale ticket is FDSR_E_STATE and the message
+ *     names the call that came in between; it never yields gradients of other activations.  Neither call synchronises the
+ *     device after the object's first training call.
+ *   fdsr_nafnet_copy_grads    the flat gradient (count == the sum of all tensors' elements; fdsr_nafnet_weight_info order, the
+ *                             reference's layouts), stream-ordered into device memory.
+ *   fdsr_nafnet_set_weights_flat   all tensors at once from device memory in that same order and layout: the inverse of
+ *                             fdsr_nafnet_read_weight.  Stream-ordered copy into the master, then the device-side re-pack of
+ *                             fdsr_nafnet_optim_step; drops the time-row table and the graph as that call does.  The weights must
+ *                             have been loaded once through fdsr_nafnet_load_weight.  No host round trip. */
 #define FDSR_NAFNET_LOSS_L1 0
 #define FDSR_NAFNET_LOSS_L2 1
 #define FDSR_NAFNET_LOSS_WEIGHTED 256
@@ -445,6 +466,13 @@ int fdsr_nafnet_train_workspace_bytes(fdsr_nafnet n, int batch, int height, int 
 int fdsr_nafnet_train_grads(fdsr_nafnet n, const float* state_nchw, const float* cond_nchw, const float* gt_nchw,
                             const int32_t* timesteps_dev, int loss_type, float weight, float* loss_out_dev, int batch, int height,
                             int width, void* workspace, size_t workspace_bytes, void* hip_stream);
+int fdsr_nafnet_forward_train(fdsr_nafnet n, const float* x_nchw, const float* cond_nchw, const float* time_dev, float* out_nchw,
+                              int batch, int height, int width, void* workspace, size_t workspace_bytes, int64_t* ticket,
+                              void* hip_stream);
+int fdsr_nafnet_backward(fdsr_nafnet n, int64_t ticket, const float* d_out_nchw, float* d_x_nchw, float* d_cond_nchw, int batch,
+                         int height, int width, void* workspace, size_t workspace_bytes, void* hip_stream);
+int fdsr_nafnet_copy_grads(fdsr_nafnet n, float* dst_dev, size_t count, void* hip_stream);
+int fdsr_nafnet_set_weights_flat(fdsr_nafnet n, const float* src_dev, size_t count, void* hip_stream);
 int fdsr_nafnet_grad_buffer(fdsr_nafnet n, float** device_ptr, size_t* count);
 int fdsr_nafnet_read_grad(fdsr_nafnet n, const char* key, float* host_f32);
 int fdsr_nafnet_optim_step(fdsr_nafnet n, int kind, double lr, double beta1, double beta2, double eps, double weight_decay,

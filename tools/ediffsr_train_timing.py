@@ -1,12 +1,15 @@
 """EDiffSR training-step times on one GPU -> profiles/ediffsr_train_timing.txt (or --out).
 
-    python tools/ediffsr_train_timing.py [--out FILE] [--size 256] [--repeats 5] [--baseline]
+    python tools/ediffsr_train_timing.py [--out FILE] [--size 256] [--repeats 5] [--baseline] [--bridge]
 
 Shipped setting (width 64, enc [14,1,1,1]), synthetic weights, l1 loss, AdamW (lr 4e-5, betas 0.9 / 0.99), B = 2 (the
 reference's batch_size) and B = 16: one step = fdsr_nafnet_train_grads + fdsr_nafnet_optim_step with the parameter copy-back, ms
 per step and images/s as the median of --repeats timed steps after two warm-up steps (hipEvents around the step), and the step's
 workspace bytes.  --baseline adds the same step of tests/ediffsr_train_restatement.py through stock PyTorch autograd and
-torch.optim.AdamW on the same GPU, fp32: a baseline only, never the product path.  The file records what was seen."""
+torch.optim.AdamW on the same GPU, fp32: a baseline only, never the product path.  --bridge adds the step through torch autograd
+on the engine (model.requires_grad_(True): fdsr_nafnet_forward_train, IRSDE's loss terms in torch, fdsr_nafnet_backward,
+torch.optim.AdamW, the weights back through fdsr_nafnet_set_weights_flat), and the same without the optimizer.  The file records what
+was seen."""
 import argparse
 import os
 import statistics
@@ -41,6 +44,7 @@ def main():
     ap.add_argument('--size', type=int, default=256)
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--baseline', action='store_true')
+    ap.add_argument('--bridge', action='store_true')
     a = ap.parse_args()
     from fastdiffsr_amd.ediffsr import ConditionalNAFNet, IRSDE
     from fastdiffsr_amd.synth import synth_nafnet
@@ -72,6 +76,32 @@ def main():
         print(lines[-1], flush=True)
         del m
         torch.cuda.empty_cache()
+        if a.bridge:
+            m = ConditionalNAFNet(**SETTING)
+            m.load_state_dict(sd, strict=True)
+            m = m.to(dev).train().requires_grad_(True)
+            dsde = IRSDE(max_sigma=50, T=100, schedule='cosine', eps=0.005, device=dev)
+            dsde.set_model(m)
+            dsde.set_mu(c)
+            opt = torch.optim.AdamW(m.parameters(), lr=4e-5, betas=(0.9, 0.99), weight_decay=0.0)
+            tsd = ts.to(dev)
+
+            def fwd_bwd():
+                opt.zero_grad(set_to_none=True)
+                score = dsde.get_score_from_noise(dsde.noise_fn(x, tsd.squeeze()), tsd)
+                diff = dsde.reverse_sde_step_mean(x, score, tsd) - dsde.reverse_optimum_step(x, y, tsd)
+                diff.abs().flatten(1).mean(dim=1).mean().backward()
+
+            def bridged():
+                fwd_bwd()
+                opt.step()
+            for name, fn in (('fwd+bwd', fwd_bwd), ('step', bridged)):
+                med, lo, hi = timed(fn, a.repeats)
+                lines.append('bridge    B=%-2d %-9s %9.2f ms/step  %7.2f images/s  (torch autograd on the engine, loss in torch%s; median of %d; min %.2f max %.2f)' % (
+                    b, name, med, b * 1000 / med, ', torch.optim.AdamW' if name == 'step' else ', no optimizer', a.repeats, lo, hi))
+                print(lines[-1], flush=True)
+            del m, opt, dsde
+            torch.cuda.empty_cache()
         if a.baseline:
             w = {k: v.to(dev).requires_grad_(True) for k, v in sd.items()}
             tb = tuple(t.to(dev) for t in TR.cast_tables(sde, torch.float32))
