@@ -64,6 +64,8 @@ struct GemmArgs {
   int o32;
 };
 
+#include "fdsr_nafnet_gemm.h"
+
 // One workgroup: BM output pixels x BN packed output columns; 4 waves, each 32 pixels x 64 columns (two 32x32 accumulators, so the
 // two halves of a gated pair sit in one lane).  Thread t stages pixel t % BM and k-octet t / BM of every BK chunk; registers prefetch
 // the next chunk while the MFMAs run on this one.  Out-of-image taps and k >= K read as zero.  VEC: Cin % 8 == 0 (all but intro).
@@ -73,88 +75,23 @@ __global__ void __launch_bounds__(NT) naf_gemm_kernel(GemmArgs p) {
   __shared__ __attribute__((aligned(16))) float sA[BK * AP];
   __shared__ __attribute__((aligned(16))) float sB[BK * BP];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int HWo = p.Hout * p.Wout;
-  const int M = p.N * HWo;
   const int m0 = blockIdx.x * BM, co0 = blockIdx.y * BN;
 
   const int am = t & (BM - 1), ak = (t >> 7) * 8;
-  const int gm = m0 + am;
-  const bool mval = gm < M;
-  int n = 0, oy = 0, ox = 0;
-  if (mval) {
-    n = gm / HWo;
-    const int r = gm - n * HWo;
-    oy = r / p.Wout;
-    ox = r - oy * p.Wout;
-  }
-  const int iy0 = oy * p.S - p.P, ix0 = ox * p.S - p.P;
+  const NafRow row = naf_row<PRO>(p, m0 + am);
   const int bk = t >> 4, bn = (t & 15) * 4;
-  float mean = 0.f, rstd = 0.f;
-  const float *pm = nullptr, *pa = nullptr;
-  if (PRO != PRO_NONE && mval) {
-    pm = p.pmul + (size_t)n * p.pstride;
-    if (PRO == PRO_LN) {
-      pa = p.padd + (size_t)n * p.pstride;
-      mean = p.stats[2 * (size_t)gm];
-      rstd = p.stats[2 * (size_t)gm + 1];
-    }
-  }
 
   float ra[8];
   f32x4 rb;
   auto load = [&](int kc) {
     const int kb = kc * BK;
-    if (!VEC) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = kb + ak + j;
-        float v = 0.f;
-        if (mval && k < p.K) {
-          const int tap = k / p.Cin, ci = k - tap * p.Cin;
-          const int ky = tap / p.KW, kx = tap - ky * p.KW;
-          const int iy = iy0 + ky, ix = ix0 + kx;
-          if (iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win) v = p.x[(((size_t)n * p.Hin + iy) * p.Win + ix) * p.Cin + ci];
-        }
-        ra[j] = v;
-      }
-    } else {
-      const int k = kb + ak;
-      f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
-      if (mval && k < p.K) {
-        const int tap = k / p.Cin, ci = k - tap * p.Cin;
-        const int ky = tap / p.KW, kx = tap - ky * p.KW;
-        const int iy = iy0 + ky, ix = ix0 + kx;
-        if (iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win) {
-          const f32x4* src = reinterpret_cast<const f32x4*>(p.x + (((size_t)n * p.Hin + iy) * p.Win + ix) * p.Cin + ci);
-          v0 = src[0];
-          v1 = src[1];
-          if (PRO != PRO_NONE) {
-            const f32x4 m0v = *reinterpret_cast<const f32x4*>(pm + ci), m1v = *reinterpret_cast<const f32x4*>(pm + ci + 4);
-            if (PRO == PRO_LN) {
-              const f32x4 a0v = *reinterpret_cast<const f32x4*>(pa + ci), a1v = *reinterpret_cast<const f32x4*>(pa + ci + 4);
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                v0[j] = (v0[j] - mean) * rstd * m0v[j] + a0v[j];
-                v1[j] = (v1[j] - mean) * rstd * m1v[j] + a1v[j];
-              }
-            } else {
-              v0 *= m0v;
-              v1 *= m1v;
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) { ra[j] = v0[j]; ra[4 + j] = v1[j]; }
-    }
+    if (VEC) naf_gather_octet<PRO>(p, row, kb + ak, ra);
+    else naf_gather_scalar<8>(p, row, kb + ak, ra);
     rb = *reinterpret_cast<const f32x4*>(p.w + (size_t)(kb + bk) * p.CoutPad + co0 + bn);   // rows < Kpad, columns < CoutPad
   };
 
   f32x16 acc[2];
-#pragma unroll
-  for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[nb][i] = 0.f;
+  naf_zero(acc);
 
   const int r31 = lane & 31, h = lane >> 5;
   const int nk = p.Kpad / BK;
@@ -175,52 +112,7 @@ __global__ void __launch_bounds__(NT) naf_gemm_kernel(GemmArgs p) {
       for (int nb = 0; nb < 2; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, sB[kr * BP + nb * 32 + r31], acc[nb], 0, 0, 0);
     }
   }
-
-  // C/D map: column = lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5) (pixel)
-  const int mw = m0 + wave * 32 + 4 * h;
-  if (p.epi == EPI_GATE) {
-    // packed columns [64 q, 64 q + 32) are channels 32 q + r of the first half, [64 q + 32, 64 q + 64) the same channels of the second
-    const int half = p.Cout >> 1;
-    const int cg = blockIdx.y * 32 + r31;
-    if (cg >= half) return;
-    const float b0 = p.bias[co0 + r31], b1 = p.bias[co0 + 32 + r31];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int om = mw + (i & 3) + 8 * (i >> 2);
-      if (om >= M) continue;
-      const float u0 = acc[0][i] + b0, u1 = acc[1][i] + b1;
-      p.out[(size_t)om * p.ostride + cg] = u0 * u1;
-      if (p.out2) {
-        p.out2[(size_t)om * p.Cout + cg] = u0;
-        p.out2[(size_t)om * p.Cout + half + cg] = u1;
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int nb = 0; nb < 2; ++nb) {
-    const int co = co0 + nb * 32 + r31;
-    if (co >= p.Cout) continue;
-    const float bias = p.bias[co];
-    const float ev = p.epi == EPI_RES ? p.evec[co] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int om = mw + (i & 3) + 8 * (i >> 2);
-      if (om >= M) continue;
-      const float v = acc[nb][i] + bias;
-      if (p.epi == EPI_PSHUF) {
-        // PixelShuffle(2): out[n][c][2y + dy][2x + dx] = in[n][4c + 2dy + dx][y][x], then + enc_skip
-        const int pn = om / HWo, r = om - pn * HWo;
-        const int y = r / p.Wout, x = r - y * p.Wout;
-        const int c = co >> 2, dy = (co >> 1) & 1, dx = co & 1;
-        const size_t oi = (((size_t)pn * 2 * p.Hout + 2 * y + dy) * 2 * p.Wout + 2 * x + dx) * p.ostride + c;
-        p.out[oi] = v + p.res[oi];
-      } else {
-        const size_t oi = (size_t)om * p.ostride + co;
-        p.out[oi] = p.epi == EPI_RELU ? fmaxf(v, 0.f) : p.epi == EPI_RES ? p.res[oi] + v * ev : v;
-      }
-    }
-  }
+  naf_epilogue(p, acc, m0, co0, lane, wave, NafEpiF32<false>{p});
 }
 
 #include "fdsr_nafnet_h3.h"

@@ -3,7 +3,7 @@
 // reads (exact), computes as its fp32 sibling does and rounds once (to nearest even) where it stores; side results formed from
 // registers (the strip sums) come from the fp32 values before that rounding.  A value to be stored or staged beyond +-65504 (or a NaN)
 // is clamped with fmed3 and raises the sticky flag (a plain vector store), in every kernel that stores f16.
-//   naf_gemm_h1_kernel: GemmArgs, tile (BM pixels x BN packed columns, 4 waves of 32 x 64), prologues and epilogues of naf_gemm_kernel.
+//   naf_gemm_h1_kernel: naf_gemm_kernel's gather, prologues and epilogue walk (fdsr_nafnet_gemm.h) around a k-loop of its own.
 //   * the VEC path loads 8 halves (16 B) per octet; with PRO_NONE they go to LDS as they are, otherwise the fp32 value after LN + FiLM
 //     or the SCA multiply is rounded to f16 once.  The non-VEC instance (intro) reads the fp32 xin.
 //   * the weights are the hi planes of split_weights' fragments, f16(w 2^e), straight from L2 into VGPRs; the accumulator is un-scaled
@@ -12,7 +12,7 @@
 //     rows lands on distinct slots), two buffers, one barrier per chunk.
 //   * the store: the 32x32 C/D map gives a lane one column and 16 rows, 2 B per lane in 64-byte row segments.  After the last barrier
 //     the staging LDS is free: the rounded tile is turned through it (144-byte rows) and leaves as 16 B per lane.  PixelShuffle
-//     (a scatter) and ending's fp32 eps store directly.  -DNAF_H1_DIRECT_STORE keeps the direct store everywhere.
+//     (a scatter) and ending's fp32 eps store directly.
 #pragma once
 
 typedef _Float16 naf_h2 __attribute__((ext_vector_type(2)));
@@ -26,38 +26,36 @@ __device__ __forceinline__ _Float16 naf_to_h(float v, int* sat) {
   return (_Float16)__builtin_amdgcn_fmed3f(v, -F16_MAX, F16_MAX);
 }
 
+// epilogue policies (naf_epilogue): res is f16; a finished value goes to global memory (f16, or fp32 under o32), or rounded into the
+// LDS tile [pixel row][column] of H1OP-byte rows
+struct NafEpiH1 {
+  static constexpr bool SCALE = true;
+  const GemmArgs& p;
+  __device__ __forceinline__ float res(size_t oi) const { return (float)reinterpret_cast<const _Float16*>(p.res)[oi]; }
+  __device__ __forceinline__ void put(size_t oi, int, int, float v) const {
+    if (p.o32) p.out[oi] = v;
+    else reinterpret_cast<_Float16*>(p.out)[oi] = naf_to_h(v, p.sat);
+  }
+  __device__ __forceinline__ void pair(int, int, float, float) const {}
+};
+struct NafEpiH1Lds : NafEpiH1 {
+  unsigned char* tile;
+  __device__ __forceinline__ void put(size_t, int row, int col, float v) const {
+    *reinterpret_cast<_Float16*>(tile + row * H1OP + col * 2) = naf_to_h(v, p.sat);
+  }
+};
+
 template <int PRO, bool VEC>
 __global__ void __launch_bounds__(NT) naf_gemm_h1_kernel(GemmArgs p) {
   static_assert(BM * H1OP <= 2 * BM * H1ROW, "the output tile fits the staging buffers");
   __shared__ __attribute__((aligned(16))) unsigned char sA[2 * BM * H1ROW];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int HWo = p.Hout * p.Wout;
-  const int M = p.N * HWo;
   const int m0 = blockIdx.x * BM, co0 = blockIdx.y * BN;
   const _Float16* xh = reinterpret_cast<const _Float16*>(p.x);   // VEC: the input is f16
 
   // thread t stages pixel t % BM, k in [16 (t / BM), +16) of every chunk
   const int am = t & (BM - 1), ak = (t >> 7) * 16;
-  const int gm = m0 + am;
-  const bool mval = gm < M;
-  int n = 0, oy = 0, ox = 0;
-  if (mval) {
-    n = gm / HWo;
-    const int r = gm - n * HWo;
-    oy = r / p.Wout;
-    ox = r - oy * p.Wout;
-  }
-  const int iy0 = oy * p.S - p.P, ix0 = ox * p.S - p.P;
-  float mean = 0.f, rstd = 0.f;
-  const float *pm = nullptr, *pa = nullptr;
-  if (PRO != PRO_NONE && mval) {
-    pm = p.pmul + (size_t)n * p.pstride;
-    if (PRO == PRO_LN) {
-      pa = p.padd + (size_t)n * p.pstride;
-      mean = p.stats[2 * (size_t)gm];
-      rstd = p.stats[2 * (size_t)gm + 1];
-    }
-  }
+  const NafRow row = naf_row<PRO>(p, m0 + am);
 
   // what a chunk's loads leave in registers; the arithmetic waits until stage(), after the MFMAs of the chunk before
   float rf[VEC ? 1 : 16];
@@ -66,40 +64,23 @@ __global__ void __launch_bounds__(NT) naf_gemm_h1_kernel(GemmArgs p) {
   bool ok[2];
   auto load = [&](int kc) {
     const int kb = kc * HK + ak;
-    if (!VEC) {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int k = kb + j;
-        float v = 0.f;
-        if (mval && k < p.K) {
-          const int tap = k / p.Cin, ci = k - tap * p.Cin;
-          const int ky = tap / p.KW, kx = tap - ky * p.KW;
-          const int iy = iy0 + ky, ix = ix0 + kx;
-          if (iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win) v = p.x[(((size_t)n * p.Hin + iy) * p.Win + ix) * p.Cin + ci];
-        }
-        rf[VEC ? 0 : j] = v;
-      }
-    } else {
+    if constexpr (!VEC) naf_gather_scalar<16>(p, row, kb, rf);
+    else {
 #pragma unroll
       for (int o = 0; o < 2; ++o) {   // two octets: each lies inside one tap (Cin % 8 == 0)
-        const int k = kb + 8 * o;
-        ok[o] = false;
+        int ci;
+        size_t off;
+        ok[o] = naf_tap(p, row, kb + 8 * o, ci, off);
 #pragma unroll
         for (int j = 0; j < 8; ++j) rh[o][j] = (_Float16)0.f;
-        if (mval && k < p.K) {
-          const int tap = k / p.Cin, ci = k - tap * p.Cin;
-          const int ky = tap / p.KW, kx = tap - ky * p.KW;
-          const int iy = iy0 + ky, ix = ix0 + kx;
-          if (iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win) {
-            ok[o] = true;
-            rh[o] = *reinterpret_cast<const naf_h8*>(xh + (((size_t)n * p.Hin + iy) * p.Win + ix) * p.Cin + ci);
-            if (PRO != PRO_NONE) {
-              rm[o][0] = *reinterpret_cast<const f32x4*>(pm + ci);
-              rm[o][1] = *reinterpret_cast<const f32x4*>(pm + ci + 4);
-              if (PRO == PRO_LN) {
-                rd[o][0] = *reinterpret_cast<const f32x4*>(pa + ci);
-                rd[o][1] = *reinterpret_cast<const f32x4*>(pa + ci + 4);
-              }
+        if (ok[o]) {
+          rh[o] = *reinterpret_cast<const naf_h8*>(xh + off);
+          if (PRO != PRO_NONE) {
+            rm[o][0] = *reinterpret_cast<const f32x4*>(row.pm + ci);
+            rm[o][1] = *reinterpret_cast<const f32x4*>(row.pm + ci + 4);
+            if (PRO == PRO_LN) {
+              rd[o][0] = *reinterpret_cast<const f32x4*>(row.pa + ci);
+              rd[o][1] = *reinterpret_cast<const f32x4*>(row.pa + ci + 4);
             }
           }
         }
@@ -118,8 +99,7 @@ __global__ void __launch_bounds__(NT) naf_gemm_h1_kernel(GemmArgs p) {
         for (int j = 0; j < 8; ++j) {
           if (!VEC) v[j] = rf[VEC ? 0 : 8 * o + j];
           else if (!ok[o]) v[j] = 0.f;
-          else if (PRO == PRO_LN) v[j] = ((float)rh[o][j] - mean) * rstd * rm[o][j >> 2][j & 3] + rd[o][j >> 2][j & 3];
-          else v[j] = (float)rh[o][j] * rm[o][j >> 2][j & 3];
+          else v[j] = naf_pro<PRO>((float)rh[o][j], row.mean, row.rstd, rm[o][j >> 2][j & 3], PRO == PRO_LN ? rd[o][j >> 2][j & 3] : 0.f);
         }
         bool out = false;   // beyond the range, infinite or NaN
 #pragma unroll
@@ -132,21 +112,14 @@ __global__ void __launch_bounds__(NT) naf_gemm_h1_kernel(GemmArgs p) {
     }
   };
 
-  // weight fragments [column tile][chunk][nb][s][plane][lane] x 16 B (split_weights): the hi plane only
   const int nk = (p.Kpad + HK - 1) / HK;
-  const uint4* wq = p.wq + ((size_t)blockIdx.y * nk * 8) * 64 + lane;
-  uint4 Bf[2][2];
-  auto load_b = [&](int kc, int nb, int s) { Bf[nb][s] = wq[((size_t)kc * 8 + nb * 4 + s * 2) * 64]; };
+  uint4 Bf[2][2];   // the hi plane only
+  auto load_b = [&](int kc, int nb, int s) { Bf[nb][s] = *naf_bfrag(p, nk, lane, kc, nb, s); };
 
   f32x16 acc[2];
-#pragma unroll
-  for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[nb][i] = 0.f;
+  naf_zero(acc);
 
-  const int r31 = lane & 31, h = lane >> 5;
-  // 32x32x16 A operand: A[i = lane & 31][k = 8 (lane >> 5) + j] (pixel, k)
-  const int aoff = (wave * 32 + r31) * H1ROW + 16 * h;
+  const int aoff = naf_aoff(lane, wave, H1ROW);
 #pragma unroll
   for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
@@ -171,94 +144,23 @@ __global__ void __launch_bounds__(NT) naf_gemm_h1_kernel(GemmArgs p) {
     __syncthreads();
   }
 
-  // the epilogue of naf_gemm_kernel on acc * winv; res is f16, out is f16 unless o32 (ending's eps)
-  // C/D map: column = lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5) (pixel)
-  const float winv = p.winv;
-  const int rw = wave * 32 + 4 * h;   // this lane's first row of the tile
+  if (p.epi == EPI_PSHUF || p.o32) {
+    naf_epilogue(p, acc, m0, co0, lane, wave, NafEpiH1{p});
+    return;
+  }
+  // rounded values into LDS [pixel row][column of the tile], then 16 B per lane: a row's 8-column octets are whole (Cout % 8 == 0)
+  naf_epilogue(p, acc, m0, co0, lane, wave, NafEpiH1Lds{{p}, sA});
+  __syncthreads();
+  const int M = p.N * p.Hout * p.Wout;
+  const bool gate = p.epi == EPI_GATE;
+  const int cvalid = gate ? p.Cout >> 1 : p.Cout;   // columns of `out`
+  const int cbase = gate ? blockIdx.y * 32 : co0;   // the tile's first
+  const int octs = gate ? 4 : 8;                    // 16-byte pieces per row
   _Float16* outh = reinterpret_cast<_Float16*>(p.out);
-  const _Float16* resh = reinterpret_cast<const _Float16*>(p.res);
-#ifndef NAF_H1_DIRECT_STORE
-  if (p.epi != EPI_PSHUF && !p.o32) {
-    // rounded values into LDS [pixel row][column of the tile], then 16 B per lane: a row's 8-column octets are whole (Cout % 8 == 0)
-    const bool gate = p.epi == EPI_GATE;
-    const int cvalid = gate ? p.Cout >> 1 : p.Cout;   // columns of `out`
-    const int cbase = gate ? blockIdx.y * 32 : co0;   // the tile's first
-    if (gate) {
-      const bool cok = cbase + r31 < cvalid;
-      const float b0 = p.bias[co0 + r31], b1 = p.bias[co0 + 32 + r31];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int row = rw + (i & 3) + 8 * (i >> 2);
-        if (!cok || m0 + row >= M) continue;
-        const float u0 = acc[0][i] * winv + b0, u1 = acc[1][i] * winv + b1;
-        *reinterpret_cast<_Float16*>(sA + row * H1OP + r31 * 2) = naf_to_h(u0 * u1, p.sat);
-      }
-    } else {
-#pragma unroll
-      for (int nb = 0; nb < 2; ++nb) {
-        const int co = co0 + nb * 32 + r31;
-        if (co >= p.Cout) continue;
-        const float bias = p.bias[co];
-        const float ev = p.epi == EPI_RES ? p.evec[co] : 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int row = rw + (i & 3) + 8 * (i >> 2);
-          if (m0 + row >= M) continue;
-          const float v = acc[nb][i] * winv + bias;
-          const float o = p.epi == EPI_RELU ? fmaxf(v, 0.f) : p.epi == EPI_RES ? (float)resh[(size_t)(m0 + row) * p.ostride + co] + v * ev : v;
-          *reinterpret_cast<_Float16*>(sA + row * H1OP + (nb * 32 + r31) * 2) = naf_to_h(o, p.sat);
-        }
-      }
-    }
-    __syncthreads();
-    const int octs = gate ? 4 : 8;   // 16-byte pieces per row
-    for (int idx = t; idx < BM * octs; idx += NT) {
-      const int row = idx / octs, oc = idx - row * octs;
-      if (m0 + row >= M || cbase + 8 * oc >= cvalid) continue;
-      *reinterpret_cast<naf_h8*>(outh + (size_t)(m0 + row) * p.ostride + cbase + 8 * oc) = *reinterpret_cast<const naf_h8*>(sA + row * H1OP + oc * 16);
-    }
-    return;
-  }
-#endif
-  const int mw = m0 + rw;
-  if (p.epi == EPI_GATE) {
-    const int half = p.Cout >> 1;
-    const int cg = blockIdx.y * 32 + r31;
-    if (cg >= half) return;
-    const float b0 = p.bias[co0 + r31], b1 = p.bias[co0 + 32 + r31];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int om = mw + (i & 3) + 8 * (i >> 2);
-      if (om >= M) continue;
-      const float u0 = acc[0][i] * winv + b0, u1 = acc[1][i] * winv + b1;
-      outh[(size_t)om * p.ostride + cg] = naf_to_h(u0 * u1, p.sat);
-    }
-    return;
-  }
-#pragma unroll
-  for (int nb = 0; nb < 2; ++nb) {
-    const int co = co0 + nb * 32 + r31;
-    if (co >= p.Cout) continue;
-    const float bias = p.bias[co];
-    const float ev = p.epi == EPI_RES ? p.evec[co] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int om = mw + (i & 3) + 8 * (i >> 2);
-      if (om >= M) continue;
-      const float v = acc[nb][i] * winv + bias;
-      if (p.epi == EPI_PSHUF) {
-        const int pn = om / HWo, r = om - pn * HWo;
-        const int y = r / p.Wout, x = r - y * p.Wout;
-        const int c = co >> 2, dy = (co >> 1) & 1, dx = co & 1;
-        const size_t oi = (((size_t)pn * 2 * p.Hout + 2 * y + dy) * 2 * p.Wout + 2 * x + dx) * p.ostride + c;
-        outh[oi] = naf_to_h(v + (float)resh[oi], p.sat);
-      } else {
-        const size_t oi = (size_t)om * p.ostride + co;
-        const float o = p.epi == EPI_RELU ? fmaxf(v, 0.f) : p.epi == EPI_RES ? (float)resh[oi] + v * ev : v;
-        if (p.o32) p.out[oi] = o;
-        else outh[oi] = naf_to_h(o, p.sat);
-      }
-    }
+  for (int idx = t; idx < BM * octs; idx += NT) {
+    const int r = idx / octs, oc = idx - r * octs;
+    if (m0 + r >= M || cbase + 8 * oc >= cvalid) continue;
+    *reinterpret_cast<naf_h8*>(outh + (size_t)(m0 + r) * p.ostride + cbase + 8 * oc) = *reinterpret_cast<const naf_h8*>(sA + r * H1OP + oc * 16);
   }
 }
 

@@ -70,9 +70,9 @@ __global__ void __launch_bounds__(256) naf_wgrad_kernel(WgArgs p) {
           const int iy = oy * p.S - p.P + ky, ix = ox * p.S - p.P + kx;
           if (iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win) {
             a = p.x[(((size_t)n * p.Hin + iy) * p.Win + ix) * p.Cin + ci];
-            if (PRO == PRO_MUL) a *= p.pmul[(size_t)n * p.pstride + ci];
+            if (PRO == PRO_MUL) a = naf_pro<PRO_MUL>(a, 0.f, 0.f, p.pmul[(size_t)n * p.pstride + ci], 0.f);
             if (PRO == PRO_LN)
-              a = (a - p.stats[2 * (size_t)pix]) * p.stats[2 * (size_t)pix + 1] * p.pmul[(size_t)n * p.pstride + ci] + p.padd[(size_t)n * p.pstride + ci];
+              a = naf_pro<PRO_LN>(a, p.stats[2 * (size_t)pix], p.stats[2 * (size_t)pix + 1], p.pmul[(size_t)n * p.pstride + ci], p.padd[(size_t)n * p.pstride + ci]);
           }
         }
       }
