@@ -147,6 +147,7 @@ SYMBOLS = {
     'fdsr_nafnet_destroy': (None, [C.c_void_p]),
     'fdsr_nafnet_set_precision': (C.c_int, [C.c_void_p, C.c_int]),
     'fdsr_nafnet_set_storage': (C.c_int, [C.c_void_p, C.c_int]),
+    'fdsr_nafnet_set_train_storage': (C.c_int, [C.c_void_p, C.c_int]),
     'fdsr_nafnet_check_saturation': (C.c_int, [C.c_void_p, C.c_void_p]),
     'fdsr_set_debug': (C.c_int, [C.c_void_p, C.c_int]),
     'fdsr_debug_option': (C.c_int, [C.c_char_p, C.c_longlong]),

@@ -25,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "fdsr_act_io.h"
 #include "fdsr_engine_int.h"
 #include "fdsr_philox.h"
 
@@ -62,6 +63,9 @@ struct GemmArgs {
   int* sat;
   // FDSR_NAF_STORE_F16 (naf_gemm_h1_kernel): x (but for intro's fp32 xin), res and out are f16; o32: out is fp32 (ending's eps)
   int o32;
+  // training under f16 storage (fdsr_nafnet_set_train_storage): 2^-e from the device table the weight rebuild writes (null: winv);
+  // out2 is f16 there
+  const float* winvp;
 };
 
 #include "fdsr_nafnet_gemm.h"
@@ -470,6 +474,7 @@ struct GemmL {
   size_t woff = 0, boff = 0;   // float offsets into the device arena
   bool split = false;          // f16x3: has a split form (the forward GEMMs; build_schema)
   size_t hoff = 0;             //        its first 16-byte fragment
+  int hidx = 0;                //        its entry in the device table of scales (d_hinv)
   float hinv = 1.f;            //        2^-e of the split form's scale (split_weights)
   int K32() const { return round_up(K(), HK); }
   size_t hfrags() const { return (size_t)(CoutPad() / BN) * (K32() / HK) * 8 * 64; }
@@ -516,8 +521,13 @@ struct fdsr_nafnet_obj {
   // FDSR_PREC_F16X3: hi / lo planes of the forward GEMMs' weights (built by finalize in that mode) and the range flag
   int prec = FDSR_PREC_F32;
   int store = FDSR_NAF_STORE_F32;   // FDSR_NAF_STORE_F16: f16 activations, the hi planes of d_wq, the same flag (fdsr_nafnet_h1.h)
+  // training's own storage setting; it takes effect while the sampling side is FDSR_PREC_F32 with FDSR_NAF_STORE_F32
+  int train_store = FDSR_NAF_STORE_F32;
+  bool train16() const { return train_store == FDSR_NAF_STORE_F16 && store == FDSR_NAF_STORE_F32 && prec == FDSR_PREC_F32; }
   size_t hfrags = 0;
   uint4* d_wq = nullptr;
+  float* d_hinv = nullptr;   // [gemms]: 2^-e of every split form, as split_weights / naf_wq_scale_kernel left it
+  void* d_hdesc = nullptr;   // [gemms] WqDesc: where the device rebuild of d_wq finds each GEMM (fdsr_nafnet_train.h)
   int *d_sat = nullptr, *h_sat = nullptr;
   // training (fdsr_nafnet_train.h): flat fp32 buffers in the reference's layout, tensors in state_dict order
   float *d_master = nullptr, *d_grad = nullptr, *d_m = nullptr, *d_v = nullptr, *d_cum = nullptr;
@@ -679,7 +689,7 @@ void build_schema(fdsr_nafnet n) {
   n->off_zero = take(off, zmax);
   for (GemmL& t : n->tgemms) t.boff = n->off_zero;
   n->arena_floats = off;
-  for (GemmL& g : n->gemms) { g.split = true; g.hoff = n->hfrags; n->hfrags += g.hfrags(); }
+  for (GemmL& g : n->gemms) { g.split = true; g.hoff = n->hfrags; n->hfrags += g.hfrags(); g.hidx = (int)(&g - n->gemms.data()); }
   size_t po = 0;
   for (const WT& wt : n->wts) { n->poff.push_back(po); po += numel(wt.shape); }
   n->P = po;
@@ -808,10 +818,14 @@ int finalize(fdsr_nafnet n) {
   if (!n->d_arena) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_arena), a.size() * sizeof(float)));
   HIPCHK(nullptr, hipDeviceSynchronize());   // nothing in flight reads the old forms
   HIPCHK(nullptr, hipMemcpy(n->d_arena, a.data(), a.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (n->prec == FDSR_PREC_F16X3 || n->store == FDSR_NAF_STORE_F16) {
+  if (n->prec == FDSR_PREC_F16X3 || n->store == FDSR_NAF_STORE_F16 || n->train_store == FDSR_NAF_STORE_F16) {
     const std::vector<uint16_t> q = split_weights(n, a);
     if (!n->d_wq) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_wq), q.size() * sizeof(uint16_t)));
     HIPCHK(nullptr, hipMemcpy(n->d_wq, q.data(), q.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    std::vector<float> hinv;
+    for (const GemmL& g : n->gemms) hinv.push_back(g.hinv);
+    if (!n->d_hinv) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_hinv), hinv.size() * sizeof(float)));
+    HIPCHK(nullptr, hipMemcpy(n->d_hinv, hinv.data(), hinv.size() * sizeof(float), hipMemcpyHostToDevice));
     if (!n->d_sat) {
       HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_sat), 256));
       HIPCHK(nullptr, hipMemset(n->d_sat, 0, 256));
@@ -920,6 +934,7 @@ struct Run {
   const float* tap_ptr = nullptr;
   int tap_h = 0, tap_w = 0, tap_c = 0;
   int err = FDSR_OK;
+  bool t16 = false;   // a training call under f16 training storage: the forward is the h1 walk, into half-size slots
 
   const float* P(size_t off) const { return n->d_arena + off; }
   static unsigned nb(size_t total) { return (unsigned)((total + 255) / 256); }
@@ -931,7 +946,7 @@ struct Run {
     hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
     check();
   }
-  bool h1() const { return n->store == FDSR_NAF_STORE_F16; }
+  bool h1() const { return t16 || n->store == FDSR_NAF_STORE_F16; }
   void copy(float* dst, const float* src, size_t elems) {   // an activation: f16 elements under h1
     (void)hipMemcpyAsync(dst, src, elems * (h1() ? sizeof(_Float16) : sizeof(float)), hipMemcpyDeviceToDevice, st);
     check();
@@ -946,7 +961,7 @@ struct Run {
 
   void gemm_l(const GemmL& g, const float* x, float* out, int Hin, int Win, int epi, int pro = PRO_NONE, const float* pmul = nullptr,
               const float* padd = nullptr, int pstride = 0, const float* stats = nullptr, const float* res = nullptr,
-              const float* evec = nullptr, float* out2 = nullptr) {
+              const float* evec = nullptr, float* out2 = nullptr, bool o32 = false) {
     GemmArgs a{};
     a.x = x; a.w = P(g.woff); a.bias = P(g.boff); a.out = out; a.out2 = out2;
     a.stats = stats; a.pmul = pmul; a.padd = padd; a.res = res; a.evec = evec;
@@ -958,14 +973,17 @@ struct Run {
     a.pstride = pstride; a.epi = epi;
     const int M = d.N * a.Hout * a.Wout;
     const dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(a.CoutPad / BN));
-    const int form = h1() ? FORM_H1 : n->prec == FDSR_PREC_F16X3 ? FORM_H3 : FORM_F32;
+    // training under f16 storage: the forward GEMMs (and conv3 / conv5 formed again, o32) on the h1 kernel, the input-gradient
+    // GEMMs (no split form: fp32 gradients against the fp32 transposed packs) on the exact kernel
+    const int form = t16 ? (g.split ? FORM_H1 : FORM_F32) : h1() ? FORM_H1 : n->prec == FDSR_PREC_F16X3 ? FORM_H3 : FORM_F32;
     if (form != FORM_F32) {
-      if (out2 || !g.split) {
+      if ((out2 && !t16) || !g.split) {
         if (err == FDSR_OK) err = fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet: this GEMM has no f16 form");
         return;
       }
       a.wq = n->d_wq + g.hoff; a.winv = g.hinv; a.sat = n->d_sat;
-      a.o32 = out == d.eps;
+      a.o32 = out == d.eps || o32;
+      if (t16) a.winvp = n->d_hinv + g.hidx;
     }
     const GemmFn k = g.cin % 8 ? gemm_fn<PRO_NONE, false>(form) : pro == PRO_LN ? gemm_fn<PRO_LN, true>(form)
                      : pro == PRO_MUL ? gemm_fn<PRO_MUL, true>(form) : gemm_fn<PRO_NONE, true>(form);
@@ -1143,7 +1161,7 @@ void fdsr_nafnet_destroy(fdsr_nafnet n) {
   drop_graph(n);
   for (void* p : {(void*)n->d_arena, (void*)n->d_sde, (void*)n->d_rowtable, (void*)n->d_cur_row, (void*)n->d_ctl, (void*)n->d_master,
                   (void*)n->d_grad, (void*)n->d_m, (void*)n->d_v, (void*)n->d_cum, (void*)n->d_map, (void*)n->d_rowmap, (void*)n->d_wq,
-                  (void*)n->d_sat})
+                  (void*)n->d_sat, (void*)n->d_hinv, n->d_hdesc})
     if (p) (void)hipFree(p);
   if (n->h_sat) (void)hipHostFree(n->h_sat);
   delete n;
@@ -1221,11 +1239,24 @@ int fdsr_nafnet_set_storage(fdsr_nafnet n, int mode) {
   return FDSR_OK;
 }
 
+int fdsr_nafnet_set_train_storage(fdsr_nafnet n, int mode) {
+  if (!n || (mode != FDSR_NAF_STORE_F32 && mode != FDSR_NAF_STORE_F16))
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_set_train_storage: mode must be FDSR_NAF_STORE_F32 (0) or FDSR_NAF_STORE_F16 (1), not %d", mode);
+  if (mode == n->train_store) return FDSR_OK;
+  const int rc = host_from_master(n);   // as a storage switch: finalize builds the hi planes and the table of scales the f16 forward reads
+  if (rc) return rc;
+  n->train_store = mode;
+  n->dirty = true;
+  kill_ticket(n, "fdsr_nafnet_set_train_storage (a storage switch)");
+  drop_graph(n);
+  return FDSR_OK;
+}
+
 int fdsr_nafnet_check_saturation(fdsr_nafnet n, void* hip_stream) {
   if (!n) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_check_saturation: null object");
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   HIPCHK(nullptr, hipStreamSynchronize(st));
-  if ((n->prec != FDSR_PREC_F16X3 && n->store != FDSR_NAF_STORE_F16) || !n->d_sat) return FDSR_OK;
+  if ((n->prec != FDSR_PREC_F16X3 && n->store != FDSR_NAF_STORE_F16 && !n->train16()) || !n->d_sat) return FDSR_OK;
   if (!n->h_sat) HIPCHK(nullptr, hipHostMalloc(reinterpret_cast<void**>(&n->h_sat), 64, hipHostMallocDefault));
   *n->h_sat = 0;
   HIPCHK(nullptr, hipMemcpyAsync(n->h_sat, n->d_sat, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1235,6 +1266,10 @@ int fdsr_nafnet_check_saturation(fdsr_nafnet n, void* hip_stream) {
   if (n->store == FDSR_NAF_STORE_F16)
     return fail(nullptr, FDSR_E_SATURATED, "f16 storage: an activation of the NAFNet exceeded the f16 range (+-65504) and was clamped; "
                                            "re-run this call after fdsr_nafnet_set_storage(FDSR_NAF_STORE_F32)");
+  if (n->train16())
+    return fail(nullptr, FDSR_E_SATURATED, "f16 training storage: an activation of the NAFNet exceeded the f16 range (+-65504) and was clamped; "
+                                           "the gradients of this call are not to be used: skip the step, or train after "
+                                           "fdsr_nafnet_set_train_storage(FDSR_NAF_STORE_F32)");
   return fail(nullptr, FDSR_E_SATURATED, "f16x3: a GEMM input of the NAFNet exceeded the f16 range (+-65504) and was clamped; "
                                          "re-run this call after fdsr_nafnet_set_precision(FDSR_PREC_F32)");
 }

@@ -117,7 +117,7 @@ __device__ __forceinline__ int naf_aoff(int lane, int wave, int pitch) { return 
 
 // The epilogue of a wave's two 32x32 accumulators (pixels x packed columns [co0, co0 + 64) of the tile at pixel m0): bias, then the
 // gate / ReLU / residual / PixelShuffle form GemmArgs::epi names.  The policy E says what differs between the kernels:
-//   E::SCALE                 the accumulator is un-scaled by winv before the bias (not `* 1`: the fp32 kernel keeps acc + bias)
+//   E::SCALE, e.winv()       the accumulator is un-scaled by winv before the bias (not `* 1`: the fp32 kernel keeps acc + bias)
 //   e.res(oi)                the residual at element oi of the output
 //   e.put(oi, row, col, v)   a finished value: element oi of the output, (pixel row, column) of the tile
 //   e.pair(om, cg, u0, u1)   EPI_GATE: the pair before the gate
@@ -127,7 +127,7 @@ __device__ __forceinline__ void naf_epilogue(const GemmArgs& p, const f32x16 (&a
   const int M = p.N * HWo;
   const int r31 = lane & 31;
   auto biased = [&](float a, float b) {
-    if constexpr (E::SCALE) return a * p.winv + b;
+    if constexpr (E::SCALE) return a * e.winv() + b;
     else return a + b;
   };
   // C/D map: column = lane & 31, row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5) (pixel)
@@ -173,12 +173,13 @@ __device__ __forceinline__ void naf_epilogue(const GemmArgs& p, const f32x16 (&a
   }
 }
 
-// fp32 output in global memory: naf_gemm_kernel (SCALE false) and naf_gemm_h3_kernel (SCALE true).  out2 is training's, which runs
-// in fp32 only (the host refuses it for the f16 forms).
+// fp32 output in global memory: naf_gemm_kernel (SCALE false) and naf_gemm_h3_kernel (SCALE true).  out2 is training's: fp32 here
+// (the host refuses it for f16x3); under f16 training storage the f16 kernel's policy stores it (fdsr_nafnet_h1.h).
 template <bool SCALE_>
 struct NafEpiF32 {
   static constexpr bool SCALE = SCALE_;
   const GemmArgs& p;
+  __device__ __forceinline__ float winv() const { return p.winv; }
   __device__ __forceinline__ float res(size_t oi) const { return p.res[oi]; }
   __device__ __forceinline__ void put(size_t oi, int, int, float v) const { p.out[oi] = v; }
   __device__ __forceinline__ void pair(int om, int cg, float u0, float u1) const {

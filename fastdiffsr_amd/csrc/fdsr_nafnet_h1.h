@@ -27,16 +27,24 @@ __device__ __forceinline__ _Float16 naf_to_h(float v, int* sat) {
 }
 
 // epilogue policies (naf_epilogue): res is f16; a finished value goes to global memory (f16, or fp32 under o32), or rounded into the
-// LDS tile [pixel row][column] of H1OP-byte rows
+// LDS tile [pixel row][column] of H1OP-byte rows.  wi: 2^-e, the kernel argument or (training) the device table's.  pair: training
+// keeps conv4's pair before the gate as f16 too, [M][Cout] in channel order
 struct NafEpiH1 {
   static constexpr bool SCALE = true;
   const GemmArgs& p;
+  float wi;
+  __device__ __forceinline__ float winv() const { return wi; }
   __device__ __forceinline__ float res(size_t oi) const { return (float)reinterpret_cast<const _Float16*>(p.res)[oi]; }
   __device__ __forceinline__ void put(size_t oi, int, int, float v) const {
     if (p.o32) p.out[oi] = v;
     else reinterpret_cast<_Float16*>(p.out)[oi] = naf_to_h(v, p.sat);
   }
-  __device__ __forceinline__ void pair(int, int, float, float) const {}
+  __device__ __forceinline__ void pair(int om, int cg, float u0, float u1) const {
+    if (!p.out2) return;
+    _Float16* o = reinterpret_cast<_Float16*>(p.out2);
+    o[(size_t)om * p.Cout + cg] = naf_to_h(u0, p.sat);
+    o[(size_t)om * p.Cout + (p.Cout >> 1) + cg] = naf_to_h(u1, p.sat);
+  }
 };
 struct NafEpiH1Lds : NafEpiH1 {
   unsigned char* tile;
@@ -144,12 +152,13 @@ __global__ void __launch_bounds__(NT) naf_gemm_h1_kernel(GemmArgs p) {
     __syncthreads();
   }
 
+  const float wi = p.winvp ? *p.winvp : p.winv;
   if (p.epi == EPI_PSHUF || p.o32) {
-    naf_epilogue(p, acc, m0, co0, lane, wave, NafEpiH1{p});
+    naf_epilogue(p, acc, m0, co0, lane, wave, NafEpiH1{p, wi});
     return;
   }
   // rounded values into LDS [pixel row][column of the tile], then 16 B per lane: a row's 8-column octets are whole (Cout % 8 == 0)
-  naf_epilogue(p, acc, m0, co0, lane, wave, NafEpiH1Lds{{p}, sA});
+  naf_epilogue(p, acc, m0, co0, lane, wave, NafEpiH1Lds{{p, wi}, sA});
   __syncthreads();
   const int M = p.N * p.Hout * p.Wout;
   const bool gate = p.epi == EPI_GATE;

@@ -12,8 +12,16 @@
 // gated product, the SCA vector, y, conv4's pair before the gate and its product.  Recomputed in the backward: the LN-modulated
 // inputs of conv1 / conv4 and the SCA-scaled input of conv3 (prologues of the weight-gradient kernel), conv2's outputs (in the gate's
 // backward), conv3's and conv5's outputs (for d beta / d gamma), SCA's and the RCAB's pooled means.
+//
+// f16 training storage (fdsr_nafnet_set_train_storage; the contract is in include/fdsr.h): the forward is fdsr_nafnet_h1.h's into
+// half-size slots, and every backward kernel that reads a saved activation is a template on the stored type (ACT_F32 / ACT_F16 through
+// fdsr_act_io.h's ActIO): it widens what it reads, which is exact, and computes in fp32 as before.  Gradients stay fp32 everywhere.
 
 namespace {
+
+constexpr int ACT_F32 = fdsr::PREC_F16X3, ACT_F16 = fdsr::PREC_F16;   // ActIO's names for fp32 and f16 elements in memory
+template <int ST>
+__device__ __forceinline__ float act_ld(const float* base, size_t i) { return fdsr::ActIO<ST>::load1(base, i); }
 
 constexpr int WG_CHUNK = 2048;   // pixels per partial sum of a weight gradient
 constexpr int WG_PB = 16;        // pixels per LDS stage
@@ -33,7 +41,10 @@ struct WgArgs {
 // dW[k][co] = sum over pixels of A[p][k] dY[p][co]; A is the forward GEMM's operand (im2col, with the forward's prologue), and
 // row k == K (when Keff > K) is a column of ones: the bias gradient.  Workgroup: 64 k x 64 co of one pixel chunk; wave w owns the
 // 32 x 32 tile (w & 1, w >> 1).  MFMA 32x32x2: A[i = k][kk = pixel], B[kk = pixel][j = co]; 16 pixels per stage.
-template <int PRO>
+// XS / DS: the stored type of x / dy (dy is a saved activation only for ups, whose operands are exchanged).  Where x is f16 and a
+// prologue forms A again, A is clamped and rounded to f16 as the forward staged it: dW is the derivative of the product the forward
+// computed.
+template <int PRO, int XS, int DS>
 __global__ void __launch_bounds__(256) naf_wgrad_kernel(WgArgs p) {
   __shared__ float sA[WG_PB * WG_P];
   __shared__ float sB[WG_PB * WG_P];
@@ -62,17 +73,18 @@ __global__ void __launch_bounds__(256) naf_wgrad_kernel(WgArgs p) {
       const int pix = p0 + pl0 + 4 * j;
       float a = 0.f, b = 0.f;
       if (pix < pend) {
-        if (cval) b = p.dy[(size_t)pix * p.ldy + co] * cm;
+        if (cval) b = act_ld<DS>(p.dy, (size_t)pix * p.ldy + co) * cm;
         if (kone) a = 1.f;
         else if (kval) {
           const int n = pix / HWo, r = pix - n * HWo;
           const int oy = r / p.Wout, ox = r - oy * p.Wout;
           const int iy = oy * p.S - p.P + ky, ix = ox * p.S - p.P + kx;
           if (iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win) {
-            a = p.x[(((size_t)n * p.Hin + iy) * p.Win + ix) * p.Cin + ci];
+            a = act_ld<XS>(p.x, (((size_t)n * p.Hin + iy) * p.Win + ix) * p.Cin + ci);
             if (PRO == PRO_MUL) a = naf_pro<PRO_MUL>(a, 0.f, 0.f, p.pmul[(size_t)n * p.pstride + ci], 0.f);
             if (PRO == PRO_LN)
               a = naf_pro<PRO_LN>(a, p.stats[2 * (size_t)pix], p.stats[2 * (size_t)pix + 1], p.pmul[(size_t)n * p.pstride + ci], p.padd[(size_t)n * p.pstride + ci]);
+            if (XS == ACT_F16 && PRO != PRO_NONE) a = (float)(_Float16)__builtin_amdgcn_fmed3f(a, -F16_MAX, F16_MAX);
           }
         }
       }
@@ -115,6 +127,7 @@ __global__ void __launch_bounds__(256) naf_wgrad_finish_kernel(const float* __re
 }
 
 // per-strip channel sums of a (mode 0), a b (mode 1) or a (b - mean) rstd (mode 2): part[n][strip][ch], as naf_chansum_kernel
+template <int AS, int BS>
 __global__ void __launch_bounds__(256) naf_dot_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ stats,
                                                       float* __restrict__ part, int HW, int c, int nstrips, int mode) {
   __shared__ float red[4][64];
@@ -126,9 +139,9 @@ __global__ void __launch_bounds__(256) naf_dot_kernel(const float* __restrict__ 
       const int pix = strip * STRIP + q;
       if (pix >= HW) break;
       const size_t gp = (size_t)n * HW + pix, i = gp * c + ch;
-      float v = a[i];
-      if (mode == 1) v *= b[i];
-      if (mode == 2) v *= (b[i] - stats[2 * gp]) * stats[2 * gp + 1];
+      float v = act_ld<AS>(a, i);
+      if (mode == 1) v *= act_ld<BS>(b, i);
+      if (mode == 2) v *= (act_ld<BS>(b, i) - stats[2 * gp]) * stats[2 * gp + 1];
       sum += v;
     }
   red[py][cl] = sum;
@@ -149,6 +162,7 @@ __global__ void __launch_bounds__(256) naf_reduce_kernel(const float* __restrict
 
 // LayerNorm + FiLM backward onto the running gradient: out = xh mul + add, xh = (x - mean) rstd;
 // g += rstd (d mul - mean_c(d mul) - xh mean_c(d mul xh)).  16 lanes per pixel, as naf_ln_stats_kernel.
+template <int XS>
 __global__ void __launch_bounds__(256) naf_ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ d, const float* __restrict__ stats,
                                                          const float* __restrict__ mul, int mstride, float* __restrict__ g, int M, int HW, int C) {
   const int sub = threadIdx.x & 15;
@@ -159,7 +173,7 @@ __global__ void __launch_bounds__(256) naf_ln_bwd_kernel(const float* __restrict
   const float mean = stats[2 * (size_t)(ok ? pix : 0)], rstd = stats[2 * (size_t)(ok ? pix : 0) + 1];
   float s1 = 0.f, s2 = 0.f;
   for (int c = sub; c < C; c += 16) {
-    const float dh = d[base + c] * m[c], xh = (x[base + c] - mean) * rstd;
+    const float dh = d[base + c] * m[c], xh = (act_ld<XS>(x, base + c) - mean) * rstd;
     s1 += dh;
     s2 += dh * xh;
   }
@@ -169,12 +183,13 @@ __global__ void __launch_bounds__(256) naf_ln_bwd_kernel(const float* __restrict
   s2 /= (float)C;
   if (!ok) return;
   for (int c = sub; c < C; c += 16) {
-    const float dh = d[base + c] * m[c], xh = (x[base + c] - mean) * rstd;
+    const float dh = d[base + c] * m[c], xh = (act_ld<XS>(x, base + c) - mean) * rstd;
     g[base + c] += rstd * (dh - s1 - xh * s2);
   }
 }
 
 // SimpleGate backward from the saved pair: out[p][j] = d[p][j] u[p][c + j], out[p][c + j] = d[p][j] u[p][j]
+template <int US>
 __global__ void __launch_bounds__(256) naf_gate_bwd_kernel(const float* __restrict__ d, const float* __restrict__ u, float* __restrict__ out, int c,
                                                            size_t total) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -182,11 +197,12 @@ __global__ void __launch_bounds__(256) naf_gate_bwd_kernel(const float* __restri
   const size_t pix = i / c;
   const int j = (int)(i - pix * c);
   const float v = d[i];
-  out[pix * 2 * c + j] = v * u[pix * 2 * c + c + j];
-  out[pix * 2 * c + c + j] = v * u[pix * 2 * c + j];
+  out[pix * 2 * c + j] = v * act_ld<US>(u, pix * 2 * c + c + j);
+  out[pix * 2 * c + c + j] = v * act_ld<US>(u, pix * 2 * c + j);
 }
 
 // x sca backward, then conv2's SimpleGate: d t2 = d[p][ch] sca[n][ch] + dpool[n][ch]; conv2's two outputs are formed again from x.
+template <int XS>
 __global__ void __launch_bounds__(256) naf_dwgate_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
                                                              const float* __restrict__ d, const float* __restrict__ sca, const float* __restrict__ dpool,
                                                              float* __restrict__ out, int H, int W, int c, size_t total) {
@@ -196,7 +212,7 @@ __global__ void __launch_bounds__(256) naf_dwgate_bwd_kernel(const float* __rest
   const int ch = (int)(i - gp * c), HW = H * W, C2 = 2 * c;
   const int n = (int)(gp / HW), pix = (int)(gp - (size_t)n * HW);
   const int yy = pix / W, xx = pix - yy * W;
-  const float* xn = x + (size_t)n * HW * C2;
+  const float* xn = XS == ACT_F16 ? x + (size_t)n * HW * c : x + (size_t)n * HW * C2;   // the image (C2 halves are c floats)
   float a0 = 0.f, a1 = 0.f;
 #pragma unroll
   for (int dy = 0; dy < 3; ++dy)
@@ -204,9 +220,9 @@ __global__ void __launch_bounds__(256) naf_dwgate_bwd_kernel(const float* __rest
     for (int dx = 0; dx < 3; ++dx) {
       const int iy = yy + dy - 1, ix = xx + dx - 1;
       if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
-      const float* src = xn + ((size_t)iy * W + ix) * C2;
-      a0 += w[(dy * 3 + dx) * C2 + ch] * src[ch];
-      a1 += w[(dy * 3 + dx) * C2 + c + ch] * src[c + ch];
+      const size_t src = ((size_t)iy * W + ix) * C2;
+      a0 += w[(dy * 3 + dx) * C2 + ch] * act_ld<XS>(xn, src + ch);
+      a1 += w[(dy * 3 + dx) * C2 + c + ch] * act_ld<XS>(xn, src + c + ch);
     }
   a0 += b[ch];
   a1 += b[c + ch];
@@ -217,6 +233,7 @@ __global__ void __launch_bounds__(256) naf_dwgate_bwd_kernel(const float* __rest
 
 // depthwise 3x3 backward: dx[q][ch] = sum_k w[k][ch] da[q - off_k][ch]; and the strip's sums of da[p] x[p + off_k] (k < 9) and of da
 // (k = 9): part[n][strip][10][C2]
+template <int XS>
 __global__ void __launch_bounds__(256) naf_dw_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ da,
                                                          float* __restrict__ dx, float* __restrict__ part, int H, int W, int C2, int nstrips) {
   __shared__ float red[4][10][64];
@@ -230,7 +247,7 @@ __global__ void __launch_bounds__(256) naf_dw_bwd_kernel(const float* __restrict
     float wk[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) wk[k] = w[k * C2 + ch];
-    const float* xn = x + (size_t)n * HW * C2;
+    const float* xn = XS == ACT_F16 ? x + (size_t)n * HW * (C2 / 2) : x + (size_t)n * HW * C2;   // the image (C2 is even)
     const float* dn = da + (size_t)n * HW * C2;
     for (int q = py; q < STRIP; q += 4) {
       const int pix = strip * STRIP + q;
@@ -244,7 +261,7 @@ __global__ void __launch_bounds__(256) naf_dw_bwd_kernel(const float* __restrict
         for (int dxx = 0; dxx < 3; ++dxx) {
           const int k = dy * 3 + dxx;
           const int fy = yy + dy - 1, fx = xx + dxx - 1;   // the forward tap of this pixel
-          if (fy >= 0 && fy < H && fx >= 0 && fx < W) acc[k] += dv * xn[((size_t)fy * W + fx) * C2 + ch];
+          if (fy >= 0 && fy < H && fx >= 0 && fx < W) acc[k] += dv * act_ld<XS>(xn, ((size_t)fy * W + fx) * C2 + ch);
           const int by = yy - dy + 1, bx = xx - dxx + 1;   // the output pixel that read this one through tap k
           if (by >= 0 && by < H && bx >= 0 && bx < W) s += wk[k] * dn[((size_t)by * W + bx) * C2 + ch];
         }
@@ -365,9 +382,10 @@ __global__ void __launch_bounds__(256) naf_scale_add_kernel(const float* __restr
   out[i] = g[i] * a[n * c + ch] + dpool[n * c + ch];
 }
 
+template <int YS>
 __global__ void __launch_bounds__(256) naf_relu_mask_kernel(float* __restrict__ g, const float* __restrict__ y, size_t total) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < total && !(y[i] > 0.f)) g[i] = 0.f;
+  if (i < total && !(act_ld<YS>(y, i) > 0.f)) g[i] = 0.f;
 }
 
 // g = 2 g + t: x + (rcab(x) + x) passes its gradient to x twice
@@ -605,6 +623,96 @@ __global__ void __launch_bounds__(256) naf_repack_kernel(float* __restrict__ are
   if (s >= 0) arena[i] = master[s];
 }
 
+// The f16 forms again from the re-packed arena, on the device (f16 training storage: the forward after a step reads the hi planes).
+// split_weights' arithmetic per GEMM, bit for bit: the maximum of min(|w|, 65504) over the pack (two passes, WQ_SLICES workgroups per GEMM), e = min(12, floor(log2(32768 / max)))
+// from the maximum's exponent and mantissa bits (32768 / max is a power of two exactly when the mantissa is zero), hi = f16(w 2^e),
+// lo = f16(w 2^e - hi) in fragment order.  A maximum has no order to keep.
+struct WqDesc {
+  unsigned long long woff, hoff;   // the pack's first float in the arena, the GEMM's first fragment in d_wq
+  unsigned h0;                     // the hi fragments before this GEMM's (a multiple of 256)
+  int Kp, Cp, nk;
+};
+
+constexpr int WQ_SLICES = 64;   // workgroups per GEMM of the maximum's first pass
+
+// max of min(|w|, 65504) over slice blockIdx.y of GEMM blockIdx.x's pack: part[gemm][slice]
+__global__ void __launch_bounds__(256) naf_wq_max_kernel(const float* __restrict__ arena, const WqDesc* __restrict__ desc, float* __restrict__ part) {
+  __shared__ float red[256];
+  const WqDesc g = desc[blockIdx.x];
+  const float* w = arena + g.woff;
+  const size_t total = (size_t)g.Kp * g.Cp;
+  float amax = 0.f;
+  for (size_t i = (size_t)blockIdx.y * 256 + threadIdx.x; i < total; i += (size_t)WQ_SLICES * 256) {
+    float v = fabsf(w[i]);
+    v = F16_MAX < v ? F16_MAX : v;   // std::min / std::max of the host, NaN for NaN
+    amax = amax < v ? v : amax;
+  }
+  red[threadIdx.x] = amax;
+  __syncthreads();
+  for (int o = 128; o; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] = red[threadIdx.x] < red[threadIdx.x + o] ? red[threadIdx.x + o] : red[threadIdx.x];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[(size_t)blockIdx.x * WQ_SLICES + blockIdx.y] = red[0];
+}
+
+// the slices' maxima -> e and 2^-e of GEMM blockIdx.x; one wave
+__global__ void __launch_bounds__(WQ_SLICES) naf_wq_scale_kernel(const float* __restrict__ part, float* __restrict__ hinv, int* __restrict__ hexp) {
+  float amax = part[(size_t)blockIdx.x * WQ_SLICES + threadIdx.x];
+#pragma unroll
+  for (int o = WQ_SLICES / 2; o; o >>= 1) {
+    const float other = __shfl_xor(amax, o, WQ_SLICES);
+    amax = amax < other ? other : amax;
+  }
+  if (threadIdx.x == 0) {
+    int e = 12;   // max <= 8: 32768 / max >= 2^12
+    if (amax > 8.f) {
+      const unsigned bits = __float_as_uint(amax);
+      e = 15 - ((int)(bits >> 23) - 127) - ((bits & 0x7fffffu) ? 1 : 0);
+    }
+    hexp[blockIdx.x] = e;
+    hinv[blockIdx.x] = __uint_as_float((unsigned)(127 - e) << 23);
+  }
+}
+
+// one thread per hi fragment (and its lo twin, 64 further): blocks do not straddle GEMMs
+__global__ void __launch_bounds__(256) naf_wq_pack_kernel(const float* __restrict__ arena, const WqDesc* __restrict__ desc, int ngemms,
+                                                          const int* __restrict__ hexp, uint4* __restrict__ wq, unsigned total) {
+  const unsigned gi = blockIdx.x * 256 + threadIdx.x;
+  if (gi >= total) return;
+  int lo = 0, hi = ngemms - 1;   // the last GEMM whose h0 <= gi
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (desc[mid].h0 <= gi) lo = mid;
+    else hi = mid - 1;
+  }
+  const WqDesc g = desc[lo];
+  const float scale = __uint_as_float((unsigned)(127 + hexp[lo]) << 23);
+  const unsigned idx = gi - g.h0;
+  const int l = idx & 63, s = (idx >> 6) & 1, nb = (idx >> 7) & 1;
+  const unsigned rest = idx >> 8;
+  const int kc = (int)(rest % (unsigned)g.nk), cot = (int)(rest / (unsigned)g.nk);
+  const int col = cot * BN + nb * 32 + (l & 31);
+  const float* w = arena + g.woff;
+  naf_h8 qh, ql;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int k = kc * HK + 16 * s + 8 * (l >> 5) + j;
+    float v = 0.f;
+    if (k < g.Kp) {
+      v = w[(size_t)k * g.Cp + col];
+      v = v < -F16_MAX ? -F16_MAX : v;
+      v = F16_MAX < v ? F16_MAX : v;
+      v = __fmul_rn(v, scale);
+    }
+    qh[j] = (_Float16)v;
+    ql[j] = (_Float16)__fsub_rn(v, (float)qh[j]);
+  }
+  uint4* dst = wq + g.hoff + (size_t)(idx >> 6) * 128 + l;
+  dst[0] = __builtin_bit_cast(uint4, qh);
+  dst[64] = __builtin_bit_cast(uint4, ql);
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 
 typedef Slots<size_t> BlockSlots;   // workspace offsets
@@ -634,8 +742,11 @@ TrainPlan make_train_plan(fdsr_nafnet n, int N, int H, int W) {
   const size_t M0 = (size_t)N * p.Hp * p.Wp;
   size_t off = 0;
   auto buf = [&](size_t floats) { const size_t o = off; off = align_up(off + floats * sizeof(float), 256); return o; };
+  // a saved activation: f16 elements under f16 training storage, in a slot of half the bytes
+  const size_t esz = n->train16() ? sizeof(_Float16) : sizeof(float);
+  auto abuf = [&](size_t elems) { const size_t o = off; off = align_up(off + elems * esz, 256); return o; };
   p.xin = buf(M0 * 6);
-  p.x0 = buf(M0 * w); p.r1 = buf(M0 * w); p.r = buf(M0 * w); p.enh = buf(M0 * w);
+  p.x0 = abuf(M0 * w); p.r1 = abuf(M0 * w); p.r = abuf(M0 * w); p.enh = abuf(M0 * w);
   p.ca = buf((size_t)N * w);
   p.eps = buf(M0 * 3); p.deps = buf(M0 * 3);
   p.tg = buf((size_t)N * 2 * w); p.trow = buf((size_t)N * n->R); p.tf = buf(N);
@@ -652,12 +763,12 @@ TrainPlan make_train_plan(fdsr_nafnet n, int N, int H, int W) {
     const int c = n->blocks[bi].c, l = ilog2(c / w);
     const size_t M = M0 >> (2 * l);
     BlockSlots& s = p.blk[bi];
-    s.out = buf(M * c); s.st1 = buf(M * 2); s.t1 = buf(M * 2 * c); s.t2 = buf(M * c); s.sca = buf((size_t)N * c);
-    s.y = buf(M * c); s.st2 = buf(M * 2); s.p4 = buf(M * 2 * c); s.g4 = buf(M * c);
+    s.out = abuf(M * c); s.st1 = buf(M * 2); s.t1 = abuf(M * 2 * c); s.t2 = abuf(M * c); s.sca = buf((size_t)N * c);
+    s.y = abuf(M * c); s.st2 = buf(M * 2); s.p4 = abuf(M * 2 * c); s.g4 = abuf(M * c);
   }
   for (int l = 0; l < L; ++l) {
-    p.down.push_back(buf((M0 * w) >> (l + 1)));                 // level l + 1
-    p.up.push_back(buf((M0 * w) >> (L - 1 - l)));               // ups[l] lands on level L - 1 - l
+    p.down.push_back(abuf((M0 * w) >> (l + 1)));                // level l + 1
+    p.up.push_back(abuf((M0 * w) >> (L - 1 - l)));              // ups[l] lands on level L - 1 - l
     p.dskip.push_back(buf((M0 * w) >> l));
   }
   size_t wg = 0;
@@ -694,6 +805,11 @@ int ensure_train(fdsr_nafnet n) {
       }
     HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_rowmap), rm.size() * sizeof(int)));
     HIPCHK(nullptr, hipMemcpy(n->d_rowmap, rm.data(), rm.size() * sizeof(int), hipMemcpyHostToDevice));
+    // the device rebuild of the f16 forms: each GEMM's place; its exponent e and the maximum's partial results after the table
+    std::vector<WqDesc> desc;
+    for (const GemmL& g : n->gemms) desc.push_back({g.woff, g.hoff, (unsigned)(g.hoff / 2), g.Kpad(), g.CoutPad(), g.K32() / HK});
+    HIPCHK(nullptr, hipMalloc(&n->d_hdesc, desc.size() * (sizeof(WqDesc) + sizeof(int) + WQ_SLICES * sizeof(float))));
+    HIPCHK(nullptr, hipMemcpy(n->d_hdesc, desc.data(), desc.size() * sizeof(WqDesc), hipMemcpyHostToDevice));
   }
   if (!n->master_valid) {
     HIPCHK(nullptr, hipDeviceSynchronize());
@@ -701,6 +817,22 @@ int ensure_train(fdsr_nafnet n) {
       HIPCHK(nullptr, hipMemcpy(n->d_master + n->poff[i], n->wts[i].host.data(), n->wts[i].host.size() * sizeof(float), hipMemcpyHostToDevice));
     n->master_valid = true;
   }
+  return FDSR_OK;
+}
+
+// after a re-pack under f16 training storage: the f16 forms and their scales follow the arena, stream-ordered, no host round trip
+int rebuild_wq(fdsr_nafnet n, hipStream_t st) {
+  if (!n->train16()) return FDSR_OK;
+  const WqDesc* desc = static_cast<const WqDesc*>(n->d_hdesc);
+  int* hexp = reinterpret_cast<int*>(static_cast<char*>(n->d_hdesc) + n->gemms.size() * sizeof(WqDesc));
+  const unsigned total = (unsigned)(n->hfrags / 2);
+  float* part = reinterpret_cast<float*>(hexp + n->gemms.size());   // [gemms][WQ_SLICES]
+  hipLaunchKernelGGL(naf_wq_max_kernel, dim3((unsigned)n->gemms.size(), WQ_SLICES), dim3(256), 0, st, n->d_arena, desc, part);
+  HIPCHK(nullptr, hipGetLastError());
+  hipLaunchKernelGGL(naf_wq_scale_kernel, dim3((unsigned)n->gemms.size()), dim3(WQ_SLICES), 0, st, part, n->d_hinv, hexp);
+  HIPCHK(nullptr, hipGetLastError());
+  hipLaunchKernelGGL(naf_wq_pack_kernel, dim3(total / 256), dim3(256), 0, st, n->d_arena, desc, (int)n->gemms.size(), hexp, n->d_wq, total);
+  HIPCHK(nullptr, hipGetLastError());
   return FDSR_OK;
 }
 
@@ -739,6 +871,19 @@ struct TrainRun : Run {
   const float* enc_in(int i) const { return i ? d.down[i - 1] : d.enh; }
 
   // ---- backward launchers ----
+  // A saved activation is f16 under f16 training storage (t16): SEL picks the kernel instance for the stored type of the operands
+  // that are saved activations.  Gradients are fp32 always: their copies too.
+#define NAF_SEL1(K, h) ((h) ? K<ACT_F16> : K<ACT_F32>)
+  void gcopy(float* dst, const float* src, size_t floats) {
+    (void)hipMemcpyAsync(dst, src, floats * sizeof(float), hipMemcpyDeviceToDevice, st);
+    check();
+  }
+  // conv3's / conv5's output (before beta / gamma and the residual) formed again in fp32 for d beta / d gamma: the forward's own
+  // kernel and operands, so under t16 the very value the forward scaled
+  void reform(int gi, const float* x, float* out, int h, int w, int pro = PRO_NONE, const float* pmul = nullptr, int pstride = 0) {
+    gemm(gi, x, out, h, w, EPI_BIAS, pro, pmul, nullptr, pstride, nullptr, nullptr, nullptr, nullptr, true);
+  }
+
   // weight (and bias) gradient of gemm gi: x its forward input (Hin x Win), dy [M][cout]
   void wgrad(int gi, const float* x, const float* dy, int Hin, int Win, int pro = PRO_NONE, const float* stats = nullptr, const float* pmul = nullptr,
              const float* padd = nullptr, int pstride = 0, const float* colmul = nullptr) {
@@ -749,25 +894,33 @@ struct TrainRun : Run {
     a.Hout = (Hin + 2 * g.p - g.ks) / g.s + 1;
     a.Wout = (Win + 2 * g.p - g.ks) / g.s + 1;
     a.Cout = g.cout; a.KW = g.ks; a.S = g.s; a.P = g.p; a.K = g.K(); a.Keff = g.b >= 0 ? a.K + 1 : a.K; a.ldy = g.cout; a.pstride = pstride;
-    wgrad_launch(a, pro, 0, g.ks * g.ks, G(g.w), g.b >= 0 ? G(g.b) : nullptr);
+    wgrad_launch(a, pro, 0, g.ks * g.ks, G(g.w), g.b >= 0 ? G(g.b) : nullptr, t16 && x != d.xin, false);
   }
 
-  void wgrad_launch(const WgArgs& a, int pro, int mode, int taps, float* gw, float* gb) {
+  // xh / dh: x / dy is a saved f16 activation
+  void wgrad_launch(const WgArgs& a, int pro, int mode, int taps, float* gw, float* gb, bool xh, bool dh) {
     const int M = a.N * a.Hout * a.Wout, nz = (M + WG_CHUNK - 1) / WG_CHUNK;
     const dim3 grid((unsigned)((a.Keff + 63) / 64), (unsigned)((a.Cout + 63) / 64), (unsigned)nz);
     if ((size_t)nz * grid.x * 64 * grid.y * 64 > tp.wg_floats) {
       if (err == FDSR_OK) err = fail(nullptr, FDSR_E_WORKSPACE, "fdsr_nafnet: weight-gradient scratch too small");
       return;
     }
-    launch(pro == PRO_LN ? naf_wgrad_kernel<PRO_LN> : pro == PRO_MUL ? naf_wgrad_kernel<PRO_MUL> : naf_wgrad_kernel<PRO_NONE>, grid, dim3(256), 0, a);
+    void (*k)(WgArgs) = pro == PRO_LN ? naf_wgrad_kernel<PRO_LN, ACT_F32, ACT_F32> : pro == PRO_MUL ? naf_wgrad_kernel<PRO_MUL, ACT_F32, ACT_F32>
+                                                                                                     : naf_wgrad_kernel<PRO_NONE, ACT_F32, ACT_F32>;
+    if (xh) k = pro == PRO_LN ? naf_wgrad_kernel<PRO_LN, ACT_F16, ACT_F32> : pro == PRO_MUL ? naf_wgrad_kernel<PRO_MUL, ACT_F16, ACT_F32>
+                                                                                             : naf_wgrad_kernel<PRO_NONE, ACT_F16, ACT_F32>;
+    if (dh) k = naf_wgrad_kernel<PRO_NONE, ACT_F32, ACT_F16>;   // ups: the gathered gradient is A, the saved input is "dy"
+    launch(k, grid, dim3(256), 0, a);
     launch(naf_wgrad_finish_kernel, dim3(nb((size_t)a.Keff * a.Cout)), dim3(256), 0, a.part, nz, (int)grid.x * 64, (int)grid.y * 64, a.Keff, a.K,
            a.Cout, a.Cin, taps, mode, gw, gb);
   }
 
   // per-channel sums over pixels: dst[g][ch], groups = N (per image, rows dstride apart) or 1 (everything)
-  void dot(const float* a, const float* b, const float* stats, int mode, int HW, int c, float* dst, bool per_image, int dstride, float scale = 1.f) {
+  // ah / bh: a / b is a saved activation (never both)
+  void dot(const float* a, const float* b, const float* stats, int mode, int HW, int c, float* dst, bool per_image, int dstride, float scale = 1.f,
+           bool ah = false, bool bh = false) {
     const int ns = nstrips_of(HW);
-    launch(naf_dot_kernel, dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)tp.N), dim3(256), 0, a, b, stats, d.part, HW, c, ns, mode);
+    launch(t16 && ah ? naf_dot_kernel<ACT_F16, ACT_F32> : t16 && bh ? naf_dot_kernel<ACT_F32, ACT_F16> : naf_dot_kernel<ACT_F32, ACT_F32>, dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)tp.N), dim3(256), 0, a, b, stats, d.part, HW, c, ns, mode);
     const int groups = per_image ? tp.N : 1, Gn = per_image ? ns : tp.N * ns;
     launch(naf_reduce_kernel, dim3(nb((size_t)groups * c)), dim3(256), 0, d.part, dst, groups, Gn, c, scale, dstride);
   }
@@ -775,9 +928,9 @@ struct TrainRun : Run {
   // LayerNorm + FiLM backward: g += d x; the image's d (folded scale) and d shift rows into drows
   void ln_bwd(const float* x, const float* dy, const float* stats, const float* mulrow, float* g, int HW, int c, float* dmul, float* dadd) {
     const int M = tp.N * HW;
-    dot(dy, x, stats, 2, HW, c, dmul, true, n->R);
+    dot(dy, x, stats, 2, HW, c, dmul, true, n->R, 1.f, false, true);
     dot(dy, nullptr, nullptr, 0, HW, c, dadd, true, n->R);
-    launch(naf_ln_bwd_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, x, dy, stats, mulrow, rstride, g, M, HW, c);
+    launch(NAF_SEL1(naf_ln_bwd_kernel, t16), dim3((unsigned)((M + 15) / 16)), dim3(256), 0, x, dy, stats, mulrow, rstride, g, M, HW, c);
   }
 
   // g: d out on entry, d inp on return (in place); cur: the block's input
@@ -791,25 +944,25 @@ struct TrainRun : Run {
     float* sm = F(tp.small);
     float *ds = sm, *pooled = sm + (size_t)tp.N * c, *dpool = sm + 2 * (size_t)tp.N * c;
     // out = y + conv5(g4) gamma
-    gemm(b.conv5, s.g4, gt, h, w, EPI_BIAS);
+    reform(b.conv5, s.g4, gt, h, w);
     dot(g, gt, nullptr, 1, HW, c, G(b.gamma), false, 0);
     wgrad(b.conv5, s.g4, g, h, w, PRO_NONE, nullptr, nullptr, nullptr, 0, P(b.off_gamma));
     gemm_l(n->tgemms[b.conv5], g, gt, h, w, EPI_BIAS, PRO_MUL, P(b.off_gamma), nullptr, 0);
-    launch(naf_gate_bwd_kernel, dim3(nb(tot)), dim3(256), 0, gt, s.p4, g2a, c, tot);
+    launch(NAF_SEL1(naf_gate_bwd_kernel, t16), dim3(nb(tot)), dim3(256), 0, gt, s.p4, g2a, c, tot);
     wgrad(b.conv4, s.y, g2a, h, w, PRO_LN, s.st2, rw + 3 * c, rw + 2 * c, rstride);
     gemm_l(n->tgemms[b.conv4], g2a, gt, h, w, EPI_BIAS);
     ln_bwd(s.y, gt, s.st2, rw + 3 * c, g, HW, c, dr + 3 * c, dr + 2 * c);
     // y = inp + conv3(t2 sca) beta
-    gemm(b.conv3, s.t2, gt, h, w, EPI_BIAS, PRO_MUL, s.sca, nullptr, c);
+    reform(b.conv3, s.t2, gt, h, w, PRO_MUL, s.sca, c);
     dot(g, gt, nullptr, 1, HW, c, G(b.beta), false, 0);
     wgrad(b.conv3, s.t2, g, h, w, PRO_MUL, nullptr, s.sca, nullptr, c, P(b.off_beta));
     gemm_l(n->tgemms[b.conv3], g, gt, h, w, EPI_BIAS, PRO_MUL, P(b.off_beta), nullptr, 0);
-    dot(gt, s.t2, nullptr, 1, HW, c, ds, true, c);
-    dot(s.t2, nullptr, nullptr, 0, HW, c, pooled, true, c, 1.f / (float)HW);
+    dot(gt, s.t2, nullptr, 1, HW, c, ds, true, c, 1.f, false, true);
+    dot(s.t2, nullptr, nullptr, 0, HW, c, pooled, true, c, 1.f / (float)HW, true);
     launch(naf_sca_bwd_w_kernel, dim3(nb((size_t)c * c)), dim3(256), 0, ds, pooled, G(b.scaw), G(b.scab), tp.N, c);
     launch(naf_sca_bwd_x_kernel, dim3(nb((size_t)tp.N * c)), dim3(256), 0, ds, P(b.off_scaw), dpool, tp.N, c, 1.f / (float)HW);
-    launch(naf_dwgate_bwd_kernel, dim3(nb(tot)), dim3(256), 0, s.t1, P(b.off_dww), P(b.off_dwb), gt, s.sca, dpool, g2a, h, w, c, tot);
-    launch(naf_dw_bwd_kernel, dim3((unsigned)ns, (unsigned)((2 * c + 63) / 64), (unsigned)tp.N), dim3(256), 0, s.t1, P(b.off_dww), g2a, g2b,
+    launch(NAF_SEL1(naf_dwgate_bwd_kernel, t16), dim3(nb(tot)), dim3(256), 0, s.t1, P(b.off_dww), P(b.off_dwb), gt, s.sca, dpool, g2a, h, w, c, tot);
+    launch(NAF_SEL1(naf_dw_bwd_kernel, t16), dim3((unsigned)ns, (unsigned)((2 * c + 63) / 64), (unsigned)tp.N), dim3(256), 0, s.t1, P(b.off_dww), g2a, g2b,
            d.part, h, w, 2 * c, ns);
     launch(naf_dw_finish_kernel, dim3(nb((size_t)20 * c)), dim3(256), 0, d.part, tp.N * ns, 2 * c, G(b.dww), G(b.dwb));
     wgrad(b.conv1, cur, g2b, h, w, PRO_LN, s.st1, rw + c, rw, rstride);
@@ -830,7 +983,7 @@ struct TrainRun : Run {
     for (int i = L - 1; i >= 0; --i) {
       chain_bwd(n->dec[i], d.up[i], g, h, w);
       // ups[i]: g is d (shuffle(conv(x)) + skip).  The skip's share is g itself; the convolution's is a 2x2 stride-2 gather of g.
-      copy(F(tp.dskip[L - 1 - i]), g, (size_t)tp.N * h * w * c);
+      gcopy(F(tp.dskip[L - 1 - i]), g, (size_t)tp.N * h * w * c);
       const float* x = i ? d.dec[i - 1] : d.mid;   // ups[i]'s forward input
       const GemmL& t = n->tgemms[n->ups[i]];
       const GemmL& gf = n->gemms[n->ups[i]];
@@ -839,7 +992,7 @@ struct TrainRun : Run {
         a.x = F(tp.dskip[L - 1 - i]); a.dy = x; a.part = F(tp.wgpart);
         a.N = tp.N; a.Hin = h; a.Win = w; a.Cin = t.cin; a.Hout = h / 2; a.Wout = w / 2; a.Cout = t.cout; a.KW = 2; a.S = 2; a.P = 0;
         a.K = t.K(); a.Keff = a.K; a.ldy = t.cout;
-        wgrad_launch(a, PRO_NONE, 1, 4, G(gf.w), nullptr);
+        wgrad_launch(a, PRO_NONE, 1, 4, G(gf.w), nullptr, false, t16);
       }
       gemm_l(t, F(tp.dskip[L - 1 - i]), g, h, w, EPI_BIAS);
       h /= 2; w /= 2; c *= 2;
@@ -850,7 +1003,7 @@ struct TrainRun : Run {
       wgrad(n->downs[i], d.skip[i], g, 2 * h, 2 * w);
       gemm_l(n->tgemms[n->downs[i]], g, gt, h, w, EPI_PSHUF, PRO_NONE, nullptr, nullptr, 0, nullptr, F(tp.dskip[i]));
       h *= 2; w *= 2; c /= 2;
-      copy(g, gt, (size_t)tp.N * h * w * c);
+      gcopy(g, gt, (size_t)tp.N * h * w * c);
       chain_bwd(n->enc[i], enc_in(i), g, h, w);
     }
     // enh = x0 + (r a + x0), a = CA(mean r)
@@ -859,8 +1012,9 @@ struct TrainRun : Run {
     float* sm = F(tp.small);
     float *da = sm, *dz2 = sm + (size_t)tp.N * wd, *pooled = sm + 2 * (size_t)tp.N * wd, *dpool = sm + 3 * (size_t)tp.N * wd,
           *dz1 = sm + 4 * (size_t)tp.N * wd, *hid = dz1 + (size_t)tp.N * cs;
-    dot(g, d.r, nullptr, 1, HW, wd, da, true, wd);
-    launch(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)tp.N), dim3(256), 0, d.r, d.part, HW, wd, ns);
+    dot(g, d.r, nullptr, 1, HW, wd, da, true, wd, 1.f, false, true);
+    if (t16) launch(naf_chansum_h_kernel, dim3((unsigned)ns, (unsigned)((wd + 127) / 128), (unsigned)tp.N), dim3(256), 0, H(d.r), d.part, HW, wd, ns);
+    else launch(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)tp.N), dim3(256), 0, d.r, d.part, HW, wd, ns);
     launch(naf_ca_bwd_kernel, dim3((unsigned)tp.N), dim3(256), (3 * wd + 256 + 2 * cs) * sizeof(float), d.part, ns, HW, P(n->off_ca1w),
            P(n->off_ca1b), P(n->off_ca2w), d.ca, da, dz2, dz1, hid, pooled, dpool, wd, cs);
     launch(naf_linear_w_kernel, dim3(nb((size_t)wd * cs)), dim3(256), 0, dz2, hid, G(n->ca2w), G(n->ca2b), tp.N, wd, cs);
@@ -868,7 +1022,7 @@ struct TrainRun : Run {
     launch(naf_scale_add_kernel, dim3(nb(tot)), dim3(256), 0, g, d.ca, dpool, gt, HW, wd, tot);
     wgrad(n->g_rcab2, d.r1, gt, h, w);
     gemm_l(n->tgemms[n->g_rcab2], gt, gu, h, w, EPI_BIAS);
-    launch(naf_relu_mask_kernel, dim3(nb(tot)), dim3(256), 0, gu, d.r1, tot);
+    launch(NAF_SEL1(naf_relu_mask_kernel, t16), dim3(nb(tot)), dim3(256), 0, gu, d.r1, tot);
     wgrad(n->g_rcab0, d.intro, gu, h, w);
     gemm_l(n->tgemms[n->g_rcab0], gu, gt, h, w, EPI_BIAS);
     launch(naf_twice_plus_kernel, dim3(nb(tot)), dim3(256), 0, g, gt, tot);
@@ -896,6 +1050,7 @@ struct TrainRun : Run {
     launch(naf_linear_w_kernel, dim3(nb((size_t)16 * wd * wd)), dim3(256), 0, dh2, g1, G(n->t2w), G(n->t2b), N, 4 * wd, 4 * wd);
     launch(naf_linear_w_kernel, dim3(nb((size_t)8 * wd * wd)), dim3(256), 0, dh1, emb, G(n->t1w), G(n->t1b), N, 8 * wd, wd);
   }
+#undef NAF_SEL1
 };
 
 // what train_grads, forward_train and backward check alike; the messages are train_grads'
@@ -955,6 +1110,7 @@ int fdsr_nafnet_train_grads(fdsr_nafnet n, const float* state_nchw, const float*
   char* ws = static_cast<char*>(workspace);
   const TrainPlan tp = make_train_plan(n, batch, height, width);
   TrainRun t{{n, train_dst(n, tp, ws), st, nullptr, n->R}, tp, ws};
+  t.t16 = n->train16();
   HIPCHK(nullptr, hipMemsetAsync(n->d_grad, 0, n->P * sizeof(float), st));
   HIPCHK(nullptr, hipMemsetAsync(t.F(tp.deps), 0, (size_t)batch * tp.Hp * tp.Wp * 3 * sizeof(float), st));
   t.launch(naf_i2f_kernel, dim3(Run::nb(batch)), dim3(256), 0, timesteps_dev, t.F(tp.tf), batch);
@@ -988,6 +1144,7 @@ int fdsr_nafnet_forward_train(fdsr_nafnet n, const float* x_nchw, const float* c
   char* ws = static_cast<char*>(workspace);
   const TrainPlan tp = make_train_plan(n, batch, height, width);
   TrainRun t{{n, train_dst(n, tp, ws), st, nullptr, n->R}, tp, ws};
+  t.t16 = n->train16();
   HIPCHK(nullptr, hipMemcpyAsync(t.F(tp.tf), time_dev, (size_t)batch * sizeof(float), hipMemcpyDeviceToDevice, st));   // time_bwd reads it
   t.time_rows(t.F(tp.tf), batch, t.d.tg, t.d.trow);
   t.rows = t.d.trow;
@@ -1019,6 +1176,7 @@ int fdsr_nafnet_backward(fdsr_nafnet n, int64_t ticket, const float* d_out_nchw,
   char* ws = static_cast<char*>(workspace);
   const TrainPlan tp = make_train_plan(n, batch, height, width);
   TrainRun t{{n, train_dst(n, tp, ws), st, nullptr, n->R}, tp, ws};
+  t.t16 = n->train16();
   t.rows = t.d.trow;
   HIPCHK(nullptr, hipMemsetAsync(n->d_grad, 0, n->P * sizeof(float), st));
   const size_t total = (size_t)batch * tp.Hp * tp.Wp;
@@ -1052,6 +1210,7 @@ int fdsr_nafnet_set_weights_flat(fdsr_nafnet n, const float* src_dev, size_t cou
   HIPCHK(nullptr, hipMemcpyAsync(n->d_master, src_dev, n->P * sizeof(float), hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(naf_repack_kernel, dim3(Run::nb(n->arena_floats)), dim3(256), 0, st, n->d_arena, n->d_master, n->d_map, n->arena_floats);
   HIPCHK(nullptr, hipGetLastError());
+  if ((rc = rebuild_wq(n, st))) return rc;
   n->host_stale = true;
   n->table_valid = false;
   kill_ticket(n, fn);
@@ -1087,6 +1246,7 @@ int fdsr_nafnet_optim_step(fdsr_nafnet n, int kind, double lr, double beta1, dou
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_optim_step: training runs in FDSR_PREC_F32 only, the object is in f16x3");
   if (!n->d_grad || !n->master_valid || n->dirty) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet_optim_step: no gradients (fdsr_nafnet_train_grads first)");
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
+  int rc = FDSR_OK;
   kill_ticket(n, "fdsr_nafnet_optim_step");
   n->opt_step += 1;
   OptArgs o{};
@@ -1099,6 +1259,7 @@ int fdsr_nafnet_optim_step(fdsr_nafnet n, int kind, double lr, double beta1, dou
   HIPCHK(nullptr, hipGetLastError());
   hipLaunchKernelGGL(naf_repack_kernel, dim3(Run::nb(n->arena_floats)), dim3(256), 0, st, n->d_arena, n->d_master, n->d_map, n->arena_floats);
   HIPCHK(nullptr, hipGetLastError());
+  if ((rc = rebuild_wq(n, st))) return rc;
   n->host_stale = true;
   n->table_valid = false;
   drop_graph(n);

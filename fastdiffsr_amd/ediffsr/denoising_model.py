@@ -3,13 +3,20 @@ around ConditionalNAFNet.  optimize_parameters is one engine call for the loss a
 learning-rate schedules are evaluated on the host.  Not on this engine-only path: the EMA copy, multi-rank training,
 is_weighted, any loss other than l1 / l2.  All four are reached the other way round: the reference's own DenoisingModel around
 this package's ConditionalNAFNet with requires_grad_(True), whose forward is differentiable through torch autograd (model.py;
-INTEGRATION 6).  On neither path: 16-bit modes for training, DenoisingUNet_arch."""
+INTEGRATION 6).  On neither path: f16x3 or bf16 training, DenoisingUNet_arch.
+
+train_precision='f16' trains with f16 activation storage and fp32 gradients (ConditionalNAFNet.set_train_precision).  Its range
+guard is read after every train_grads: a step whose forward left the f16 range is skipped -- the weights and the optimizer state
+stay as they were -- with a warning that names the iteration; skipped_steps counts them and consecutive_skips the current run,
+which ediffsr.train stops on."""
 import math
 import os
+import warnings
 from collections import OrderedDict
 
 import torch
 
+from .. import _lib
 from .model import ConditionalNAFNet
 
 
@@ -35,14 +42,19 @@ def multistep_restart_lr(base_lr, step, milestones, gamma=0.1, restarts=None, we
 
 
 class DenoisingModel:
-    def __init__(self, opt):
+    def __init__(self, opt, train_precision='f32'):
         self.opt = opt
+        self.train_precision = train_precision
+        self.skipped_steps = 0        # optimizer steps skipped because the f16 forward saturated
+        self.consecutive_skips = 0    # ... since the last step that was taken
         self.is_train = opt.get('is_train', True)
         self.device = torch.device('cuda', torch.cuda.current_device())
         net = opt['network_G']
         if net.get('which_model_G', 'ConditionalNAFNet') != 'ConditionalNAFNet':
             raise NotImplementedError('only ConditionalNAFNet trains on this engine (not %s)' % net['which_model_G'])
         self.model = ConditionalNAFNet(**net['setting']).to(self.device)
+        if train_precision != 'f32':
+            self.model.set_train_precision(train_precision)
         self.schedulers, self.optimizers = [], []
         self.log_dict = OrderedDict()
         self.load()
@@ -74,8 +86,18 @@ class DenoisingModel:
     def optimize_parameters(self, step, timesteps, sde=None):
         sde.set_mu(self.condition)
         out = self.model.train_grads(self.state, self.condition, self.state_0, timesteps, loss_type=self.loss_type, weight=self.weight)
-        self.model.optim_step(self.optimizer, self.lr, self.betas, 1e-8, self.wd)
         self.log_dict['loss'] = out[0].item()
+        if self.train_precision == 'f16':   # the .item() above has synchronised already
+            try:
+                self.model.check_saturation()
+            except _lib.FdsrSaturated:
+                self.skipped_steps += 1
+                self.consecutive_skips += 1
+                warnings.warn('iteration %d: an activation left the f16 range, the optimizer step is skipped (%d skipped so far)'
+                              % (step, self.skipped_steps))
+                return
+        self.consecutive_skips = 0
+        self.model.optim_step(self.optimizer, self.lr, self.betas, 1e-8, self.wd)
 
     def test(self, sde=None, save_states=False):
         sde.set_mu(self.condition)

@@ -125,11 +125,12 @@ class ConditionalNAFNet(nn.Module):
 
     def __getstate__(self):
         """What copy.deepcopy and pickle carry: the parameters and the configuration.  The engine object and what belongs to
-        it stay behind -- the handle, the upload stamp, the workspaces, the graph stream, and the precision and schedule that
-        were set on that handle -- so a copy creates an engine of its own (in 'f32', without a schedule) on first use."""
+        it stay behind -- the handle, the upload stamp, the workspaces, the graph stream, and the precision, the training
+        precision and the schedule that were set on that handle -- so a copy creates an engine of its own (in 'f32', training
+        in 'f32', without a schedule) on first use."""
         d = dict(self.__dict__)
         d['_h'], d['_uploaded'], d['_ws'] = None, None, {}
-        for k in ('_graph_stream', '_precision', '_sde_T'):
+        for k in ('_graph_stream', '_precision', '_train_precision', '_sde_T'):
             d.pop(k, None)
         return d
 
@@ -277,10 +278,32 @@ class ConditionalNAFNet(nn.Module):
                 _lib.check(None, lib.fdsr_nafnet_set_storage(h, _lib.FDSR_NAF_STORE_F16))
         self._precision = mode
 
+    # ---- storage of the activations a training call keeps (include/fdsr.h: fdsr_nafnet_set_train_storage) ----
+    TRAIN_PRECISIONS = ('f32', 'f16')
+
+    @property
+    def train_precision(self):
+        return getattr(self, '_train_precision', 'f32')
+
+    def set_train_precision(self, mode):
+        """'f32' (the default) or 'f16': mixed-precision training.  Under 'f16' train_grads, the autograd bridge and optim_step
+        run the f16-storage forward into a training workspace of about half the bytes and keep every gradient in fp32 (no loss
+        scaling); check_saturation after train_grads tells whether a stored value left the f16 range.  The setting is the
+        training calls' own: forward, debug_tensor and sample follow set_precision as before, and it takes effect only while
+        that is 'f32' (under 'f16x3' and 'f16' training refuses as it always did)."""
+        if mode not in self.TRAIN_PRECISIONS:
+            raise ValueError('train precision must be one of %s, not %r' % (self.TRAIN_PRECISIONS, mode))
+        dev = next(self.parameters()).device
+        with torch.cuda.device(dev) if dev.type == 'cuda' else contextlib.nullcontext():
+            _lib.check(None, _lib.load().fdsr_nafnet_set_train_storage(
+                self._handle(), _lib.FDSR_NAF_STORE_F16 if mode == 'f16' else _lib.FDSR_NAF_STORE_F32))
+        self._train_precision = mode
+
     def check_saturation(self):
         """f16x3 clamps GEMM inputs beyond +-65504 and raises a sticky flag, f16 does so for every value it stores or stages:
         synchronises, reads and clears it.  Raises _lib.FdsrSaturated when it was set (re-run the calls since the last check
-        in 'f32'); a no-op in 'f32'."""
+        in 'f32'); a no-op in 'f32'.  Training under set_train_precision('f16') raises the same flag from the
+        stores of its forward: the gradients of that train_grads are then not to be used."""
         dev = next(self.parameters()).device
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream

@@ -1,6 +1,6 @@
 """EDiffSR's config/sisr/train.py on the HIP engine, driven by the reference's own YAML options:
 
-    python -m fastdiffsr_amd.ediffsr.train -opt setting_mfe_Train_x4.yml [--batch N] [--seed S] [--root DIR]
+    python -m fastdiffsr_amd.ediffsr.train -opt setting_mfe_Train_x4.yml [--batch N] [--seed S] [--root DIR] [--precision f32|f16]
 
 Reads `sde`, `degradation.scale`, `datasets.train` / `datasets.val` (dataroot_GT / dataroot_LQ, GT_size, use_flip, use_rot,
 batch_size), `network_G.setting`, `train.*`, `logger.print_freq` / `save_checkpoint_freq`, `path.pretrain_model_G` /
@@ -8,7 +8,9 @@ batch_size), `network_G.setting`, `train.*`, `logger.print_freq` / `save_checkpo
 upscale on the device, IRSDE.generate_random_states, DenoisingModel.optimize_parameters, the lr update; a log line every
 print_freq, a val pass (PSNR through ediffsr/test.py) every val_freq, `{iter}_G.pth` and `{iter}.state` every
 save_checkpoint_freq under <root>/models and <root>/training_state (root: --root, else experiments/<name>).
-Single process; no EMA copy.  Returns {'losses', 'lrs', 'psnr', 'iter'}."""
+--precision f16 trains with f16 activation storage and fp32 gradients; the val passes sample as they do under f32.  A
+step whose forward leaves the f16 range is skipped; after MAX_CONSECUTIVE_SKIPS such steps in a row the run stops and names
+--precision f32.  Single process; no EMA copy.  Returns {'losses', 'lrs', 'psnr', 'iter'}."""
 import argparse
 import os
 import random
@@ -20,6 +22,20 @@ from .denoising_model import DenoisingModel
 from .model import upscale
 from .sde import IRSDE
 from . import test as T
+
+
+MAX_CONSECUTIVE_SKIPS = 10
+
+
+def make_parser():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('-opt', required=True, help='the reference\'s YAML train options')
+    ap.add_argument('--batch', type=int, default=None, help='overrides datasets.train.batch_size')
+    ap.add_argument('--seed', type=int, default=None, help='overrides train.manual_seed')
+    ap.add_argument('--root', default=None, help='experiment folder (default: experiments/<name>)')
+    ap.add_argument('--precision', choices=('f32', 'f16'), default='f32',
+                    help='storage of the activations training keeps: f32 (default) or f16 (mixed precision, fp32 gradients)')
+    return ap
 
 
 def parse_options(path):
@@ -70,12 +86,7 @@ def _train_batch(ds, pairs, order, pos, batch, scale):
 
 def main(argv=None):
     from .. import metrics as M
-    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('-opt', required=True, help='the reference\'s YAML train options')
-    ap.add_argument('--batch', type=int, default=None, help='overrides datasets.train.batch_size')
-    ap.add_argument('--seed', type=int, default=None, help='overrides train.manual_seed')
-    ap.add_argument('--root', default=None, help='experiment folder (default: experiments/<name>)')
-    a = ap.parse_args(argv)
+    a = make_parser().parse_args(argv)
     opt = parse_options(a.opt)
     seed = a.seed if a.seed is not None else (opt['train'].get('manual_seed') or 0)
     random.seed(seed)
@@ -86,7 +97,7 @@ def main(argv=None):
     for d in (opt['path']['models'], opt['path']['training_state']):
         os.makedirs(d, exist_ok=True)
     device = torch.device('cuda', torch.cuda.current_device())
-    model = DenoisingModel(opt)
+    model = DenoisingModel(opt, train_precision=a.precision)
     s = opt['sde']
     sde = IRSDE(max_sigma=s['max_sigma'], T=s['T'], schedule=s['schedule'], eps=s['eps'], device=device)
     sde.set_model(model.model)
@@ -124,6 +135,9 @@ def main(argv=None):
         timesteps, states = sde.generate_random_states(x0=GT, mu=LQ)
         model.feed_data(states, LQ, GT)
         model.optimize_parameters(step, timesteps, sde)
+        if model.consecutive_skips >= MAX_CONSECUTIVE_SKIPS:
+            raise RuntimeError('iteration %d: %d steps in a row left the f16 range and were skipped; train this model with --precision f32'
+                               % (step, model.consecutive_skips))
         lr_used = model.get_current_learning_rate()
         model.update_learning_rate(step, warmup_iter=tr.get('warmup_iter', -1))
         losses.append(model.get_current_log()['loss'])
@@ -139,7 +153,8 @@ def main(argv=None):
             print('Saving models and training states.')
             model.save(step)
             model.save_training_state(epoch, step)
-    return {'losses': losses, 'lrs': lrs, 'psnr': psnrs, 'iter': step, 'opt_step': model.model.optim_state(model.model._names[0])[2]}
+    return {'losses': losses, 'lrs': lrs, 'psnr': psnrs, 'iter': step, 'opt_step': model.model.optim_state(model.model._names[0])[2],
+            'skipped': model.skipped_steps}
 
 
 if __name__ == '__main__':

@@ -380,8 +380,9 @@ void fdsr_nafnet_destroy(fdsr_nafnet n);
  *   fdsr_nafnet_check_saturation   f16x3 clamps a GEMM input beyond +-65504 to the f16 range and raises a sticky device flag (so does a NaN).
  *                             This call synchronises hip_stream, reads and clears the flag: FDSR_OK or FDSR_E_SATURATED (the
  *                             outputs since the last check are then not fp32-grade: re-run them in FDSR_PREC_F32, which has no
- *                             such limit).  FDSR_NAF_STORE_F16 raises the same flag from its stores too.  Always FDSR_OK in FDSR_PREC_F32
- *                             with FDSR_NAF_STORE_F32. */
+ *                             such limit).  FDSR_NAF_STORE_F16 raises the same flag from its stores too, and so does a training call under
+ *                             fdsr_nafnet_set_train_storage(FDSR_NAF_STORE_F16).  Otherwise always FDSR_OK in FDSR_PREC_F32 with
+ *                             FDSR_NAF_STORE_F32. */
 int fdsr_nafnet_set_precision(fdsr_nafnet n, int mode);
 int fdsr_nafnet_check_saturation(fdsr_nafnet n, void* hip_stream);
 /* Storage of the NAFNet's activations: the 16-bit, PSNR-grade sampling mode (11 mantissa bits; not fp32-grade).
@@ -481,6 +482,42 @@ int fdsr_nafnet_read_weight(fdsr_nafnet n, const char* key, float* dst, int dst_
 int fdsr_nafnet_optim_get_state(fdsr_nafnet n, const char* key, float* exp_avg_host, float* exp_avg_sq_host, int64_t* step);
 int fdsr_nafnet_optim_set_state(fdsr_nafnet n, const char* key, const float* exp_avg_host, const float* exp_avg_sq_host,
                                 int64_t step);
+
+/* Training with f16 activation storage: mixed precision for the training calls, opt-in, fp32 gradients, no loss scaling.
+ *   fdsr_nafnet_set_train_storage   FDSR_NAF_STORE_F32 (default) or FDSR_NAF_STORE_F16; any other value: FDSR_E_INVALID.  A setting
+ *                             of the training calls alone -- fdsr_nafnet_train_grads, _forward_train, _backward, _optim_step,
+ *                             _set_weights_flat and fdsr_nafnet_train_workspace_bytes, which answers for the current setting.  It
+ *                             takes effect while the sampling side is FDSR_PREC_F32 with FDSR_NAF_STORE_F32; with the object in
+ *                             f16x3 or in sampling f16 storage the training calls refuse as they always did, whatever this setting.
+ *                             fdsr_nafnet_forward / _sample / _debug_tensor never look at it.  A change rebuilds the weight forms
+ *                             on the next call and makes an outstanding ticket stale, as the other switches do.
+ *     Forward.  The f16-storage forward of fdsr_nafnet_set_storage above: its kernels, roundings and range guard, written into the
+ *       training slots.  Stored as f16: intro, the RCAB's two convolution outputs, x + enhance(x), per block out, conv1's output, the
+ *       depthwise + gate output, y, conv4's pair before the gate (each half rounded once from the fp32 value the gate multiplies) and
+ *       the gate output, the downs and the ups.  fp32 as before: LayerNorm statistics, SCA / CA vectors, strip sums, time rows, the
+ *       6-channel input, eps, the loss head.  fdsr_nafnet_forward_train's out equals fdsr_nafnet_forward's under FDSR_NAF_STORE_F16
+ *       bit for bit.
+ *     Workspace.  An f16 tensor has a slot of half the bytes (not the first half of an fp32 slot).
+ *     Backward.  Every gradient tensor in memory and the flat parameter gradient are fp32.  A kernel widens what it reads of the
+ *       saved forward (exact) and computes in fp32 as the fp32 step does; the gradient is that of the forward as computed, a
+ *       rounding passed straight through (d round(v) / d v = 1).  The three choices:
+ *       - weight gradients: exact fp32 MFMAs, dW = A^T dY with dY fp32.  Where a prologue forms A again (LN + FiLM for conv1 /
+ *         conv4, the SCA multiply for conv3), A is clamped and rounded to f16 as the forward staged it; a saved f16 input without a
+ *         prologue is A as it is.  intro's A is the fp32 6-channel input, not rounded (the forward's staging rounded it).
+ *       - input gradients: the exact fp32 kernel over the fp32 transposed packs, dX = dY W^T with the master's w, not the hi plane
+ *         f16(w 2^e) 2^-e the forward multiplied by (they differ by 2^-12 |w| at most).
+ *       - d beta / d gamma: conv3's and conv5's outputs are formed again by the forward's own f16 kernel on the saved input, with
+ *         an fp32 store: the very value the forward scaled by beta / gamma, before any rounding.
+ *       What the forward formed from fp32 values before a rounding and the backward can only form from the stored ones: SCA's pooled
+ *       mean in d W_sca (from the stored gate output), the gate's partners in conv4's gate backward (the stored pair), ReLU's mask
+ *       (the stored output).  Every sum keeps one order fixed by the shapes, there are no atomics, two calls give the same bits.
+ *     Weights after a step.  fdsr_nafnet_optim_step and fdsr_nafnet_set_weights_flat rebuild the f16 weight forms on the device from
+ *       the re-packed arena (per GEMM: max |w| -> e, then f16(w 2^e) and the lo plane in fragment order), bit for bit what the host
+ *       builds from the same master; 2^-e goes to a small device table that the training launches of the f16 GEMM kernel read
+ *       (sampling passes it as a kernel argument, as before).  No host round trip.
+ *     Range.  The f16 stores raise the sticky flag as in sampling: fdsr_nafnet_check_saturation after fdsr_nafnet_train_grads /
+ *       _forward_train returns FDSR_E_SATURATED (and clears it); the gradients of that call are not to be used. */
+int fdsr_nafnet_set_train_storage(fdsr_nafnet n, int mode);
 
 /* -- input-pipeline helper------------------------------------ */
 /* The dataset's tensor transform on the device (data/util.py:66-75 transform_augment: ToTensor() = uint8 / 255 as fp32,

@@ -1,6 +1,6 @@
 """EDiffSR training-step times on one GPU -> profiles/ediffsr_train_timing.txt (or --out).
 
-    python tools/ediffsr_train_timing.py [--out FILE] [--size 256] [--repeats 5] [--baseline] [--bridge]
+    python tools/ediffsr_train_timing.py [--out FILE] [--append] [--size 256] [--repeats 5] [--baseline] [--bridge] [--precision f32|f16]
 
 Shipped setting (width 64, enc [14,1,1,1]), synthetic weights, l1 loss, AdamW (lr 4e-5, betas 0.9 / 0.99), B = 2 (the
 reference's batch_size) and B = 16: one step = fdsr_nafnet_train_grads + fdsr_nafnet_optim_step with the parameter copy-back, ms
@@ -8,8 +8,9 @@ per step and images/s as the median of --repeats timed steps after two warm-up s
 workspace bytes.  --baseline adds the same step of tests/ediffsr_train_restatement.py through stock PyTorch autograd and
 torch.optim.AdamW on the same GPU, fp32: a baseline only, never the product path.  --bridge adds the step through torch autograd
 on the engine (model.requires_grad_(True): fdsr_nafnet_forward_train, IRSDE's loss terms in torch, fdsr_nafnet_backward,
-torch.optim.AdamW, the weights back through fdsr_nafnet_set_weights_flat), and the same without the optimizer.  The file records what
-was seen."""
+torch.optim.AdamW, the weights back through fdsr_nafnet_set_weights_flat), and the same without the optimizer.  --precision f16 times
+the engine (and the bridge) with f16 activation storage for training (set_train_precision('f16'): fp32 gradients); the baseline
+stays fp32.  --append adds to the file instead of replacing it.  The file records what was seen."""
 import argparse
 import os
 import statistics
@@ -45,6 +46,8 @@ def main():
     ap.add_argument('--repeats', type=int, default=5)
     ap.add_argument('--baseline', action='store_true')
     ap.add_argument('--bridge', action='store_true')
+    ap.add_argument('--append', action='store_true')
+    ap.add_argument('--precision', choices=('f32', 'f16'), default='f32')
     a = ap.parse_args()
     from fastdiffsr_amd.ediffsr import ConditionalNAFNet, IRSDE
     from fastdiffsr_amd.synth import synth_nafnet
@@ -52,8 +55,9 @@ def main():
     dev = torch.device('cuda', torch.cuda.current_device())
     sd = {k: torch.from_numpy(v) for k, v in synth_nafnet(0, **SETTING).items()}
     sde = IRSDE(max_sigma=50, T=100, schedule='cosine', eps=0.005, device='cpu')
-    lines = ['EDiffSR training timing: %s, width 64 enc [14,1,1,1], %dx%d, fp32 (exact-fp32 MFMA), l1, AdamW' % (
-        torch.cuda.get_device_name(dev), a.size, a.size), 'command: python tools/ediffsr_train_timing.py ' + ' '.join(sys.argv[1:])]
+    lines = ['EDiffSR training timing: %s, width 64 enc [14,1,1,1], %dx%d, %s, l1, AdamW' % (
+        torch.cuda.get_device_name(dev), a.size, a.size,
+        'fp32 (exact-fp32 MFMA)' if a.precision == 'f32' else 'f16 activation storage for training (f16 MFMA forward, fp32 gradients)'), 'command: python tools/ediffsr_train_timing.py ' + ' '.join(sys.argv[1:])]
     for b in (2, 16):
         g = torch.Generator().manual_seed(b)
         gt = torch.rand(b, 3, a.size, a.size, generator=g)
@@ -65,14 +69,16 @@ def main():
         m = ConditionalNAFNet(**SETTING)
         m.load_state_dict(sd, strict=True)
         m = m.to(dev).eval()
+        m.set_train_precision(a.precision)
         sde.set_model(m)
 
         def step():
             m.train_grads(x, c, y, ts)
             m.optim_step('AdamW', 4e-5, (0.9, 0.99), 1e-8, 0.0)
         med, lo, hi = timed(step, a.repeats)
-        lines.append('step      B=%-2d engine    %9.2f ms/step  %7.2f images/s  (median of %d; min %.2f max %.2f)  workspace %.2f GiB' % (
-            b, med, b * 1000 / med, a.repeats, lo, hi, m.train_workspace_bytes(b, a.size, a.size) / 2 ** 30))
+        lines.append('step      B=%-2d %-10s%9.2f ms/step  %7.2f images/s  (median of %d; min %.2f max %.2f)  workspace %.2f GiB' % (
+            b, 'engine' if a.precision == 'f32' else 'engine-f16', med, b * 1000 / med, a.repeats, lo, hi,
+            m.train_workspace_bytes(b, a.size, a.size) / 2 ** 30))
         print(lines[-1], flush=True)
         del m
         torch.cuda.empty_cache()
@@ -80,6 +86,7 @@ def main():
             m = ConditionalNAFNet(**SETTING)
             m.load_state_dict(sd, strict=True)
             m = m.to(dev).train().requires_grad_(True)
+            m.set_train_precision(a.precision)
             dsde = IRSDE(max_sigma=50, T=100, schedule='cosine', eps=0.005, device=dev)
             dsde.set_model(m)
             dsde.set_mu(c)
@@ -119,7 +126,7 @@ def main():
             del w, opt
             torch.cuda.empty_cache()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
+    with open(a.out, 'a' if a.append else 'w') as f:
         f.write('\n'.join(lines) + '\n')
 
 
