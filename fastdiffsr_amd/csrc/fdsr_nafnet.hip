@@ -472,8 +472,7 @@ struct GemmL {
   int cin = 0, cout = 0, ks = 1, s = 1, p = 0;
   bool gate = false;
   size_t woff = 0, boff = 0;   // float offsets into the device arena
-  bool split = false;          // f16x3: has a split form (the forward GEMMs; build_schema)
-  size_t hoff = 0;             //        its first 16-byte fragment
+  size_t hoff = 0;             // f16x3 (the forward GEMMs; build_schema): the split form's first 16-byte fragment
   int hidx = 0;                //        its entry in the device table of scales (d_hinv)
   float hinv = 1.f;            //        2^-e of the split form's scale (split_weights)
   int K32() const { return round_up(K(), HK); }
@@ -521,9 +520,7 @@ struct fdsr_nafnet_obj {
   // FDSR_PREC_F16X3: hi / lo planes of the forward GEMMs' weights (built by finalize in that mode) and the range flag
   int prec = FDSR_PREC_F32;
   int store = FDSR_NAF_STORE_F32;   // FDSR_NAF_STORE_F16: f16 activations, the hi planes of d_wq, the same flag (fdsr_nafnet_h1.h)
-  // training's own storage setting; it takes effect while the sampling side is FDSR_PREC_F32 with FDSR_NAF_STORE_F32
-  int train_store = FDSR_NAF_STORE_F32;
-  bool train16() const { return train_store == FDSR_NAF_STORE_F16 && store == FDSR_NAF_STORE_F32 && prec == FDSR_PREC_F32; }
+  int train_store = FDSR_NAF_STORE_F32;   // training's own storage setting.  What the three make of a call: mode_of
   size_t hfrags = 0;
   uint4* d_wq = nullptr;
   float* d_hinv = nullptr;   // [gemms]: 2^-e of every split form, as split_weights / naf_wq_scale_kernel left it
@@ -565,6 +562,24 @@ void drop_graph(fdsr_nafnet n) {
   if (n->graph.exec) (void)hipGraphExecDestroy(n->graph.exec);
   n->graph.exec = nullptr;
 }
+
+// The mode of a call, resolved once from the object's three settings and handed to its Run: the family the forward GEMMs run on
+// (exact fp32, the f16x3 split, or one f16 MFMA per product, and with that one activations are f16 in memory), and whether the f16
+// scale 2^-e is read from the device table the weight rebuild writes (training) or passed by value.  Training's own storage setting
+// takes effect while the sampling side is plain fp32; under anything else a training call is refused (refuse_training).
+enum { FORM_F32 = 0, FORM_H3 = 1, FORM_H1 = 2 };
+struct Mode {
+  int form = FORM_F32;
+  bool table = false;
+  bool h() const { return form == FORM_H1; }   // activations are f16
+};
+Mode mode_of(fdsr_nafnet n, bool training) {
+  const bool plain = n->store == FDSR_NAF_STORE_F32 && n->prec == FDSR_PREC_F32;
+  if (training) return n->train_store == FDSR_NAF_STORE_F16 && plain ? Mode{FORM_H1, true} : Mode{};
+  return {n->store == FDSR_NAF_STORE_F16 ? FORM_H1 : n->prec == FDSR_PREC_F16X3 ? FORM_H3 : FORM_F32, false};
+}
+// some call reads the f16 forms of the weights (d_wq, d_hinv) and raises the range flag
+bool f16_forms(fdsr_nafnet n) { return mode_of(n, false).form != FORM_F32 || mode_of(n, true).form != FORM_F32; }
 
 int add_wt(fdsr_nafnet n, const std::string& key, std::vector<int64_t> shape) {
   WT w;
@@ -689,7 +704,7 @@ void build_schema(fdsr_nafnet n) {
   n->off_zero = take(off, zmax);
   for (GemmL& t : n->tgemms) t.boff = n->off_zero;
   n->arena_floats = off;
-  for (GemmL& g : n->gemms) { g.split = true; g.hoff = n->hfrags; n->hfrags += g.hfrags(); g.hidx = (int)(&g - n->gemms.data()); }
+  for (GemmL& g : n->gemms) { g.hoff = n->hfrags; n->hfrags += g.hfrags(); g.hidx = (int)(&g - n->gemms.data()); }
   size_t po = 0;
   for (const WT& wt : n->wts) { n->poff.push_back(po); po += numel(wt.shape); }
   n->P = po;
@@ -818,7 +833,7 @@ int finalize(fdsr_nafnet n) {
   if (!n->d_arena) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_arena), a.size() * sizeof(float)));
   HIPCHK(nullptr, hipDeviceSynchronize());   // nothing in flight reads the old forms
   HIPCHK(nullptr, hipMemcpy(n->d_arena, a.data(), a.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (n->prec == FDSR_PREC_F16X3 || n->store == FDSR_NAF_STORE_F16 || n->train_store == FDSR_NAF_STORE_F16) {
+  if (f16_forms(n)) {
     const std::vector<uint16_t> q = split_weights(n, a);
     if (!n->d_wq) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_wq), q.size() * sizeof(uint16_t)));
     HIPCHK(nullptr, hipMemcpy(n->d_wq, q.data(), q.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
@@ -881,60 +896,78 @@ Plan make_plan(fdsr_nafnet n, int N, int H, int W) {
   return p;
 }
 
+// A buffer of the walk and the type stored in it: fp32, or f16 elements in the first half of the slot.  sample_dst / train_dst say
+// which where they hand the slots out, and every launch helper picks its kernel instance from its operands' h.  A plain float* --
+// xin, eps, statistics, vectors, every gradient -- converts to an fp32 Act.  The activation slots of one NetDst are f16 exactly when
+// its Run's mode is FORM_H1: sample_run and train_run, the only makers of a Run that walks, hand both the same Mode::h().
+struct Act {
+  float* p;
+  bool h;
+  Act(float* ptr = nullptr, bool f16 = false) : p(ptr), h(f16) {}
+  operator float*() const { return p; }
+  _Float16* f16() const { return reinterpret_cast<_Float16*>(p); }
+};
+
 // Where the forward walk (Run::net / Run::block) puts every tensor.  Sampling fills the table with aliases of four shared buffers
 // (sample_dst), training with a slot per tensor its backward reads (train_dst in fdsr_nafnet_train.h).
 template <class T> struct Slots { T out, st1, t1, t2, sca, y, st2, p4, g4; };   // a block's; st1 / st2: LayerNorm statistics, p4: conv4's pair before the gate
-typedef Slots<float*> BlockDst;                              // p4 null: not kept
+typedef Slots<Act> BlockDst;                                 // p4 null: not kept
 
 struct NetDst {
   int N, H, W, Hp, Wp;
-  float *xin, *intro, *r1, *r, *ca, *enh, *eps, *part, *tg, *trow;   // r1, r: the RCAB's two convolutions
+  Act xin, intro, r1, r, enh, eps;   // r1, r: the RCAB's two convolutions
+  float *ca, *part, *tg, *trow;
   // per level i: downs[i]'s and ups[i]'s outputs; where encoder level i's skip and decoder step i's result are wanted -- a chain of
   // blocks that ends elsewhere (an empty list) is copied there; mid: the same for the middle blocks
-  float *down[FDSR_NAFNET_MAX_LEVELS], *up[FDSR_NAFNET_MAX_LEVELS], *skip[FDSR_NAFNET_MAX_LEVELS], *dec[FDSR_NAFNET_MAX_LEVELS], *mid;
+  Act down[FDSR_NAFNET_MAX_LEVELS], up[FDSR_NAFNET_MAX_LEVELS], skip[FDSR_NAFNET_MAX_LEVELS], dec[FDSR_NAFNET_MAX_LEVELS], mid;
   std::vector<BlockDst> blk;
 };
 
 // A block may write over its input (out == input); its input and out may be none of y, t1, t2 -- except that the input may be y.
-// downs[i] reads skip[i] and writes down[i]: the two are different buffers.
-NetDst sample_dst(fdsr_nafnet n, int N, int H, int W, void* workspace) {
+// downs[i] reads skip[i] and writes down[i]: the two are different buffers.  h: the activations are f16.
+NetDst sample_dst(fdsr_nafnet n, bool h, int N, int H, int W, void* workspace) {
   const Plan pl = make_plan(n, N, H, W);
   auto F = [&](size_t off) { return reinterpret_cast<float*>(static_cast<char*>(workspace) + off); };
-  float *A = F(pl.A), *B = F(pl.B), *T1 = F(pl.T1), *T2 = F(pl.T2), *st = F(pl.stats);
+  const Act A{F(pl.A), h}, B{F(pl.B), h}, T1{F(pl.T1), h}, T2{F(pl.T2), h}, st{F(pl.stats)};
   NetDst d{};
   d.N = pl.N; d.H = pl.H; d.W = pl.W; d.Hp = pl.Hp; d.Wp = pl.Wp;
   d.xin = F(pl.xin); d.intro = B; d.r1 = T2; d.r = T1; d.ca = F(pl.ca); d.enh = A; d.eps = F(pl.eps); d.part = F(pl.part);
   d.tg = F(pl.tg); d.trow = F(pl.trow);
-  d.blk.assign(n->blocks.size(), BlockDst{A, st, T1, T2, F(pl.sca), B, st, nullptr, T2});
+  d.blk.assign(n->blocks.size(), BlockDst{A, st, T1, T2, F(pl.sca), B, st, Act{}, T2});
   d.mid = A;
   for (int i = 0; i < n->L; ++i) {
-    d.down[i] = d.dec[i] = A; d.up[i] = B; d.skip[i] = F(pl.skip[i]);
+    d.down[i] = d.dec[i] = A; d.up[i] = B; d.skip[i] = Act{F(pl.skip[i]), h};
     if (!n->enc[i].empty()) d.blk[n->enc[i].back()].out = d.skip[i];
   }
   return d;
 }
 
 typedef void (*GemmFn)(GemmArgs);
-enum { FORM_F32 = 0, FORM_H3 = 1, FORM_H1 = 2 };
 template <int PRO, bool VEC> GemmFn gemm_fn(int form) {
   return form == FORM_H1 ? naf_gemm_h1_kernel<PRO, VEC> : form == FORM_H3 ? naf_gemm_h3_kernel<PRO, VEC> : naf_gemm_kernel<PRO, VEC>;
 }
-// an activation slot under FDSR_NAF_STORE_F16: the first half of the fp32 slot, as f16
-inline _Float16* H(float* p) { return reinterpret_cast<_Float16*>(p); }
-inline const _Float16* H(const float* p) { return reinterpret_cast<const _Float16*>(p); }
+
+// A GEMM's prologue (1x1 convolutions only: k is the input channel) and epilogue, as GemmArgs names their operands
+struct Pro { int kind = PRO_NONE; const float *pmul = nullptr, *padd = nullptr; int pstride = 0; const float* stats = nullptr; };
+struct Epi { int kind = EPI_BIAS; const float *res = nullptr, *evec = nullptr; float* out2 = nullptr; };
+inline Pro ln(const float* stats, const float* mul, const float* add, int stride) { return {PRO_LN, mul, add, stride, stats}; }
+inline Pro scaled(const float* vec, int stride) { return {PRO_MUL, vec, nullptr, stride}; }
+inline Epi residual(const float* res, const float* evec) { return {EPI_RES, res, evec}; }   // out = res + v evec[co]
+inline Epi gated(float* pair) { return {EPI_GATE, nullptr, nullptr, pair}; }                // pair: kept before the gate (training), or null
+inline Epi shuffled(const float* skip) { return {EPI_PSHUF, skip}; }                        // out = PixelShuffle(v) + skip
 
 struct Run {
   fdsr_nafnet n;
+  Mode m;     // mode_of(n, is this a training call); d's slots were handed out for it
   NetDst d;
   hipStream_t st;
   const float* rows;   // the blocks' time rows, image b at rows + b * rstride
   int rstride;
   const char* stop = nullptr;   // debug tap: stop after this tensor
   bool hit = false;
-  const float* tap_ptr = nullptr;
+  Act tap_at;
   int tap_h = 0, tap_w = 0, tap_c = 0;
   int err = FDSR_OK;
-  bool t16 = false;   // a training call under f16 training storage: the forward is the h1 walk, into half-size slots
 
   const float* P(size_t off) const { return n->d_arena + off; }
   static unsigned nb(size_t total) { return (unsigned)((total + 255) / 256); }
@@ -946,89 +979,95 @@ struct Run {
     hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
     check();
   }
-  bool h1() const { return t16 || n->store == FDSR_NAF_STORE_F16; }
-  void copy(float* dst, const float* src, size_t elems) {   // an activation: f16 elements under h1
-    (void)hipMemcpyAsync(dst, src, elems * (h1() ? sizeof(_Float16) : sizeof(float)), hipMemcpyDeviceToDevice, st);
+  // operands whose stored types do not fit the kernel a helper would pick: a mistake in this file, never a caller's -- made loud
+  bool misfit(bool bad) {
+    if (bad && err == FDSR_OK) err = fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet: internal error: an operand's stored type does not fit its kernel");
+    return bad;
+  }
+  void copy(Act dst, Act src, size_t elems) {   // between slots of one stored type
+    if (misfit(dst.h != src.h)) return;
+    (void)hipMemcpyAsync(dst, src, elems * (src.h ? sizeof(_Float16) : sizeof(float)), hipMemcpyDeviceToDevice, st);
     check();
   }
-  bool tap(const std::string& name, const float* ptr, int h, int w, int c) {
+  bool tap(const std::string& name, Act at, int h, int w, int c) {
     if (err != FDSR_OK) return true;
-    if (stop && name == stop) { hit = true; tap_ptr = ptr; tap_h = h; tap_w = w; tap_c = c; return true; }
+    if (stop && name == stop) { hit = true; tap_at = at; tap_h = h; tap_w = w; tap_c = c; return true; }
     return false;
   }
 
-  template <class... A> void gemm(int gi, A... a) { gemm_l(n->gemms[gi], a...); }
+  // A forward GEMM runs on the mode's family.
+  void gemm(int gi, Act x, Act out, int Hin, int Win, Pro pro = {}, Epi epi = {}) { gemm_l(n->gemms[gi], m.form, x, out, Hin, Win, pro, epi); }
 
-  void gemm_l(const GemmL& g, const float* x, float* out, int Hin, int Win, int epi, int pro = PRO_NONE, const float* pmul = nullptr,
-              const float* padd = nullptr, int pstride = 0, const float* stats = nullptr, const float* res = nullptr,
-              const float* evec = nullptr, float* out2 = nullptr, bool o32 = false) {
+  // The family fixes how the kernel reads: naf_gemm_h1_kernel takes x (but for intro's fp32 xin, the one input with cin % 8), res and
+  // out2 as f16, the other two take them as fp32; only out's type is an argument (o32, which H1 alone reads).  x is checked against
+  // that; res and out2 are slots of the same NetDst as x and out (see Act) and travel as plain pointers.
+  void gemm_l(const GemmL& g, int form, Act x, Act out, int Hin, int Win, Pro pro, Epi epi) {
+    if (misfit(g.cin % 8 == 0 && x.h != (form == FORM_H1))) return;
     GemmArgs a{};
-    a.x = x; a.w = P(g.woff); a.bias = P(g.boff); a.out = out; a.out2 = out2;
-    a.stats = stats; a.pmul = pmul; a.padd = padd; a.res = res; a.evec = evec;
+    a.x = x; a.w = P(g.woff); a.bias = P(g.boff); a.out = out; a.out2 = epi.out2;
+    a.stats = pro.stats; a.pmul = pro.pmul; a.padd = pro.padd; a.res = epi.res; a.evec = epi.evec;
     a.N = d.N; a.Hin = Hin; a.Win = Win; a.Cin = g.cin;
     a.Hout = (Hin + 2 * g.p - g.ks) / g.s + 1;
     a.Wout = (Win + 2 * g.p - g.ks) / g.s + 1;
     a.Cout = g.cout; a.KW = g.ks; a.S = g.s; a.P = g.p; a.K = g.K(); a.Kpad = g.Kpad(); a.CoutPad = g.CoutPad();
-    a.ostride = epi == EPI_GATE ? g.cout / 2 : epi == EPI_PSHUF ? g.cout / 4 : g.cout;
-    a.pstride = pstride; a.epi = epi;
+    a.ostride = epi.kind == EPI_GATE ? g.cout / 2 : epi.kind == EPI_PSHUF ? g.cout / 4 : g.cout;
+    a.pstride = pro.pstride; a.epi = epi.kind;
     const int M = d.N * a.Hout * a.Wout;
     const dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(a.CoutPad / BN));
-    // training under f16 storage: the forward GEMMs (and conv3 / conv5 formed again, o32) on the h1 kernel, the input-gradient
-    // GEMMs (no split form: fp32 gradients against the fp32 transposed packs) on the exact kernel
-    const int form = t16 ? (g.split ? FORM_H1 : FORM_F32) : h1() ? FORM_H1 : n->prec == FDSR_PREC_F16X3 ? FORM_H3 : FORM_F32;
     if (form != FORM_F32) {
-      if ((out2 && !t16) || !g.split) {
-        if (err == FDSR_OK) err = fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet: this GEMM has no f16 form");
-        return;
-      }
       a.wq = n->d_wq + g.hoff; a.winv = g.hinv; a.sat = n->d_sat;
-      a.o32 = out == d.eps || o32;
-      if (t16) a.winvp = n->d_hinv + g.hidx;
+      a.o32 = form == FORM_H1 && !out.h;
+      if (m.table) a.winvp = n->d_hinv + g.hidx;
     }
-    const GemmFn k = g.cin % 8 ? gemm_fn<PRO_NONE, false>(form) : pro == PRO_LN ? gemm_fn<PRO_LN, true>(form)
-                     : pro == PRO_MUL ? gemm_fn<PRO_MUL, true>(form) : gemm_fn<PRO_NONE, true>(form);
+    const GemmFn k = g.cin % 8 ? gemm_fn<PRO_NONE, false>(form) : pro.kind == PRO_LN ? gemm_fn<PRO_LN, true>(form)
+                     : pro.kind == PRO_MUL ? gemm_fn<PRO_MUL, true>(form) : gemm_fn<PRO_NONE, true>(form);
     launch(k, grid, dim3(NT), 0, a);
   }
 
-  void ln_stats(const float* x, float* stats, int M, int C) {
-    if (h1()) launch(naf_ln_stats_h_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, H(x), stats, M, C);
+  void ln_stats(Act x, float* stats, int M, int C) {
+    if (x.h) launch(naf_ln_stats_h_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, x.f16(), stats, M, C);
     else launch(naf_ln_stats_kernel, dim3((unsigned)((M + 15) / 16)), dim3(256), 0, x, stats, M, C);
   }
-  void dw_gate(const BlockL& b, const float* x, float* y, int h, int w, int ns) {
+  void dw_gate(const BlockL& b, Act x, Act y, int h, int w, int ns) {
     const int c = b.c;
-    if (h1()) {
+    if (x.h) {
       int lp_shift = 3;   // 2^lp_shift lanes, two channels each, cover a pixel: 8 (c = 16) .. 64
       while (lp_shift < 6 && (2 << lp_shift) < c) ++lp_shift;
-      launch(naf_dw_gate_h_kernel, dim3((unsigned)ns, (unsigned)((c + (2 << lp_shift) - 1) / (2 << lp_shift)), (unsigned)d.N), dim3(256), 0, H(x),
-             P(b.off_dww), P(b.off_dwb), H(y), d.part, h, w, c, ns, lp_shift, n->d_sat);
+      launch(naf_dw_gate_h_kernel, dim3((unsigned)ns, (unsigned)((c + (2 << lp_shift) - 1) / (2 << lp_shift)), (unsigned)d.N), dim3(256), 0, x.f16(),
+             P(b.off_dww), P(b.off_dwb), y.f16(), d.part, h, w, c, ns, lp_shift, n->d_sat);
     } else launch(naf_dw_gate_kernel, dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)d.N), dim3(256), 0, x, P(b.off_dww), P(b.off_dwb), y,
                 d.part, h, w, c, ns);
   }
+  void chansum(Act r, int HW, int ns) {   // the RCAB's pool: per-strip sums of r [N][HW][wd] into d.part
+    const int wd = n->wd;
+    if (r.h) launch(naf_chansum_h_kernel, dim3((unsigned)ns, (unsigned)((wd + 127) / 128), (unsigned)d.N), dim3(256), 0, r.f16(), d.part, HW, wd, ns);
+    else launch(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)d.N), dim3(256), 0, r, d.part, HW, wd, ns);
+  }
 
-  void block(int bi, const float* cur, int h, int w) {
+  void block(int bi, Act cur, int h, int w) {
     const BlockL& b = n->blocks[bi];
     const BlockDst& s = d.blk[bi];
     const int c = b.c, HW = h * w, M = d.N * HW, ns = nstrips_of(HW);
     const float* rw = rows + b.row_off;
     ln_stats(cur, s.st1, M, c);
-    gemm(b.conv1, cur, s.t1, h, w, EPI_BIAS, PRO_LN, rw + c, rw, rstride, s.st1);
+    gemm(b.conv1, cur, s.t1, h, w, ln(s.st1, rw + c, rw, rstride));
     dw_gate(b, s.t1, s.t2, h, w, ns);
     launch(naf_sca_kernel, dim3((unsigned)((c + 15) / 16), (unsigned)d.N), dim3(256), (c + 256) * sizeof(float), d.part, ns, HW, P(b.off_scaw),
            P(b.off_scab), s.sca, c);
-    gemm(b.conv3, s.t2, s.y, h, w, EPI_RES, PRO_MUL, s.sca, nullptr, c, nullptr, cur, P(b.off_beta));
+    gemm(b.conv3, s.t2, s.y, h, w, scaled(s.sca, c), residual(cur, P(b.off_beta)));
     ln_stats(s.y, s.st2, M, c);
-    gemm(b.conv4, s.y, s.g4, h, w, EPI_GATE, PRO_LN, rw + 3 * c, rw + 2 * c, rstride, s.st2, nullptr, nullptr, s.p4);
-    gemm(b.conv5, s.g4, s.out, h, w, EPI_RES, PRO_NONE, nullptr, nullptr, 0, nullptr, s.y, P(b.off_gamma));
+    gemm(b.conv4, s.y, s.g4, h, w, ln(s.st2, rw + 3 * c, rw + 2 * c, rstride), gated(s.p4));
+    gemm(b.conv5, s.g4, s.out, h, w, {}, residual(s.y, P(b.off_gamma)));
   }
 
   // the blocks of `list` from cur on; the result is wanted at `want` and copied there if the chain ended elsewhere.  False: stop (a tap, an error)
-  bool chain(const std::vector<int>& list, const float* cur, float* want, int h, int w, int c) {
+  bool chain(const std::vector<int>& list, Act cur, Act want, int h, int w, int c) {
     for (int bi : list) {
       block(bi, cur, h, w);
       cur = d.blk[bi].out;
       if (tap(n->blocks[bi].name, cur, h, w, c)) return false;
     }
-    if (cur != want) copy(want, cur, (size_t)d.N * h * w * c);
+    if (cur.p != want.p) copy(want, cur, (size_t)d.N * h * w * c);
     return true;
   }
 
@@ -1036,33 +1075,32 @@ struct Run {
   void net() {
     const int wd = n->wd, L = n->L;
     int h = d.Hp, w = d.Wp, c = wd;
-    gemm(n->g_intro, d.xin, d.intro, h, w, EPI_BIAS);
+    gemm(n->g_intro, d.xin, d.intro, h, w);
     if (tap("intro", d.intro, h, w, wd)) return;
-    gemm(n->g_rcab0, d.intro, d.r1, h, w, EPI_RELU);
-    gemm(n->g_rcab2, d.r1, d.r, h, w, EPI_BIAS);
+    gemm(n->g_rcab0, d.intro, d.r1, h, w, {}, {EPI_RELU});
+    gemm(n->g_rcab2, d.r1, d.r, h, w);
     const int HW = h * w, ns = nstrips_of(HW);
-    if (h1()) launch(naf_chansum_h_kernel, dim3((unsigned)ns, (unsigned)((wd + 127) / 128), (unsigned)d.N), dim3(256), 0, H(d.r), d.part, HW, wd, ns);
-    else launch(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)d.N), dim3(256), 0, d.r, d.part, HW, wd, ns);
+    chansum(d.r, HW, ns);
     launch(naf_ca_kernel, dim3((unsigned)d.N), dim3(256), (wd + 256 + wd / 16) * sizeof(float), d.part, ns, HW, P(n->off_ca1w), P(n->off_ca1b),
            P(n->off_ca2w), P(n->off_ca2b), d.ca, wd, wd / 16);
     const size_t total = (size_t)d.N * HW * wd;
-    if (h1()) launch(naf_enhance_h_kernel, dim3(nb(total / 8)), dim3(256), 0, H(d.intro), H(d.r), d.ca, H(d.enh), HW, wd, total / 8, n->d_sat);
+    if (d.intro.h) launch(naf_enhance_h_kernel, dim3(nb(total / 8)), dim3(256), 0, d.intro.f16(), d.r.f16(), d.ca, d.enh.f16(), HW, wd, total / 8, n->d_sat);
     else launch(naf_enhance_kernel, dim3(nb(total)), dim3(256), 0, d.intro, d.r, d.ca, d.enh, HW, wd, total);
     if (tap("enhance", d.enh, h, w, wd)) return;
     for (int i = 0; i < L; ++i) {
       if (!chain(n->enc[i], i ? d.down[i - 1] : d.enh, d.skip[i], h, w, c)) return;
-      gemm(n->downs[i], d.skip[i], d.down[i], h, w, EPI_BIAS);
+      gemm(n->downs[i], d.skip[i], d.down[i], h, w);
       h /= 2; w /= 2; c *= 2;
       if (tap("downs." + std::to_string(i), d.down[i], h, w, c)) return;
     }
     if (!chain(n->mid, d.down[L - 1], d.mid, h, w, c)) return;
     for (int i = 0; i < L; ++i) {
-      gemm(n->ups[i], i ? d.dec[i - 1] : d.mid, d.up[i], h, w, EPI_PSHUF, PRO_NONE, nullptr, nullptr, 0, nullptr, d.skip[L - 1 - i]);
+      gemm(n->ups[i], i ? d.dec[i - 1] : d.mid, d.up[i], h, w, {}, shuffled(d.skip[L - 1 - i]));
       h *= 2; w *= 2; c /= 2;
       if (tap("ups." + std::to_string(i), d.up[i], h, w, c)) return;
       if (!chain(n->dec[i], d.up[i], d.dec[i], h, w, c)) return;
     }
-    gemm(n->g_ending, d.dec[L - 1], d.eps, h, w, EPI_BIAS);
+    gemm(n->g_ending, d.dec[L - 1], d.eps, h, w);
     tap("ending", d.eps, h, w, n->cfg.img_channel);
   }
 
@@ -1078,6 +1116,14 @@ struct Run {
            P(n->off_t2w), P(n->off_t2b), tg, wd);
     launch(naf_rows_kernel, dim3((unsigned)((n->R + 255) / 256), (unsigned)count), dim3(256), 0, tg, P(n->off_rowsw), P(n->off_rowsb),
            P(n->off_rowsadd), P(n->off_rowsmul), dst, 2 * wd, n->R);
+  }
+
+  // one forward at per-image times (device): their rows, xin, the walk
+  void forward(const float* x, const float* cond, const float* time_dev) {
+    time_rows(time_dev, d.N, d.tg, d.trow);
+    rows = d.trow;
+    prep(x, cond);
+    net();
   }
 
   void tail(int mode, float* x, const float* cond, const float* noise, float* traj, unsigned long long seed, long long first) {
@@ -1121,7 +1167,7 @@ int ensure_table(fdsr_nafnet n, hipStream_t st) {
   if (!n->d_ctl) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&n->d_ctl), 256));
   HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&times), cnt * sizeof(float)));
   HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&tg), (size_t)cnt * 2 * n->wd * sizeof(float)));
-  Run r{n, NetDst{}, st, nullptr, 0};
+  Run r{n, Mode{}, NetDst{}, st, nullptr, 0};   // the time kernels only
   r.launch(naf_iota_kernel, dim3(Run::nb(cnt)), dim3(256), 0, times, cnt);
   r.time_rows(times, cnt, tg, n->d_rowtable);
   const hipError_t e = hipStreamSynchronize(st);   // once per (weights, schedule): the scratch is freed below
@@ -1130,6 +1176,36 @@ int ensure_table(fdsr_nafnet n, hipStream_t st) {
   if (r.err) return r.err;
   HIPCHK(nullptr, e);
   n->table_valid = true;
+  return FDSR_OK;
+}
+
+// the Run of a checked sampling-side call, over sampling's shared buffers
+Run sample_run(fdsr_nafnet n, int batch, int height, int width, void* workspace, hipStream_t st, const float* rows, int rstride) {
+  const Mode m = mode_of(n, false);
+  return Run{n, m, sample_dst(n, m.h(), batch, height, width, workspace), st, rows, rstride};
+}
+
+// What the three mode setters do once the argument is good.  The device forms are rebuilt from the fp32 master through pack_forms by
+// the next call that runs (finalize: the split planes, the table of scales); after optimizer steps the master is on the device.
+int switch_mode(fdsr_nafnet n, int* setting, int mode, const char* killer) {
+  if (mode == *setting) return FDSR_OK;
+  const int rc = host_from_master(n);
+  if (rc) return rc;
+  *setting = mode; n->dirty = true;
+  kill_ticket(n, killer);
+  drop_graph(n);
+  return FDSR_OK;
+}
+
+// Training calls run while the sampling side is plain fp32 (the device-side re-pack writes the fp32 forms and, under f16 training
+// storage, the planes of that mode only).  hint: name the setter that leads back, as the calls that run the network do.
+int refuse_training(fdsr_nafnet n, const char* fn, bool hint) {
+  const int form = mode_of(n, false).form;
+  if (form == FORM_H1)
+    return fail(nullptr, FDSR_E_INVALID, "%s: training runs on fp32 activations only, the object is in FDSR_NAF_STORE_F16, f16 storage%s", fn,
+                hint ? " (fdsr_nafnet_set_storage)" : "");
+  if (form == FORM_H3)
+    return fail(nullptr, FDSR_E_INVALID, "%s: training runs in FDSR_PREC_F32 only, the object is in f16x3%s", fn, hint ? " (fdsr_nafnet_set_precision)" : "");
   return FDSR_OK;
 }
 
@@ -1211,16 +1287,7 @@ int fdsr_nafnet_set_precision(fdsr_nafnet n, int mode) {
   if (mode == FDSR_PREC_F16X3 && n->store == FDSR_NAF_STORE_F16)
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_set_precision: FDSR_PREC_F16X3 while the storage is FDSR_NAF_STORE_F16: set the storage back "
                                          "first (fdsr_nafnet_set_storage)");
-  if (mode == n->prec) return FDSR_OK;
-  // the device forms are rebuilt from the fp32 master through pack_forms by the next call that runs (finalize); after optimizer
-  // steps the master is on the device
-  const int rc = host_from_master(n);
-  if (rc) return rc;
-  n->prec = mode;
-  n->dirty = true;
-  kill_ticket(n, "fdsr_nafnet_set_precision (a precision switch)");
-  drop_graph(n);
-  return FDSR_OK;
+  return switch_mode(n, &n->prec, mode, "fdsr_nafnet_set_precision (a precision switch)");
 }
 
 int fdsr_nafnet_set_storage(fdsr_nafnet n, int mode) {
@@ -1229,44 +1296,30 @@ int fdsr_nafnet_set_storage(fdsr_nafnet n, int mode) {
   if (mode == FDSR_NAF_STORE_F16 && n->prec == FDSR_PREC_F16X3)
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_set_storage: FDSR_NAF_STORE_F16 while the precision is FDSR_PREC_F16X3: set the precision "
                                          "back first (fdsr_nafnet_set_precision)");
-  if (mode == n->store) return FDSR_OK;
-  const int rc = host_from_master(n);   // as a precision switch: the forms (here: the hi planes) are rebuilt by the next call that runs
-  if (rc) return rc;
-  n->store = mode;
-  n->dirty = true;
-  kill_ticket(n, "fdsr_nafnet_set_storage (a storage switch)");
-  drop_graph(n);
-  return FDSR_OK;
+  return switch_mode(n, &n->store, mode, "fdsr_nafnet_set_storage (a storage switch)");
 }
 
 int fdsr_nafnet_set_train_storage(fdsr_nafnet n, int mode) {
   if (!n || (mode != FDSR_NAF_STORE_F32 && mode != FDSR_NAF_STORE_F16))
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_set_train_storage: mode must be FDSR_NAF_STORE_F32 (0) or FDSR_NAF_STORE_F16 (1), not %d", mode);
-  if (mode == n->train_store) return FDSR_OK;
-  const int rc = host_from_master(n);   // as a storage switch: finalize builds the hi planes and the table of scales the f16 forward reads
-  if (rc) return rc;
-  n->train_store = mode;
-  n->dirty = true;
-  kill_ticket(n, "fdsr_nafnet_set_train_storage (a storage switch)");
-  drop_graph(n);
-  return FDSR_OK;
+  return switch_mode(n, &n->train_store, mode, "fdsr_nafnet_set_train_storage (a storage switch)");
 }
 
 int fdsr_nafnet_check_saturation(fdsr_nafnet n, void* hip_stream) {
   if (!n) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_check_saturation: null object");
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   HIPCHK(nullptr, hipStreamSynchronize(st));
-  if ((n->prec != FDSR_PREC_F16X3 && n->store != FDSR_NAF_STORE_F16 && !n->train16()) || !n->d_sat) return FDSR_OK;
+  if (!f16_forms(n) || !n->d_sat) return FDSR_OK;
   if (!n->h_sat) HIPCHK(nullptr, hipHostMalloc(reinterpret_cast<void**>(&n->h_sat), 64, hipHostMallocDefault));
   *n->h_sat = 0;
   HIPCHK(nullptr, hipMemcpyAsync(n->h_sat, n->d_sat, sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(nullptr, hipStreamSynchronize(st));
   if (!*n->h_sat) return FDSR_OK;
   HIPCHK(nullptr, hipMemsetAsync(n->d_sat, 0, sizeof(int), st));
-  if (n->store == FDSR_NAF_STORE_F16)
+  if (mode_of(n, false).h())
     return fail(nullptr, FDSR_E_SATURATED, "f16 storage: an activation of the NAFNet exceeded the f16 range (+-65504) and was clamped; "
                                            "re-run this call after fdsr_nafnet_set_storage(FDSR_NAF_STORE_F32)");
-  if (n->train16())
+  if (mode_of(n, true).h())
     return fail(nullptr, FDSR_E_SATURATED, "f16 training storage: an activation of the NAFNet exceeded the f16 range (+-65504) and was clamped; "
                                            "the gradients of this call are not to be used: skip the step, or train after "
                                            "fdsr_nafnet_set_train_storage(FDSR_NAF_STORE_F32)");
@@ -1308,11 +1361,8 @@ int fdsr_nafnet_forward(fdsr_nafnet n, const float* x_nchw, const float* cond_nc
   if (!x_nchw || !cond_nchw || !time_dev || !out_nchw) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_forward: null tensor");
   const int rc = check_args(n, "fdsr_nafnet_forward", batch, height, width, workspace, workspace_bytes, plan_bytes);
   if (rc) return rc;
-  Run r{n, sample_dst(n, batch, height, width, workspace), reinterpret_cast<hipStream_t>(hip_stream), nullptr, n->R};
-  r.time_rows(time_dev, batch, r.d.tg, r.d.trow);
-  r.rows = r.d.trow;
-  r.prep(x_nchw, cond_nchw);
-  r.net();
+  Run r = sample_run(n, batch, height, width, workspace, reinterpret_cast<hipStream_t>(hip_stream), nullptr, n->R);
+  r.forward(x_nchw, cond_nchw, time_dev);
   r.tail(0, out_nchw, nullptr, nullptr, nullptr, 0, 0);
   return r.err;
 }
@@ -1323,22 +1373,19 @@ int fdsr_nafnet_debug_tensor(fdsr_nafnet n, const char* name, const float* x_nch
   if (!name || !x_nchw || !cond_nchw || !time_dev || !out_nhwc || !dims3) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_debug_tensor: null argument");
   const int rc = check_args(n, "fdsr_nafnet_debug_tensor", batch, height, width, workspace, workspace_bytes, plan_bytes);
   if (rc) return rc;
-  Run r{n, sample_dst(n, batch, height, width, workspace), reinterpret_cast<hipStream_t>(hip_stream), nullptr, n->R};
+  Run r = sample_run(n, batch, height, width, workspace, reinterpret_cast<hipStream_t>(hip_stream), nullptr, n->R);
   r.stop = name;
-  r.time_rows(time_dev, batch, r.d.tg, r.d.trow);
-  r.rows = r.d.trow;
-  r.prep(x_nchw, cond_nchw);
-  r.net();
+  r.forward(x_nchw, cond_nchw, time_dev);
   if (r.err) return r.err;
   if (!r.hit) return fail(nullptr, FDSR_E_KEY, "fdsr_nafnet_debug_tensor: unknown tap '%s'", name);
   const size_t count = (size_t)batch * r.tap_h * r.tap_w * r.tap_c;
   if (count > capacity_floats) return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_debug_tensor: '%s' needs %zu floats", name, count);
   dims3[0] = r.tap_h; dims3[1] = r.tap_w; dims3[2] = r.tap_c;
-  if (r.h1() && r.tap_ptr != r.d.eps) {   // the stored f16 values, widened
-    r.launch(naf_widen_h_kernel, dim3(Run::nb(count)), dim3(256), 0, H(r.tap_ptr), out_nhwc, count);
+  if (r.tap_at.h) {   // the stored f16 values, widened
+    r.launch(naf_widen_h_kernel, dim3(Run::nb(count)), dim3(256), 0, r.tap_at.f16(), out_nhwc, count);
     return r.err;
   }
-  HIPCHK(nullptr, hipMemcpyAsync(out_nhwc, r.tap_ptr, count * sizeof(float), hipMemcpyDeviceToDevice, r.st));
+  HIPCHK(nullptr, hipMemcpyAsync(out_nhwc, r.tap_at, count * sizeof(float), hipMemcpyDeviceToDevice, r.st));
   return FDSR_OK;
 }
 
@@ -1357,7 +1404,7 @@ int fdsr_nafnet_sample(fdsr_nafnet n, const float* state_nchw, const float* cond
   const int mode = (flags & FDSR_NAFNET_ODE) ? 2 : 1;
   HIPCHK(nullptr, hipMemcpyAsync(out_nchw, state_nchw, (size_t)batch * 3 * height * width * sizeof(float), hipMemcpyDeviceToDevice, st));
   HIPCHK(nullptr, hipMemsetAsync(n->d_ctl, 0, sizeof(int), st));
-  Run r{n, sample_dst(n, batch, height, width, workspace), st, n->d_cur_row, 0};
+  Run r = sample_run(n, batch, height, width, workspace, st, n->d_cur_row, 0);
   auto step = [&]() -> int {
     r.launch(naf_row_copy_kernel, dim3(Run::nb(n->R)), dim3(256), 0, n->d_rowtable, n->d_cur_row, n->d_ctl, n->T, n->R);
     r.prep(out_nchw, cond_nchw);

@@ -743,7 +743,7 @@ TrainPlan make_train_plan(fdsr_nafnet n, int N, int H, int W) {
   size_t off = 0;
   auto buf = [&](size_t floats) { const size_t o = off; off = align_up(off + floats * sizeof(float), 256); return o; };
   // a saved activation: f16 elements under f16 training storage, in a slot of half the bytes
-  const size_t esz = n->train16() ? sizeof(_Float16) : sizeof(float);
+  const size_t esz = mode_of(n, true).h() ? sizeof(_Float16) : sizeof(float);
   auto abuf = [&](size_t elems) { const size_t o = off; off = align_up(off + elems * esz, 256); return o; };
   p.xin = buf(M0 * 6);
   p.x0 = abuf(M0 * w); p.r1 = abuf(M0 * w); p.r = abuf(M0 * w); p.enh = abuf(M0 * w);
@@ -822,7 +822,7 @@ int ensure_train(fdsr_nafnet n) {
 
 // after a re-pack under f16 training storage: the f16 forms and their scales follow the arena, stream-ordered, no host round trip
 int rebuild_wq(fdsr_nafnet n, hipStream_t st) {
-  if (!n->train16()) return FDSR_OK;
+  if (!mode_of(n, true).h()) return FDSR_OK;
   const WqDesc* desc = static_cast<const WqDesc*>(n->d_hdesc);
   int* hexp = reinterpret_cast<int*>(static_cast<char*>(n->d_hdesc) + n->gemms.size() * sizeof(WqDesc));
   const unsigned total = (unsigned)(n->hfrags / 2);
@@ -836,26 +836,47 @@ int rebuild_wq(fdsr_nafnet n, hipStream_t st) {
   return FDSR_OK;
 }
 
+// The master changed on the device (an optimizer step, fdsr_nafnet_set_weights_flat): every device form follows it, stream-ordered;
+// the host copies and the row table are behind, and a captured graph holds nothing to keep.
+int master_moved(fdsr_nafnet n, hipStream_t st) {
+  hipLaunchKernelGGL(naf_repack_kernel, dim3(Run::nb(n->arena_floats)), dim3(256), 0, st, n->d_arena, n->d_master, n->d_map, n->arena_floats);
+  HIPCHK(nullptr, hipGetLastError());
+  const int rc = rebuild_wq(n, st);
+  if (rc) return rc;
+  n->host_stale = true; n->table_valid = false;
+  drop_graph(n);
+  return FDSR_OK;
+}
+
 size_t train_plan_bytes(fdsr_nafnet n, int N, int H, int W) { return make_train_plan(n, N, H, W).bytes; }
 
-// the forward walk's table for training: every tensor in its own slot, and every chain of blocks wanted where it ends (no copies)
-NetDst train_dst(fdsr_nafnet n, const TrainPlan& tp, char* ws) {
+// the forward walk's table for training: every tensor in its own slot, and every chain of blocks wanted where it ends (no copies).
+// The saved activations (make_train_plan's abuf slots) are f16 under h.
+NetDst train_dst(fdsr_nafnet n, const TrainPlan& tp, char* ws, bool h) {
   auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+  auto A = [&](size_t off) { return Act{F(off), h}; };
   NetDst d{};
   d.N = tp.N; d.H = tp.H; d.W = tp.W; d.Hp = tp.Hp; d.Wp = tp.Wp;
-  d.xin = F(tp.xin); d.intro = F(tp.x0); d.r1 = F(tp.r1); d.r = F(tp.r); d.ca = F(tp.ca); d.enh = F(tp.enh); d.eps = F(tp.eps);
+  d.xin = F(tp.xin); d.intro = A(tp.x0); d.r1 = A(tp.r1); d.r = A(tp.r); d.ca = F(tp.ca); d.enh = A(tp.enh); d.eps = F(tp.eps);
   d.part = F(tp.part); d.tg = F(tp.tg); d.trow = F(tp.trow);
   for (const BlockSlots& s : tp.blk)
-    d.blk.push_back({F(s.out), F(s.st1), F(s.t1), F(s.t2), F(s.sca), F(s.y), F(s.st2), F(s.p4), F(s.g4)});
-  auto end = [&](const std::vector<int>& list, float* first) { return list.empty() ? first : d.blk[list.back()].out; };
+    d.blk.push_back({A(s.out), F(s.st1), A(s.t1), A(s.t2), F(s.sca), A(s.y), F(s.st2), A(s.p4), A(s.g4)});
+  auto end = [&](const std::vector<int>& list, Act first) { return list.empty() ? first : d.blk[list.back()].out; };
   for (int i = 0; i < n->L; ++i) {
-    d.down[i] = F(tp.down[i]);
-    d.up[i] = F(tp.up[i]);
+    d.down[i] = A(tp.down[i]);
+    d.up[i] = A(tp.up[i]);
     d.skip[i] = end(n->enc[i], i ? d.down[i - 1] : d.enh);
     d.dec[i] = end(n->dec[i], d.up[i]);
   }
   d.mid = end(n->mid, d.down[n->L - 1]);
   return d;
+}
+
+typedef void (*WgradFn)(WgArgs);
+template <int XS> WgradFn wgrad_fn(int pro) {   // XS: the stored type of x; dy is fp32
+  return pro == PRO_LN    ? naf_wgrad_kernel<PRO_LN, XS, ACT_F32>
+         : pro == PRO_MUL ? naf_wgrad_kernel<PRO_MUL, XS, ACT_F32>
+                          : naf_wgrad_kernel<PRO_NONE, XS, ACT_F32>;
 }
 
 // Run's forward walk over train_dst, then the backward over what it left there
@@ -867,74 +888,64 @@ struct TrainRun : Run {
   float* G(int wi) const { return n->d_grad + n->poff[wi]; }
 
   // the input of block j of a list whose first block reads `first`
-  const float* chain_in(const std::vector<int>& list, size_t j, const float* first) const { return j == 0 ? first : d.blk[list[j - 1]].out; }
-  const float* enc_in(int i) const { return i ? d.down[i - 1] : d.enh; }
+  Act chain_in(const std::vector<int>& list, size_t j, Act first) const { return j == 0 ? first : d.blk[list[j - 1]].out; }
 
   // ---- backward launchers ----
-  // A saved activation is f16 under f16 training storage (t16): SEL picks the kernel instance for the stored type of the operands
-  // that are saved activations.  Gradients are fp32 always: their copies too.
-#define NAF_SEL1(K, h) ((h) ? K<ACT_F16> : K<ACT_F32>)
-  void gcopy(float* dst, const float* src, size_t floats) {
-    (void)hipMemcpyAsync(dst, src, floats * sizeof(float), hipMemcpyDeviceToDevice, st);
-    check();
-  }
-  // conv3's / conv5's output (before beta / gamma and the residual) formed again in fp32 for d beta / d gamma: the forward's own
-  // kernel and operands, so under t16 the very value the forward scaled
-  void reform(int gi, const float* x, float* out, int h, int w, int pro = PRO_NONE, const float* pmul = nullptr, int pstride = 0) {
-    gemm(gi, x, out, h, w, EPI_BIAS, pro, pmul, nullptr, pstride, nullptr, nullptr, nullptr, nullptr, true);
+  // A saved activation is f16 under f16 training storage: SEL picks the kernel instance for the stored type of the operand that is
+  // one.  Gradients are fp32 always (plain float*: Run::copy moves them as such).
+#define NAF_SEL1(K, act) ((act).h ? K<ACT_F16> : K<ACT_F32>)
+  // An input gradient: gemms[gi]'s transposed pack as a convolution of its own.  Gradients are fp32 and the transposed packs have no
+  // f16 form, so this is the exact kernel in every mode.
+  void tgemm(int gi, float* g, float* out, int h, int w, Pro pro = {}, Epi epi = {}) { gemm_l(n->tgemms[gi], FORM_F32, g, out, h, w, pro, epi); }
+
+  // weight (and bias) gradient of gemm gi: x its forward input (Hin x Win) under the forward's prologue, dy [M][cout]
+  void wgrad(int gi, Act x, float* dy, int Hin, int Win, Pro pro = {}, const float* colmul = nullptr) {
+    const GemmL& g = n->gemms[gi];
+    wgrad_l(g, x, dy, Hin, Win, pro, colmul, 0, G(g.w), g.b >= 0 ? G(g.b) : nullptr);
   }
 
-  // weight (and bias) gradient of gemm gi: x its forward input (Hin x Win), dy [M][cout]
-  void wgrad(int gi, const float* x, const float* dy, int Hin, int Win, int pro = PRO_NONE, const float* stats = nullptr, const float* pmul = nullptr,
-             const float* padd = nullptr, int pstride = 0, const float* colmul = nullptr) {
-    const GemmL& g = n->gemms[gi];
+  // g: the convolution in the kernel's terms; x, dy: its two operands, either of which may be a saved activation (dy: ups only, whose
+  // g is the transposed convolution, operands exchanged, mode 1); gw, gb: where the finished sums go
+  void wgrad_l(const GemmL& g, Act x, Act dy, int Hin, int Win, Pro pro, const float* colmul, int mode, float* gw, float* gb) {
     WgArgs a{};
-    a.x = x; a.dy = dy; a.stats = stats; a.pmul = pmul; a.padd = padd; a.colmul = colmul; a.part = F(tp.wgpart);
+    a.x = x; a.dy = dy; a.stats = pro.stats; a.pmul = pro.pmul; a.padd = pro.padd; a.colmul = colmul; a.part = F(tp.wgpart);
     a.N = tp.N; a.Hin = Hin; a.Win = Win; a.Cin = g.cin;
     a.Hout = (Hin + 2 * g.p - g.ks) / g.s + 1;
     a.Wout = (Win + 2 * g.p - g.ks) / g.s + 1;
-    a.Cout = g.cout; a.KW = g.ks; a.S = g.s; a.P = g.p; a.K = g.K(); a.Keff = g.b >= 0 ? a.K + 1 : a.K; a.ldy = g.cout; a.pstride = pstride;
-    wgrad_launch(a, pro, 0, g.ks * g.ks, G(g.w), g.b >= 0 ? G(g.b) : nullptr, t16 && x != d.xin, false);
-  }
-
-  // xh / dh: x / dy is a saved f16 activation
-  void wgrad_launch(const WgArgs& a, int pro, int mode, int taps, float* gw, float* gb, bool xh, bool dh) {
+    a.Cout = g.cout; a.KW = g.ks; a.S = g.s; a.P = g.p; a.K = g.K(); a.Keff = gb ? a.K + 1 : a.K; a.ldy = g.cout; a.pstride = pro.pstride;
     const int M = a.N * a.Hout * a.Wout, nz = (M + WG_CHUNK - 1) / WG_CHUNK;
     const dim3 grid((unsigned)((a.Keff + 63) / 64), (unsigned)((a.Cout + 63) / 64), (unsigned)nz);
     if ((size_t)nz * grid.x * 64 * grid.y * 64 > tp.wg_floats) {
       if (err == FDSR_OK) err = fail(nullptr, FDSR_E_WORKSPACE, "fdsr_nafnet: weight-gradient scratch too small");
       return;
     }
-    void (*k)(WgArgs) = pro == PRO_LN ? naf_wgrad_kernel<PRO_LN, ACT_F32, ACT_F32> : pro == PRO_MUL ? naf_wgrad_kernel<PRO_MUL, ACT_F32, ACT_F32>
-                                                                                                     : naf_wgrad_kernel<PRO_NONE, ACT_F32, ACT_F32>;
-    if (xh) k = pro == PRO_LN ? naf_wgrad_kernel<PRO_LN, ACT_F16, ACT_F32> : pro == PRO_MUL ? naf_wgrad_kernel<PRO_MUL, ACT_F16, ACT_F32>
-                                                                                             : naf_wgrad_kernel<PRO_NONE, ACT_F16, ACT_F32>;
-    if (dh) k = naf_wgrad_kernel<PRO_NONE, ACT_F32, ACT_F16>;   // ups: the gathered gradient is A, the saved input is "dy"
+    // dy.h is ups' (no prologue): the gathered gradient is A, the saved input is "dy"
+    WgradFn k = x.h ? wgrad_fn<ACT_F16>(pro.kind) : wgrad_fn<ACT_F32>(pro.kind);
+    if (dy.h) k = naf_wgrad_kernel<PRO_NONE, ACT_F32, ACT_F16>;
     launch(k, grid, dim3(256), 0, a);
     launch(naf_wgrad_finish_kernel, dim3(nb((size_t)a.Keff * a.Cout)), dim3(256), 0, a.part, nz, (int)grid.x * 64, (int)grid.y * 64, a.Keff, a.K,
-           a.Cout, a.Cin, taps, mode, gw, gb);
+           a.Cout, a.Cin, g.ks * g.ks, mode, gw, gb);
   }
 
-  // per-channel sums over pixels: dst[g][ch], groups = N (per image, rows dstride apart) or 1 (everything)
-  // ah / bh: a / b is a saved activation (never both)
-  void dot(const float* a, const float* b, const float* stats, int mode, int HW, int c, float* dst, bool per_image, int dstride, float scale = 1.f,
-           bool ah = false, bool bh = false) {
+  // per-channel sums over pixels: dst[g][ch], groups = N (per image, rows dstride apart) or 1 (everything); a or b may be a saved activation
+  void dot(Act a, Act b, const float* stats, int mode, int HW, int c, float* dst, bool per_image, int dstride, float scale = 1.f) {
     const int ns = nstrips_of(HW);
-    launch(t16 && ah ? naf_dot_kernel<ACT_F16, ACT_F32> : t16 && bh ? naf_dot_kernel<ACT_F32, ACT_F16> : naf_dot_kernel<ACT_F32, ACT_F32>, dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)tp.N), dim3(256), 0, a, b, stats, d.part, HW, c, ns, mode);
+    launch(a.h ? naf_dot_kernel<ACT_F16, ACT_F32> : b.h ? naf_dot_kernel<ACT_F32, ACT_F16> : naf_dot_kernel<ACT_F32, ACT_F32>,
+           dim3((unsigned)ns, (unsigned)((c + 63) / 64), (unsigned)tp.N), dim3(256), 0, a, b, stats, d.part, HW, c, ns, mode);
     const int groups = per_image ? tp.N : 1, Gn = per_image ? ns : tp.N * ns;
     launch(naf_reduce_kernel, dim3(nb((size_t)groups * c)), dim3(256), 0, d.part, dst, groups, Gn, c, scale, dstride);
   }
 
   // LayerNorm + FiLM backward: g += d x; the image's d (folded scale) and d shift rows into drows
-  void ln_bwd(const float* x, const float* dy, const float* stats, const float* mulrow, float* g, int HW, int c, float* dmul, float* dadd) {
+  void ln_bwd(Act x, float* dy, const float* stats, const float* mulrow, float* g, int HW, int c, float* dmul, float* dadd) {
     const int M = tp.N * HW;
-    dot(dy, x, stats, 2, HW, c, dmul, true, n->R, 1.f, false, true);
+    dot(dy, x, stats, 2, HW, c, dmul, true, n->R);
     dot(dy, nullptr, nullptr, 0, HW, c, dadd, true, n->R);
-    launch(NAF_SEL1(naf_ln_bwd_kernel, t16), dim3((unsigned)((M + 15) / 16)), dim3(256), 0, x, dy, stats, mulrow, rstride, g, M, HW, c);
+    launch(NAF_SEL1(naf_ln_bwd_kernel, x), dim3((unsigned)((M + 15) / 16)), dim3(256), 0, x, dy, stats, mulrow, rstride, g, M, HW, c);
   }
 
   // g: d out on entry, d inp on return (in place); cur: the block's input
-  void block_bwd(int bi, const float* cur, float* g, int h, int w) {
+  void block_bwd(int bi, Act cur, float* g, int h, int w) {
     const BlockL& b = n->blocks[bi];
     const BlockDst& s = d.blk[bi];
     const int c = b.c, HW = h * w, M = tp.N * HW, ns = nstrips_of(HW);
@@ -943,34 +954,35 @@ struct TrainRun : Run {
     float *gt = F(tp.gt), *g2a = F(tp.g2a), *g2b = F(tp.g2b), *dr = F(tp.drows) + b.row_off;
     float* sm = F(tp.small);
     float *ds = sm, *pooled = sm + (size_t)tp.N * c, *dpool = sm + 2 * (size_t)tp.N * c;
-    // out = y + conv5(g4) gamma
-    reform(b.conv5, s.g4, gt, h, w);
+    // out = y + conv5(g4) gamma.  For d gamma (d beta below) conv5's (conv3's) output is formed again into the fp32 gt by the forward's
+    // own kernel and operands: under f16 storage the very value the forward scaled
+    gemm(b.conv5, s.g4, gt, h, w);
     dot(g, gt, nullptr, 1, HW, c, G(b.gamma), false, 0);
-    wgrad(b.conv5, s.g4, g, h, w, PRO_NONE, nullptr, nullptr, nullptr, 0, P(b.off_gamma));
-    gemm_l(n->tgemms[b.conv5], g, gt, h, w, EPI_BIAS, PRO_MUL, P(b.off_gamma), nullptr, 0);
-    launch(NAF_SEL1(naf_gate_bwd_kernel, t16), dim3(nb(tot)), dim3(256), 0, gt, s.p4, g2a, c, tot);
-    wgrad(b.conv4, s.y, g2a, h, w, PRO_LN, s.st2, rw + 3 * c, rw + 2 * c, rstride);
-    gemm_l(n->tgemms[b.conv4], g2a, gt, h, w, EPI_BIAS);
+    wgrad(b.conv5, s.g4, g, h, w, {}, P(b.off_gamma));
+    tgemm(b.conv5, g, gt, h, w, scaled(P(b.off_gamma), 0));
+    launch(NAF_SEL1(naf_gate_bwd_kernel, s.p4), dim3(nb(tot)), dim3(256), 0, gt, s.p4, g2a, c, tot);
+    wgrad(b.conv4, s.y, g2a, h, w, ln(s.st2, rw + 3 * c, rw + 2 * c, rstride));
+    tgemm(b.conv4, g2a, gt, h, w);
     ln_bwd(s.y, gt, s.st2, rw + 3 * c, g, HW, c, dr + 3 * c, dr + 2 * c);
     // y = inp + conv3(t2 sca) beta
-    reform(b.conv3, s.t2, gt, h, w, PRO_MUL, s.sca, c);
+    gemm(b.conv3, s.t2, gt, h, w, scaled(s.sca, c));
     dot(g, gt, nullptr, 1, HW, c, G(b.beta), false, 0);
-    wgrad(b.conv3, s.t2, g, h, w, PRO_MUL, nullptr, s.sca, nullptr, c, P(b.off_beta));
-    gemm_l(n->tgemms[b.conv3], g, gt, h, w, EPI_BIAS, PRO_MUL, P(b.off_beta), nullptr, 0);
-    dot(gt, s.t2, nullptr, 1, HW, c, ds, true, c, 1.f, false, true);
-    dot(s.t2, nullptr, nullptr, 0, HW, c, pooled, true, c, 1.f / (float)HW, true);
+    wgrad(b.conv3, s.t2, g, h, w, scaled(s.sca, c), P(b.off_beta));
+    tgemm(b.conv3, g, gt, h, w, scaled(P(b.off_beta), 0));
+    dot(gt, s.t2, nullptr, 1, HW, c, ds, true, c);
+    dot(s.t2, nullptr, nullptr, 0, HW, c, pooled, true, c, 1.f / (float)HW);
     launch(naf_sca_bwd_w_kernel, dim3(nb((size_t)c * c)), dim3(256), 0, ds, pooled, G(b.scaw), G(b.scab), tp.N, c);
     launch(naf_sca_bwd_x_kernel, dim3(nb((size_t)tp.N * c)), dim3(256), 0, ds, P(b.off_scaw), dpool, tp.N, c, 1.f / (float)HW);
-    launch(NAF_SEL1(naf_dwgate_bwd_kernel, t16), dim3(nb(tot)), dim3(256), 0, s.t1, P(b.off_dww), P(b.off_dwb), gt, s.sca, dpool, g2a, h, w, c, tot);
-    launch(NAF_SEL1(naf_dw_bwd_kernel, t16), dim3((unsigned)ns, (unsigned)((2 * c + 63) / 64), (unsigned)tp.N), dim3(256), 0, s.t1, P(b.off_dww), g2a, g2b,
+    launch(NAF_SEL1(naf_dwgate_bwd_kernel, s.t1), dim3(nb(tot)), dim3(256), 0, s.t1, P(b.off_dww), P(b.off_dwb), gt, s.sca, dpool, g2a, h, w, c, tot);
+    launch(NAF_SEL1(naf_dw_bwd_kernel, s.t1), dim3((unsigned)ns, (unsigned)((2 * c + 63) / 64), (unsigned)tp.N), dim3(256), 0, s.t1, P(b.off_dww), g2a, g2b,
            d.part, h, w, 2 * c, ns);
     launch(naf_dw_finish_kernel, dim3(nb((size_t)20 * c)), dim3(256), 0, d.part, tp.N * ns, 2 * c, G(b.dww), G(b.dwb));
-    wgrad(b.conv1, cur, g2b, h, w, PRO_LN, s.st1, rw + c, rw, rstride);
-    gemm_l(n->tgemms[b.conv1], g2b, gt, h, w, EPI_BIAS);
+    wgrad(b.conv1, cur, g2b, h, w, ln(s.st1, rw + c, rw, rstride));
+    tgemm(b.conv1, g2b, gt, h, w);
     ln_bwd(cur, gt, s.st1, rw + c, g, HW, c, dr + c, dr);
   }
 
-  void chain_bwd(const std::vector<int>& list, const float* first, float* g, int h, int w) {
+  void chain_bwd(const std::vector<int>& list, Act first, float* g, int h, int w) {
     for (size_t j = list.size(); j-- > 0;) block_bwd(list[j], chain_in(list, j, first), g, h, w);
   }
 
@@ -979,32 +991,25 @@ struct TrainRun : Run {
     int h = tp.Hp, w = tp.Wp, c = wd;
     float *g = F(tp.gx), *gt = F(tp.gt), *gu = F(tp.gu);
     wgrad(n->g_ending, d.dec[L - 1], F(tp.deps), h, w);
-    gemm_l(n->tgemms[n->g_ending], F(tp.deps), g, h, w, EPI_BIAS);
+    tgemm(n->g_ending, F(tp.deps), g, h, w);
     for (int i = L - 1; i >= 0; --i) {
       chain_bwd(n->dec[i], d.up[i], g, h, w);
       // ups[i]: g is d (shuffle(conv(x)) + skip).  The skip's share is g itself; the convolution's is a 2x2 stride-2 gather of g.
-      gcopy(F(tp.dskip[L - 1 - i]), g, (size_t)tp.N * h * w * c);
-      const float* x = i ? d.dec[i - 1] : d.mid;   // ups[i]'s forward input
-      const GemmL& t = n->tgemms[n->ups[i]];
-      const GemmL& gf = n->gemms[n->ups[i]];
-      {
-        WgArgs a{};   // operands exchanged: the gathered gradient is A, the forward input is "dy"
-        a.x = F(tp.dskip[L - 1 - i]); a.dy = x; a.part = F(tp.wgpart);
-        a.N = tp.N; a.Hin = h; a.Win = w; a.Cin = t.cin; a.Hout = h / 2; a.Wout = w / 2; a.Cout = t.cout; a.KW = 2; a.S = 2; a.P = 0;
-        a.K = t.K(); a.Keff = a.K; a.ldy = t.cout;
-        wgrad_launch(a, PRO_NONE, 1, 4, G(gf.w), nullptr, false, t16);
-      }
-      gemm_l(t, F(tp.dskip[L - 1 - i]), g, h, w, EPI_BIAS);
+      float* dskip = F(tp.dskip[L - 1 - i]);
+      copy(dskip, g, (size_t)tp.N * h * w * c);
+      // operands exchanged: the gathered gradient is A, ups[i]'s forward input is "dy"
+      wgrad_l(n->tgemms[n->ups[i]], dskip, i ? d.dec[i - 1] : d.mid, h, w, {}, nullptr, 1, G(n->gemms[n->ups[i]].w), nullptr);
+      tgemm(n->ups[i], dskip, g, h, w);
       h /= 2; w /= 2; c *= 2;
     }
     chain_bwd(n->mid, d.down[L - 1], g, h, w);
     for (int i = L - 1; i >= 0; --i) {
       // downs[i]: g is d out at level i + 1
       wgrad(n->downs[i], d.skip[i], g, 2 * h, 2 * w);
-      gemm_l(n->tgemms[n->downs[i]], g, gt, h, w, EPI_PSHUF, PRO_NONE, nullptr, nullptr, 0, nullptr, F(tp.dskip[i]));
+      tgemm(n->downs[i], g, gt, h, w, {}, shuffled(F(tp.dskip[i])));
       h *= 2; w *= 2; c /= 2;
-      gcopy(g, gt, (size_t)tp.N * h * w * c);
-      chain_bwd(n->enc[i], enc_in(i), g, h, w);
+      copy(g, gt, (size_t)tp.N * h * w * c);
+      chain_bwd(n->enc[i], i ? d.down[i - 1] : d.enh, g, h, w);
     }
     // enh = x0 + (r a + x0), a = CA(mean r)
     const int HW = h * w, ns = nstrips_of(HW), cs = wd / 16;
@@ -1012,19 +1017,18 @@ struct TrainRun : Run {
     float* sm = F(tp.small);
     float *da = sm, *dz2 = sm + (size_t)tp.N * wd, *pooled = sm + 2 * (size_t)tp.N * wd, *dpool = sm + 3 * (size_t)tp.N * wd,
           *dz1 = sm + 4 * (size_t)tp.N * wd, *hid = dz1 + (size_t)tp.N * cs;
-    dot(g, d.r, nullptr, 1, HW, wd, da, true, wd, 1.f, false, true);
-    if (t16) launch(naf_chansum_h_kernel, dim3((unsigned)ns, (unsigned)((wd + 127) / 128), (unsigned)tp.N), dim3(256), 0, H(d.r), d.part, HW, wd, ns);
-    else launch(naf_chansum_kernel, dim3((unsigned)ns, (unsigned)((wd + 63) / 64), (unsigned)tp.N), dim3(256), 0, d.r, d.part, HW, wd, ns);
+    dot(g, d.r, nullptr, 1, HW, wd, da, true, wd);
+    chansum(d.r, HW, ns);
     launch(naf_ca_bwd_kernel, dim3((unsigned)tp.N), dim3(256), (3 * wd + 256 + 2 * cs) * sizeof(float), d.part, ns, HW, P(n->off_ca1w),
            P(n->off_ca1b), P(n->off_ca2w), d.ca, da, dz2, dz1, hid, pooled, dpool, wd, cs);
     launch(naf_linear_w_kernel, dim3(nb((size_t)wd * cs)), dim3(256), 0, dz2, hid, G(n->ca2w), G(n->ca2b), tp.N, wd, cs);
     launch(naf_linear_w_kernel, dim3(nb((size_t)wd * cs)), dim3(256), 0, dz1, pooled, G(n->ca1w), G(n->ca1b), tp.N, cs, wd);
     launch(naf_scale_add_kernel, dim3(nb(tot)), dim3(256), 0, g, d.ca, dpool, gt, HW, wd, tot);
     wgrad(n->g_rcab2, d.r1, gt, h, w);
-    gemm_l(n->tgemms[n->g_rcab2], gt, gu, h, w, EPI_BIAS);
-    launch(NAF_SEL1(naf_relu_mask_kernel, t16), dim3(nb(tot)), dim3(256), 0, gu, d.r1, tot);
+    tgemm(n->g_rcab2, gt, gu, h, w);
+    launch(NAF_SEL1(naf_relu_mask_kernel, d.r1), dim3(nb(tot)), dim3(256), 0, gu, d.r1, tot);
     wgrad(n->g_rcab0, d.intro, gu, h, w);
-    gemm_l(n->tgemms[n->g_rcab0], gu, gt, h, w, EPI_BIAS);
+    tgemm(n->g_rcab0, gu, gt, h, w);
     launch(naf_twice_plus_kernel, dim3(nb(tot)), dim3(256), 0, g, gt, tot);
     wgrad(n->g_intro, d.xin, g, h, w);
   }
@@ -1032,7 +1036,7 @@ struct TrainRun : Run {
   // past wgrad(g_intro): d xin through intro's transposed pack, then naf_prep_kernel backwards.  net_bwd() left d intro in gx; gt
   // is free from there on and holds d xin [N][Hp][Wp][6].
   void input_bwd(float* dx, float* dcond) {
-    gemm_l(n->tgemms[n->g_intro], F(tp.gx), F(tp.gt), tp.Hp, tp.Wp, EPI_BIAS);
+    tgemm(n->g_intro, F(tp.gx), F(tp.gt), tp.Hp, tp.Wp);
     const size_t total = (size_t)tp.N * tp.H * tp.W;
     launch(naf_unprep_kernel, dim3(nb(total)), dim3(256), 0, F(tp.gt), dx, dcond, tp.H, tp.W, tp.Hp, tp.Wp, total);
   }
@@ -1056,12 +1060,15 @@ struct TrainRun : Run {
 // what train_grads, forward_train and backward check alike; the messages are train_grads'
 int check_train_call(fdsr_nafnet n, const char* fn, int batch, int height, int width, void* workspace, size_t workspace_bytes) {
   const int rc = check_args(n, fn, batch, height, width, workspace, workspace_bytes, train_plan_bytes);
-  if (rc) return rc;
-  if (n->store != FDSR_NAF_STORE_F32)
-    return fail(nullptr, FDSR_E_INVALID, "%s: training runs on fp32 activations only, the object is in FDSR_NAF_STORE_F16, f16 storage (fdsr_nafnet_set_storage)", fn);
-  if (n->prec != FDSR_PREC_F32)
-    return fail(nullptr, FDSR_E_INVALID, "%s: training runs in FDSR_PREC_F32 only, the object is in f16x3 (fdsr_nafnet_set_precision)", fn);
-  return FDSR_OK;
+  return rc ? rc : refuse_training(n, fn, true);
+}
+
+// the TrainRun of a checked call: its plan, the walk's table over the workspace, training's mode
+TrainRun train_run(fdsr_nafnet n, int batch, int height, int width, void* workspace, void* hip_stream) {
+  char* ws = static_cast<char*>(workspace);
+  const TrainPlan tp = make_train_plan(n, batch, height, width);
+  const Mode m = mode_of(n, true);
+  return TrainRun{{n, m, train_dst(n, tp, ws, m.h()), reinterpret_cast<hipStream_t>(hip_stream), nullptr, n->R}, tp, ws};
 }
 
 int find_weight(fdsr_nafnet n, const char* fn, const char* key) {
@@ -1106,18 +1113,12 @@ int fdsr_nafnet_train_grads(fdsr_nafnet n, const float* state_nchw, const float*
   if (n->T < 1 || n->cum_T != n->T) return fail(nullptr, FDSR_E_STATE, "%s: no schedule (fdsr_nafnet_set_sde, fdsr_nafnet_set_thetas_cumsum)", fn);
   if ((rc = ensure_train(n))) return rc;
   kill_ticket(n, fn);
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  char* ws = static_cast<char*>(workspace);
-  const TrainPlan tp = make_train_plan(n, batch, height, width);
-  TrainRun t{{n, train_dst(n, tp, ws), st, nullptr, n->R}, tp, ws};
-  t.t16 = n->train16();
-  HIPCHK(nullptr, hipMemsetAsync(n->d_grad, 0, n->P * sizeof(float), st));
-  HIPCHK(nullptr, hipMemsetAsync(t.F(tp.deps), 0, (size_t)batch * tp.Hp * tp.Wp * 3 * sizeof(float), st));
+  TrainRun t = train_run(n, batch, height, width, workspace, hip_stream);
+  const TrainPlan& tp = t.tp;
+  HIPCHK(nullptr, hipMemsetAsync(n->d_grad, 0, n->P * sizeof(float), t.st));
+  HIPCHK(nullptr, hipMemsetAsync(t.F(tp.deps), 0, (size_t)batch * tp.Hp * tp.Wp * 3 * sizeof(float), t.st));
   t.launch(naf_i2f_kernel, dim3(Run::nb(batch)), dim3(256), 0, timesteps_dev, t.F(tp.tf), batch);
-  t.time_rows(t.F(tp.tf), batch, t.d.tg, t.d.trow);
-  t.rows = t.d.trow;
-  t.prep(state_nchw, cond_nchw);
-  t.net();
+  t.forward(state_nchw, cond_nchw, t.F(tp.tf));
   {
     LossTables tb{n->d_sde, n->d_sde + (n->T + 1), n->d_sde + 2 * (n->T + 1), n->d_cum, n->dt, n->T};
     const int HW = height * width, nblk = (HW + 1023) / 1024;
@@ -1140,16 +1141,9 @@ int fdsr_nafnet_forward_train(fdsr_nafnet n, const float* x_nchw, const float* c
   if (rc) return rc;
   if ((rc = ensure_train(n))) return rc;
   kill_ticket(n, "a second fdsr_nafnet_forward_train");
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  char* ws = static_cast<char*>(workspace);
-  const TrainPlan tp = make_train_plan(n, batch, height, width);
-  TrainRun t{{n, train_dst(n, tp, ws), st, nullptr, n->R}, tp, ws};
-  t.t16 = n->train16();
-  HIPCHK(nullptr, hipMemcpyAsync(t.F(tp.tf), time_dev, (size_t)batch * sizeof(float), hipMemcpyDeviceToDevice, st));   // time_bwd reads it
-  t.time_rows(t.F(tp.tf), batch, t.d.tg, t.d.trow);
-  t.rows = t.d.trow;
-  t.prep(x_nchw, cond_nchw);
-  t.net();
+  TrainRun t = train_run(n, batch, height, width, workspace, hip_stream);
+  HIPCHK(nullptr, hipMemcpyAsync(t.F(t.tp.tf), time_dev, (size_t)batch * sizeof(float), hipMemcpyDeviceToDevice, t.st));   // time_bwd reads it
+  t.forward(x_nchw, cond_nchw, t.F(t.tp.tf));
   t.tail(0, out_nchw, nullptr, nullptr, nullptr, 0, 0);
   if (t.err) return t.err;
   n->ticket.live = ++n->ticket.next;
@@ -1172,13 +1166,10 @@ int fdsr_nafnet_backward(fdsr_nafnet n, int64_t ticket, const float* d_out_nchw,
   int rc = check_train_call(n, fn, batch, height, width, workspace, workspace_bytes);
   if (rc) return rc;
   kill_ticket(n, "an earlier fdsr_nafnet_backward (it consumes the ticket)");
-  hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  char* ws = static_cast<char*>(workspace);
-  const TrainPlan tp = make_train_plan(n, batch, height, width);
-  TrainRun t{{n, train_dst(n, tp, ws), st, nullptr, n->R}, tp, ws};
-  t.t16 = n->train16();
-  t.rows = t.d.trow;
-  HIPCHK(nullptr, hipMemsetAsync(n->d_grad, 0, n->P * sizeof(float), st));
+  TrainRun t = train_run(n, batch, height, width, workspace, hip_stream);
+  const TrainPlan& tp = t.tp;
+  t.rows = t.d.trow;   // the forward's
+  HIPCHK(nullptr, hipMemsetAsync(n->d_grad, 0, n->P * sizeof(float), t.st));
   const size_t total = (size_t)batch * tp.Hp * tp.Wp;
   t.launch(naf_dout_kernel, dim3(Run::nb(total)), dim3(256), 0, d_out_nchw, t.F(tp.deps), height, width, tp.Hp, tp.Wp, total);
   t.net_bwd();
@@ -1199,22 +1190,14 @@ int fdsr_nafnet_set_weights_flat(fdsr_nafnet n, const float* src_dev, size_t cou
   const char* fn = "fdsr_nafnet_set_weights_flat";
   if (!n || !src_dev) return fail(nullptr, FDSR_E_INVALID, "%s: null argument", fn);
   if (count != n->P) return fail(nullptr, FDSR_E_INVALID, "%s: count %zu is not the %zu floats of all tensors", fn, count, n->P);
-  if (n->store != FDSR_NAF_STORE_F32)
-    return fail(nullptr, FDSR_E_INVALID, "%s: training runs on fp32 activations only, the object is in FDSR_NAF_STORE_F16, f16 storage", fn);
-  if (n->prec != FDSR_PREC_F32)   // the device-side re-pack below writes the fp32 forms only
-    return fail(nullptr, FDSR_E_INVALID, "%s: training runs in FDSR_PREC_F32 only, the object is in f16x3", fn);
-  int rc = finalize(n);   // the first upload is the host's (fdsr_nafnet_load_weight): it sets the constants of the arena
+  int rc = refuse_training(n, fn, false);
   if (rc) return rc;
+  if ((rc = finalize(n))) return rc;   // the first upload is the host's (fdsr_nafnet_load_weight): it sets the constants of the arena
   if ((rc = ensure_train(n))) return rc;
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
   HIPCHK(nullptr, hipMemcpyAsync(n->d_master, src_dev, n->P * sizeof(float), hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(naf_repack_kernel, dim3(Run::nb(n->arena_floats)), dim3(256), 0, st, n->d_arena, n->d_master, n->d_map, n->arena_floats);
-  HIPCHK(nullptr, hipGetLastError());
-  if ((rc = rebuild_wq(n, st))) return rc;
-  n->host_stale = true;
-  n->table_valid = false;
+  if ((rc = master_moved(n, st))) return rc;
   kill_ticket(n, fn);
-  drop_graph(n);
   return FDSR_OK;
 }
 
@@ -1240,13 +1223,10 @@ int fdsr_nafnet_optim_step(fdsr_nafnet n, int kind, double lr, double beta1, dou
   if (!n || kind < FDSR_NAFNET_ADAM || kind > FDSR_NAFNET_LION || !(lr >= 0.) || !(beta1 >= 0. && beta1 < 1.) || !(beta2 >= 0. && beta2 < 1.) ||
       !(eps >= 0.) || !(weight_decay >= 0.))
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_optim_step: bad arguments (kind %d)", kind);
-  if (n->store != FDSR_NAF_STORE_F32)
-    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_optim_step: training runs on fp32 activations only, the object is in FDSR_NAF_STORE_F16, f16 storage");
-  if (n->prec != FDSR_PREC_F32)   // the device-side re-pack below writes the fp32 forms only
-    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_optim_step: training runs in FDSR_PREC_F32 only, the object is in f16x3");
+  const int rc = refuse_training(n, "fdsr_nafnet_optim_step", false);
+  if (rc) return rc;
   if (!n->d_grad || !n->master_valid || n->dirty) return fail(nullptr, FDSR_E_STATE, "fdsr_nafnet_optim_step: no gradients (fdsr_nafnet_train_grads first)");
   hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-  int rc = FDSR_OK;
   kill_ticket(n, "fdsr_nafnet_optim_step");
   n->opt_step += 1;
   OptArgs o{};
@@ -1257,13 +1237,7 @@ int fdsr_nafnet_optim_step(fdsr_nafnet n, int kind, double lr, double beta1, dou
   o.bc2_sqrt = (float)std::sqrt(bc2);
   hipLaunchKernelGGL(naf_optim_kernel, dim3(Run::nb(n->P)), dim3(256), 0, st, n->d_master, n->d_grad, n->d_m, n->d_v, o, n->P);
   HIPCHK(nullptr, hipGetLastError());
-  hipLaunchKernelGGL(naf_repack_kernel, dim3(Run::nb(n->arena_floats)), dim3(256), 0, st, n->d_arena, n->d_master, n->d_map, n->arena_floats);
-  HIPCHK(nullptr, hipGetLastError());
-  if ((rc = rebuild_wq(n, st))) return rc;
-  n->host_stale = true;
-  n->table_valid = false;
-  drop_graph(n);
-  return FDSR_OK;
+  return master_moved(n, st);
 }
 
 int fdsr_nafnet_read_weight(fdsr_nafnet n, const char* key, float* dst, int dst_on_device, void* hip_stream) {
