@@ -5,7 +5,8 @@
 
 namespace fdsr {
 
-typedef float f32x4_io __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // activations in HBM: fp32 (f32 / f16x3 modes) or bf16 (bf16 mode)
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned v) { return __builtin_bit_cast(float, v << 16); }
@@ -13,7 +14,7 @@ __device__ __forceinline__ unsigned short f32_to_bf16_bits(float v) { return __b
 // f16x3 range guard: the hi/lo split clamps every staged value to the f16 range.  GroupNorm'ed inputs are re-scaled before the
 // split, but a RAW conv input (res_conv, down/upsample convs, the rider's chunks) beyond +-65504 would be clamped SILENTLY:
 // the staging paths of raw inputs raise a sticky device flag instead (fdsr_check_saturation reads and clears it).
-__device__ __forceinline__ void sat_check(int* flag, f32x4_io v, float lim) {
+__device__ __forceinline__ void sat_check(int* flag, f32x4 v, float lim) {
   const float m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
   if (m > lim) *flag = 1;
 }
@@ -40,10 +41,10 @@ __device__ __forceinline__ unsigned short f32_to_f16_bits(float v) {
 }
 template <int PREC> struct ActIO;
 template <> struct ActIO<PREC_F16X3> {
-  typedef f32x4_io Quad;   // four consecutive channels as loaded
+  typedef f32x4 Quad;   // four consecutive channels as loaded
   static constexpr int ESZ = 4;
-  static __device__ __forceinline__ Quad load4(const float* base, size_t idx) { return *reinterpret_cast<const f32x4_io*>(base + idx); }
-  static __device__ __forceinline__ f32x4_io widen(Quad q) { return q; }
+  static __device__ __forceinline__ Quad load4(const float* base, size_t idx) { return *reinterpret_cast<const f32x4*>(base + idx); }
+  static __device__ __forceinline__ f32x4 widen(Quad q) { return q; }
   static __device__ __forceinline__ float load1(const float* base, size_t idx) { return base[idx]; }
   static __device__ __forceinline__ void store1(float* base, size_t idx, float v) { base[idx] = v; }
 };
@@ -53,8 +54,8 @@ template <> struct ActIO<PREC_BF16> {
   static __device__ __forceinline__ Quad load4(const float* base, size_t idx) {
     return *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(base) + idx);
   }
-  static __device__ __forceinline__ f32x4_io widen(Quad q) {
-    f32x4_io r = {__builtin_bit_cast(float, q.x << 16), __builtin_bit_cast(float, q.x & 0xffff0000u),
+  static __device__ __forceinline__ f32x4 widen(Quad q) {
+    f32x4 r = {__builtin_bit_cast(float, q.x << 16), __builtin_bit_cast(float, q.x & 0xffff0000u),
                __builtin_bit_cast(float, q.y << 16), __builtin_bit_cast(float, q.y & 0xffff0000u)};
     return r;
   }
@@ -71,10 +72,10 @@ template <> struct ActIO<PREC_F16> {
   static __device__ __forceinline__ Quad load4(const float* base, size_t idx) {
     return *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(base) + idx);
   }
-  static __device__ __forceinline__ f32x4_io widen(Quad q) {
+  static __device__ __forceinline__ f32x4 widen(Quad q) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     const h2 a = __builtin_bit_cast(h2, q.x), b = __builtin_bit_cast(h2, q.y);
-    f32x4_io r = {(float)a[0], (float)a[1], (float)b[0], (float)b[1]};
+    f32x4 r = {(float)a[0], (float)a[1], (float)b[0], (float)b[1]};
     return r;
   }
   static __device__ __forceinline__ float load1(const float* base, size_t idx) {
@@ -87,7 +88,7 @@ template <> struct ActIO<PREC_F16> {
 
 // four fp32 values -> four 16-bit values of the mode's storage format, packed (PREC_BF16 / PREC_F16)
 template <int PREC>
-__device__ __forceinline__ uint2 pack4_16(f32x4_io v) {
+__device__ __forceinline__ uint2 pack4_16(f32x4 v) {
   uint2 pk;
   if (PREC == PREC_F16) {
     pk.x = (unsigned)f32_to_f16_bits(v[0]) | ((unsigned)f32_to_f16_bits(v[1]) << 16);
@@ -103,7 +104,7 @@ __device__ __forceinline__ unsigned short f32_to_16_bits(float v, int code) { re
 // the MFMA operand form of a staged quad: no range clamp (GroupNorm'ed / Swish'ed values and bf16 / f16 activations read back are in
 // range; a RAW fp32 input is clamped by the caller where the f16x3 mode clamps it)
 template <int PREC>
-__device__ __forceinline__ uint2 stage4_16(f32x4_io v) {
+__device__ __forceinline__ uint2 stage4_16(f32x4 v) {
   if (PREC == PREC_F16) {
     typedef _Float16 h4 __attribute__((ext_vector_type(4)));
     const h4 hb = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
@@ -114,17 +115,15 @@ __device__ __forceinline__ uint2 stage4_16(f32x4_io v) {
   return __builtin_bit_cast(uint2, hb);
 }
 // one 16-bit MFMA of the mode: v_mfma_f32_16x16x32_{bf16,f16} / v_mfma_f32_32x32x16_{bf16,f16} on 16-byte operand registers
-typedef float io_f32x4 __attribute__((ext_vector_type(4)));
-typedef float io_f32x16 __attribute__((ext_vector_type(16)));
 template <int PREC>
-__device__ __forceinline__ io_f32x4 mfma16_k32(uint4 a, uint4 b, io_f32x4 c) {
+__device__ __forceinline__ f32x4 mfma16_k32(uint4 a, uint4 b, f32x4 c) {
   typedef __bf16 b8_ __attribute__((ext_vector_type(8)));
   typedef _Float16 h8_ __attribute__((ext_vector_type(8)));
   if (PREC == PREC_BF16) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8_, a), __builtin_bit_cast(b8_, b), c, 0, 0, 0);
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8_, a), __builtin_bit_cast(h8_, b), c, 0, 0, 0);
 }
 template <int PREC>
-__device__ __forceinline__ io_f32x16 mfma32_k16(uint4 a, uint4 b, io_f32x16 c) {
+__device__ __forceinline__ f32x16 mfma32_k16(uint4 a, uint4 b, f32x16 c) {
   typedef __bf16 b8_ __attribute__((ext_vector_type(8)));
   typedef _Float16 h8_ __attribute__((ext_vector_type(8)));
   if (PREC == PREC_BF16) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b8_, a), __builtin_bit_cast(b8_, b), c, 0, 0, 0);

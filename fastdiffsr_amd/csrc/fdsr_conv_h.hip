@@ -21,23 +21,13 @@
 //   * the halo is double-buffered: chunk k+1 is transformed and written while chunk k is being
 //     multiplied; one barrier per chunk
 //   * epilogue as in the fp32 kernel (bias + noise-embedding shift + residual, NHWC stores)
-#include "fdsr_kernels.h"
-#include "fdsr_act_io.h"
+#include "fdsr_conv_dev.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
 namespace fdsr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float silu_h(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
 template <int KS, int STRIDE, bool UP, int TH, int WN, int PREC, int KSUB>
 struct ConvHCfg {
@@ -94,12 +84,7 @@ __global__ void __launch_bounds__(512, 2) conv_mfma_h_kernel(const ConvParams p)
 
   const int nco = p.Cout_pad / BN;
   const int tilesX = (p.Wout + TW - 1) / TW, tilesY = (p.Hout + TH - 1) / TH;
-  int bid;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = b & 7, k = b >> 3;
-    bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k;
-  }
+  int bid = xcd_block_id(blockIdx.x, gridDim.x);
   const int SK = p.ksplit > 1 ? p.ksplit : 1;
   const int ksi = bid % SK;   // K slice of this workgroup
   bid /= SK;
@@ -147,24 +132,14 @@ __global__ void __launch_bounds__(512, 2) conv_mfma_h_kernel(const ConvParams p)
   f32x4 rsc = {1.f, 1.f, 1.f, 1.f}, rsh = {0.f, 0.f, 0.f, 0.f};
   const int nk = p.Cin_pad / KC;               // main chunks; chunks nk .. nk + nkr - 1 are the rider's (raw second input, centre tap)
   auto prefetch_to = [&](int kc, Quad* rin) {
-    int cbase = kc * KC;
-    const float* base;
-    int Cs, cc;
-    bool g = gn;
-    if (RIDER && kc >= nk) {
-      cbase -= nk * KC;
-      g = false;
-      if (cbase < p.Cr0) { base = p.xr0; Cs = p.Cr0; cc = cbase + q * 4; }
-      else { base = p.xr1; Cs = p.Cr1; cc = cbase - p.Cr0 + q * 4; }
-    } else if (cbase < p.C0) { base = p.x0; Cs = p.C0; cc = cbase + q * 4; }
-    else { base = p.x1; Cs = p.C1; cc = cbase - p.C0 + q * 4; }
-    if (g) {   // per-(image, channel) GroupNorm scale/shift travel with the input prefetch
-      rsc = *reinterpret_cast<const f32x4*>(p.gn_scale + (size_t)n * Cin + cbase + q * 4);
-      rsh = *reinterpret_cast<const f32x4*>(p.gn_shift + (size_t)n * Cin + cbase + q * 4);
+    const ChunkSrc src = chunk_src<RIDER>(p, kc, KC, nk, q, gn);
+    if (src.gn) {   // per-(image, channel) GroupNorm scale/shift travel with the input prefetch
+      rsc = *reinterpret_cast<const f32x4*>(p.gn_scale + (size_t)n * Cin + src.cbase + q * 4);
+      rsh = *reinterpret_cast<const f32x4*>(p.gn_shift + (size_t)n * Cin + src.cbase + q * 4);
     }
 #pragma unroll
     for (int i = 0; i < NIN; ++i)   // branch-free: padding / unused rows read pixel 0 and are zeroed in stage()
-      rin[i] = IO::load4(base, (size_t)(in_pix[i] < 0 ? 0 : in_pix[i]) * Cs + cc);
+      rin[i] = IO::load4(src.base, (size_t)(in_pix[i] < 0 ? 0 : in_pix[i]) * src.Cs + src.cc);
   };
   auto prefetch = [&](int kc) { prefetch_to(kc, rin); };
   auto stage_from = [&](int kc, unsigned char* buf, const Quad* rin) {
@@ -174,8 +149,7 @@ __global__ void __launch_bounds__(512, 2) conv_mfma_h_kernel(const ConvParams p)
       if (NIN * RPP > NPIX && i == NIN - 1 && row0 + i * RPP >= NPIX) continue;   // only the last pass can overrun
       f32x4 v = IO::widen(rin[i]);
       if (gn && !(RIDER && kc >= nk)) {
-        v = v * sc + sh;
-        if (!p.gn_plain) { v.x = silu_h(v.x); v.y = silu_h(v.y); v.z = silu_h(v.z); v.w = silu_h(v.w); }
+        v = gn_act4(v, sc, sh, p.gn_plain);
       } else if (PREC == PREC_F16X3 && p.sat_flag) {
         sat_check(p.sat_flag, v, 65504.f);             // a raw input the split below would clamp: tell the host
       }
@@ -183,12 +157,8 @@ __global__ void __launch_bounds__(512, 2) conv_mfma_h_kernel(const ConvParams p)
       const float lim = in_pix[i] >= 0 ? 65504.f : 0.f;   // f16 range clamp and zero padding in one med3
       unsigned char* dst = buf + (row0 + i * RPP) * ROWB + (q >> 2) * (NP * 32) + (q & 3) * 8;
       if (PREC == PREC_F16X3) {
-        // clamp to the f16 range (also maps NaN-free), hi = rn(v), lo = rn(v - hi): 22 mantissa bits
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = __builtin_amdgcn_fmed3f(v[e], -lim, lim);   // padding: lim = 0
-        h4 hi = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-        h4 lo = {(_Float16)(v.x - (float)hi.x), (_Float16)(v.y - (float)hi.y), (_Float16)(v.z - (float)hi.z),
-                 (_Float16)(v.w - (float)hi.w)};
+        h4 hi, lo;
+        split4_2step(v, lim, hi, lo);   // padding: lim = 0
         *reinterpret_cast<h4*>(dst) = hi;
         *reinterpret_cast<h4*>(dst + 32) = lo;
       } else {
@@ -346,14 +316,9 @@ __global__ void __launch_bounds__(512, 2) conv_mfma_h_kernel(const ConvParams p)
   // (sum, sumsq): the consumer's GroupNorm statistics, reduced in a fixed order. ----
   const int co = co0 + wn * 32 + r31;
   const bool cok = co < p.Cout;
-  float add;
-  {   // unconditional loads (clamped channel, noise shift through a 0 / 1 factor): one round trip, not three
-    const int cs = cok ? co : 0;
-    const float* tembp = p.temb ? p.temb + (size_t)n * p.temb_stride + p.temb_off : p.bias;
-    add = p.bias[cs];
-    if (RIDER) add += p.bias_r[cs];
-    add += (p.temb ? 1.f : 0.f) * tembp[cs];
-  }
+  // unconditional loads (clamped channel, noise shift through a 0 / 1 factor): one round trip, not three
+  const float* tembp = p.temb ? p.temb + (size_t)n * p.temb_stride + p.temb_off : p.bias;
+  const float add = epi_add1<RIDER>(p.bias, p.bias_r, tembp, p.temb ? 1.f : 0.f, cok ? co : 0);
   float s1 = 0.f, s2 = 0.f;
   const float winv_m = p.w_inv_scale_dev ? *p.w_inv_scale_dev : p.w_inv_scale;   // uniform: a scalar load
   const float winv = RIDER ? (p.w_inv_scale_r_dev ? *p.w_inv_scale_r_dev : p.w_inv_scale_r) : winv_m;

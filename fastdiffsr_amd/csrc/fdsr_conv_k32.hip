@@ -26,20 +26,11 @@
 //     the 8- / 4-row tiles; f16x3 rider-less kernels fetch and stage the next chunk in two halves and run their last chunk
 //     as a code copy that already fetches the residual tile.  The K32_* / XS_* macros below are the A/B switches of those
 //     choices (tools/k32_variant.sh builds a variant library; every measured pair is in profiles/r03_k32_ab.txt).
-#include "fdsr_kernels.h"
-#include "fdsr_act_io.h"
+#include "fdsr_conv_dev.h"
 
 #include <type_traits>
 
 namespace fdsr {
-
-typedef float k_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 k_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 k_h4 __attribute__((ext_vector_type(4)));
-typedef __bf16 k_b8 __attribute__((ext_vector_type(8)));
-typedef __bf16 k_b4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float silu_k(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
 #ifndef XS_F16X3
 #define XS_F16X3 2
@@ -135,12 +126,7 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
 
   const int nco = p.Cout_pad / BN;
   const int tilesX = (p.Wout + TW - 1) / TW, tilesY = (p.Hout + TH - 1) / TH;
-  int bid;
-  {   // consecutive tiles on one XCD (as conv_mfma_h_kernel)
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = b & 7, k = b >> 3;
-    bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k;
-  }
+  int bid = xcd_block_id(blockIdx.x, gridDim.x);   // consecutive tiles on one XCD
   const int SK = p.ksplit > 1 ? p.ksplit : 1;
   const int ksi = bid % SK;
   bid /= SK;
@@ -202,7 +188,7 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
   QM rin[NA];
   QM rr1[RIDER && SPLIT ? NIN : 1];          // rider chunks are fetched whole: first set (rin itself when not SPLIT)
   QM rin2[RIDER && K32_RIDER2 && NW == 8 ? NIN : 1];   // (small workgroups: one set -- the CU's other workgroup covers the latency)   // second prefetch set of the rider chunks
-  k_f32x4 rsc = {1.f, 1.f, 1.f, 1.f}, rsh = {0.f, 0.f, 0.f, 0.f};
+  f32x4 rsc = {1.f, 1.f, 1.f, 1.f}, rsh = {0.f, 0.f, 0.f, 0.f};
   const int nk = p.Cin_pad / KC;               // main chunks; nk .. nk + nkr - 1 are the rider's (raw second input, centre tap)
   const int nk16 = p.Cin_pad / 16;
   const int nkr = RIDER ? p.nkr / 2 : 0;
@@ -273,47 +259,38 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
   };
   auto prefetch_rng = [&](int kc, QM* rin, auto i0_tag, auto i1_tag, bool load_gn) __attribute__((always_inline)) {
     constexpr int I0 = decltype(i0_tag)::value, I1 = decltype(i1_tag)::value;
-    int cbase = kc * KC;
-    const float* base;
-    int Cs, cc;
-    bool gg = gn;
-    if (RIDER && kc >= nk) {
-      cbase -= nk * KC;
-      gg = false;
-      if (cbase < p.Cr0) { base = p.xr0; Cs = p.Cr0; cc = cbase + q * 4; }
-      else { base = p.xr1; Cs = p.Cr1; cc = cbase - p.Cr0 + q * 4; }
-    } else if (cbase < p.C0) { base = p.x0; Cs = p.C0; cc = cbase + q * 4; }
-    else { base = p.x1; Cs = p.C1; cc = cbase - p.C0 + q * 4; }
-    if (!GNC && gg && load_gn) {
-      rsc = *reinterpret_cast<const k_f32x4*>(p.gn_scale + (size_t)n * Cin + cbase + q * 4);
-      rsh = *reinterpret_cast<const k_f32x4*>(p.gn_shift + (size_t)n * Cin + cbase + q * 4);
+    const ChunkSrc src = chunk_src<RIDER>(p, kc, KC, nk, q, gn);
+    if (!GNC && src.gn && load_gn) {
+      rsc = *reinterpret_cast<const f32x4*>(p.gn_scale + (size_t)n * Cin + src.cbase + q * 4);
+      rsh = *reinterpret_cast<const f32x4*>(p.gn_shift + (size_t)n * Cin + src.cbase + q * 4);
     }
 #pragma unroll
     for (int i = I0; i < I1; ++i) {
       const size_t pi = (size_t)(in_pix[i] < 0 ? 0 : in_pix[i]);
-      rin[i - I0].q = IO::load4(base, pi * Cs + cc);
+      rin[i - I0].q = IO::load4(src.base, pi * src.Cs + src.cc);
       if (DROP)   // the dropout bytes of these four channels ([N][H][W][C0], single input); a rider chunk reads element 0 (unused): a select, not a branch
-        rin[i - I0].m = *reinterpret_cast<const unsigned*>(p.drop_mask + ((RIDER && kc >= nk) ? (size_t)0 : pi * Cs + cc));
+        rin[i - I0].m = *reinterpret_cast<const unsigned*>(p.drop_mask + ((RIDER && kc >= nk) ? (size_t)0 : pi * src.Cs + src.cc));
     }
   };
   auto prefetch_to = [&](int kc, QM* rin) __attribute__((always_inline)) { prefetch_rng(kc, rin, I_0{}, I_N{}, true); };
   auto stage_rng = [&](int kc, unsigned char* buf, const QM* rin, auto i0_tag, auto i1_tag) __attribute__((always_inline)) {
     constexpr int I0 = decltype(i0_tag)::value, I1 = decltype(i1_tag)::value;
-    k_f32x4 sc = rsc, sh = rsh;
+    f32x4 sc = rsc, sh = rsh;
     if (GNC && !(RIDER && kc >= nk)) {   // this chunk's four channels of the LDS table the prologue built
-      sc = *reinterpret_cast<const k_f32x4*>(gnc_sc + (kc * KC - gnc_lo + q * 4));
-      sh = *reinterpret_cast<const k_f32x4*>(gnc_sh + (kc * KC - gnc_lo + q * 4));
+      sc = *reinterpret_cast<const f32x4*>(gnc_sc + (kc * KC - gnc_lo + q * 4));
+      sh = *reinterpret_cast<const f32x4*>(gnc_sh + (kc * KC - gnc_lo + q * 4));
     }
 #pragma unroll
     for (int i = I0; i < I1; ++i) {
       if (NIN * RPP > NPIX && i == NIN - 1 && row0 + i * RPP >= NPIX) continue;   // only the last pass can overrun
-      k_f32x4 v = IO::widen(rin[i - I0].q);
+      f32x4 v = IO::widen(rin[i - I0].q);
       if (K32_DIAG & 16) v = sc;
       if ((K32_DIAG & 1) && gn) {
         v = v + sh;
       } else if (gn && !(RIDER && kc >= nk)) {
+        // (gn_act4 / drop4 of fdsr_conv_dev.h written out: through the calls the 16-row f16x3 tile gained an s_waitcnt vmcnt(0))
         v = v * sc + sh;
-        if (!p.gn_plain) { v.x = silu_k(v.x); v.y = silu_k(v.y); v.z = silu_k(v.z); v.w = silu_k(v.w); }
+        if (!p.gn_plain) { v.x = silu_fast(v.x); v.y = silu_fast(v.y); v.z = silu_fast(v.z); v.w = silu_fast(v.w); }
         if (DROP) {   // train-mode Dropout(p) behind the Swish: keep bytes are 0 / 1
           const unsigned m = rin[i - I0].m;
 #pragma unroll
@@ -326,31 +303,18 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
       unsigned char* dst = buf + sd;
       if (PREC == PREC_F16X3) {
         const float lim = in_pix[i] >= 0 ? 65504.f : 0.f;   // f16 range clamp and zero padding in one med3
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = __builtin_amdgcn_fmed3f(v[e], -lim, lim);
 #if K32_MIXSPLIT
-        // one packed convert and two v_fma_mix per pair: lo = f16(fma(hi, -1, v)), rounded once -- bit-identical to the two-step
-        // form below (as in fdsr_train.hip).  With 16x16x32 MFMAs holding the issue port half of their time
-        // the staging VALU count matters more than it did beside 32x32x16.
-        typedef _Float16 h2t __attribute__((ext_vector_type(2)));
+        // the mix form (same bits as the two-step form below): with 16x16x32 MFMAs holding the issue port half of their time the
+        // staging VALU count matters more than it did beside 32x32x16.
         uint2 hi, lo;
-        {
-          const h2t h0 = {(_Float16)v[0], (_Float16)v[1]}, h1 = {(_Float16)v[2], (_Float16)v[3]};
-          hi.x = __builtin_bit_cast(unsigned, h0);
-          hi.y = __builtin_bit_cast(unsigned, h1);
-        }
-        asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lo.x) : "v"(hi.x), "v"(v[0]));
-        asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo.x) : "v"(hi.x), "v"(v[1]));
-        asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lo.y) : "v"(hi.y), "v"(v[2]));
-        asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo.y) : "v"(hi.y), "v"(v[3]));
+        split4_mix(v, lim, hi, lo);
         *reinterpret_cast<uint2*>(dst) = hi;
         *reinterpret_cast<uint2*>(buf + (sd ^ 64)) = lo;   // slot + 4 of the swizzled row
 #else
-        k_h4 hi = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-        k_h4 lo = {(_Float16)(v.x - (float)hi.x), (_Float16)(v.y - (float)hi.y), (_Float16)(v.z - (float)hi.z),
-                   (_Float16)(v.w - (float)hi.w)};
-        *reinterpret_cast<k_h4*>(dst) = hi;
-        *reinterpret_cast<k_h4*>(buf + (sd ^ 64)) = lo;   // slot + 4 of the swizzled row
+        h4 hi, lo;
+        split4_2step(v, lim, hi, lo);
+        *reinterpret_cast<h4*>(dst) = hi;
+        *reinterpret_cast<h4*>(buf + (sd ^ 64)) = lo;   // slot + 4 of the swizzled row
 #endif
       } else {
         const float keep = in_pix[i] >= 0 ? 1.f : 0.f;
@@ -388,13 +352,13 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
     if (NP == 2) xoff[kx][NP - 1] = xoff[kx][0] ^ 64;
   }
 
-  k_f32x4 acc[MB][2][2];   // [row][pixel half][cout half]
+  f32x4 acc[MB][2][2];   // [row][pixel half][cout half]
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
     for (int ph = 0; ph < 2; ++ph)
 #pragma unroll
-      for (int ch = 0; ch < 2; ++ch) acc[mb][ph][ch] = k_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int ch = 0; ch < 2; ++ch) acc[mb][ph][ch] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int kc0 = ksi * nkt / SK, kc1 = (ksi + 1) * nkt / SK;   // this slice's chunks
   if (RFIRST || (RIDER && kc0 >= nk)) load_w(RFIRST ? nk : kc0, 0, 0);
@@ -450,7 +414,7 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
           for (int ch = 0; ch < 2; ++ch) {
             const uint4 xv = Xf[xs][ph][term == 0 ? NP - 1 : 0];
             const uint4 wv = Wf[ws][ch][term == 1 ? NP - 1 : 0];
-            acc[mb][ph][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(k_h8, wv), __builtin_bit_cast(k_h8, xv),
+            acc[mb][ph][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, wv), __builtin_bit_cast(h8, xv),
                                                                     acc[mb][ph][ch], 0, 0, 0);
           }
     } else {
@@ -630,7 +594,7 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
   // bias (+ the rider's) + noise shift of this lane's output channels.  Every load is issued unconditionally (a clamped channel, the
   // noise shift through a 0 / 1 factor): with `if (p.temb)` / `if (cok)` around them the compiler put an s_waitcnt vmcnt(0) behind each
   // of the eight pairs -- eight exposed round trips at the end of every tile, with nothing else running on the CU.
-  k_f32x4 add[2];
+  f32x4 add[2];
   bool cok[2];
   const float* tembp = p.temb ? p.temb + (size_t)n * p.temb_stride + p.temb_off : p.bias;
   const float tmul = p.temb ? 1.f : 0.f;
@@ -638,14 +602,7 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
   for (int ch = 0; ch < 2; ++ch) {
     const int co = cob + 16 * ch;
     cok[ch] = co < p.Cout;   // Cout % 4 == 0 (launcher)
-    const int cs = cok[ch] ? co : 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float a = p.bias[cs + r];
-      if (RIDER) a += p.bias_r[cs + r];
-      a += tmul * tembp[cs + r];
-      add[ch][r] = a;
-    }
+    add[ch] = epi_add4<RIDER>(p.bias, p.bias_r, tembp, tmul, cok[ch] ? co : 0);
   }
   const float winv_m = p.w_inv_scale_dev ? *p.w_inv_scale_dev : p.w_inv_scale;
   const float winv = RIDER && !RFIRST ? (p.w_inv_scale_r_dev ? *p.w_inv_scale_r_dev : p.w_inv_scale_r) : winv_m;
@@ -668,22 +625,15 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
         for (int ch = 0; ch < 2; ++ch) {
           const int oy = oy0 + wm + mb * WM, ox = ox0 + 16 * ph + c15;
           if (interior || (cok[ch] && oy < p.Hout && ox < p.Wout))
-            *reinterpret_cast<k_f32x4*>(sb + obase + mb * rstride + ph * pstride + 16 * ch) = acc[mb][ph][ch];
+            *reinterpret_cast<f32x4*>(sb + obase + mb * rstride + ph * pstride + 16 * ch) = acc[mb][ph][ch];
         }
     return;
   }
-  k_f32x4 s1[2], s2[2];
+  f32x4 s1[2], s2[2];
 #pragma unroll
-  for (int ch = 0; ch < 2; ++ch) s1[ch] = s2[ch] = k_f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int ch = 0; ch < 2; ++ch) s1[ch] = s2[ch] = f32x4{0.f, 0.f, 0.f, 0.f};
   auto epilogue = [&](auto out16_tag) __attribute__((always_inline)) {
     constexpr bool OUT16 = decltype(out16_tag)::value;
-    auto put4 = [&](size_t idx, k_f32x4 v) {
-      if (OUT16) {
-        *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p.out) + idx) = pack4_16<PREC>(v);
-      } else {
-        *reinterpret_cast<k_f32x4*>(p.out + idx) = v;
-      }
-    };
     if (interior) {
       if (p.res && !res_early) {
 #pragma unroll
@@ -699,9 +649,9 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
         for (int ph = 0; ph < 2; ++ph)
 #pragma unroll
           for (int ch = 0; ch < 2; ++ch) {
-            k_f32x4 v = acc[mb][ph][ch] * winv + add[ch];
+            f32x4 v = acc[mb][ph][ch] * winv + add[ch];
             if (p.res) v += IO::widen(rv[mb][ph][ch]);
-            put4(obase + mb * rstride + ph * pstride + 16 * ch, v);
+            put4<PREC, OUT16>(p.out, obase + mb * rstride + ph * pstride + 16 * ch, v);
             if (!(K32_DIAG & 4)) {
               s1[ch] += v;
               s2[ch] += v * v;
@@ -717,9 +667,9 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
             const int oy = oy0 + wm + mb * WM, ox = ox0 + 16 * ph + c15;
             if (cok[ch] && oy < p.Hout && ox < p.Wout) {
               const size_t idx = obase + mb * rstride + ph * pstride + 16 * ch;
-              k_f32x4 v = acc[mb][ph][ch] * winv + add[ch];
+              f32x4 v = acc[mb][ph][ch] * winv + add[ch];
               if (p.res) v += IO::widen(IO::load4(p.res, idx));
-              put4(idx, v);
+              put4<PREC, OUT16>(p.out, idx, v);
               s1[ch] += v;
               s2[ch] += v * v;
             }
@@ -739,9 +689,9 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch) {
       const int cs = cok[ch] ? cob + 16 * ch : 0;
-      const k_f32x4 gsc = *reinterpret_cast<const k_f32x4*>(p.gb_scale + (size_t)n * Ct + cs);
-      const k_f32x4 gsh = *reinterpret_cast<const k_f32x4*>(p.gb_shift + (size_t)n * Ct + cs);
-      k_f32x4 gme, grs;
+      const f32x4 gsc = *reinterpret_cast<const f32x4*>(p.gb_scale + (size_t)n * Ct + cs);
+      const f32x4 gsh = *reinterpret_cast<const f32x4*>(p.gb_shift + (size_t)n * Ct + cs);
+      f32x4 gme, grs;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int grp = (cs + r) / cpg;
@@ -752,7 +702,7 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
       int xcs;
       if (cs < p.gb_C0) { xb = p.gb_x0 + cs; xcs = p.gb_C0; }
       else { xb = p.gb_x1 + (cs - p.gb_C0); xcs = Ct - p.gb_C0; }
-      k_f32x4 xq[MB][2];
+      f32x4 xq[MB][2];
       unsigned mq[MB][2];
 #pragma unroll
       for (int mb = 0; mb < MB; ++mb) {
@@ -761,7 +711,7 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
         for (int ph = 0; ph < 2; ++ph) {
           const size_t pix = (size_t)(n * p.Hout + oy) * p.Wout + min(ox0 + 16 * ph + c15, p.Wout - 1);
           if (K32_GNB_DIAG & 2) { xq[mb][ph] = gsc; mq[mb][ph] = 0x01010101u; continue; }
-          xq[mb][ph] = *reinterpret_cast<const k_f32x4*>(xb + pix * xcs);
+          xq[mb][ph] = *reinterpret_cast<const f32x4*>(xb + pix * xcs);
           mq[mb][ph] = *reinterpret_cast<const unsigned*>(mk + (hm ? pix * Ct + cs : (size_t)0));
         }
       }
@@ -772,10 +722,10 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
         for (int ph = 0; ph < 2; ++ph) {
           const int ox = ox0 + 16 * ph + c15;
           const bool ok = INTERIOR || (cok[ch] && oy < p.Hout && ox < p.Wout);
-          const k_f32x4 v = acc[mb][ph][ch] * winv + add[ch];
-          const k_f32x4 x = xq[mb][ph];
+          const f32x4 v = acc[mb][ph][ch] * winv + add[ch];
+          const f32x4 x = xq[mb][ph];
           const unsigned m = mq[mb][ph];
-          k_f32x4 gq, gx;
+          f32x4 gq, gx;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float d = v[r];
@@ -784,14 +734,14 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
             float gg = d;
             if (!p.gb_plain && !(K32_GNB_DIAG & 1)) {
               const float u = fmaf(x[r], gsc[r], gsh[r]);
-              const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-u));   // (the forward's own sigmoid: silu_k)
+              const float sg = __builtin_amdgcn_rcpf(1.0f + __expf(-u));   // (the forward's own sigmoid: silu_fast)
               gg = d * (sg * (1.0f + u * (1.0f - sg)));     // d/du [u * sigmoid(u)]
             }
             gq[r] = gg;
             gx[r] = gg * xh;
           }
           if (ok) {
-            *reinterpret_cast<k_f32x4*>(p.out + obase + mb * rstride + ph * pstride + 16 * ch) = gq;
+            *reinterpret_cast<f32x4*>(p.out + obase + mb * rstride + ph * pstride + 16 * ch) = gq;
             s1[ch] += gq;
             s2[ch] += gx;
           }
@@ -809,6 +759,8 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
   if (p.part_out) {
     // Per-channel (sum, sumsq) of this wave's 4 x 32 pixels: the 16 lanes of a k group hold 16 values each
     // (value v = ch*8 + r*2 + stat); a halving butterfly over the pixel lanes leaves lane c15 with the total of value c15.
+    // (This tail and conv_up2_k32_kernel's agree statement for statement but for the partial's tile index.  They stay written out:
+    // moved into one function of fdsr_conv_dev.h -- by reference or by value -- the register allocation of 68 instantiations changed.)
     float vals[16];
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch)
@@ -887,12 +839,7 @@ __global__ void __launch_bounds__(512, 2) conv_up2_k32_kernel(const ConvParams p
   // source-resolution tiling; p.Hin/Win = source dims, p.Hout/Wout = 2x (as conv_up2_h_kernel)
   const int nco = p.Cout_pad / BN;
   const int tilesX = (p.Win + TW - 1) / TW, tilesY = (p.Hin + TH - 1) / TH;
-  int bid;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = b & 7, k = b >> 3;
-    bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k;
-  }
+  const int bid = xcd_block_id(blockIdx.x, gridDim.x);
   const int cot = bid % nco;
   int pt = bid / nco;
   const int py = pt & 1;
@@ -933,17 +880,17 @@ __global__ void __launch_bounds__(512, 2) conv_up2_k32_kernel(const ConvParams p
 #pragma unroll
     for (int i = 0; i < NIN; ++i) {
       if (NIN * RPP > NPIX && i == NIN - 1 && row0 + i * RPP >= NPIX) continue;
-      k_f32x4 v = IO::widen(rin[i]);
+      f32x4 v = IO::widen(rin[i]);
       const int sd = sbase + i * (RPP * ROWB) + 16 * ((q >> 1) ^ (int)((skeys >> (3 * i)) & 7u));
       if (PREC == PREC_F16X3) {
         if (p.sat_flag) sat_check(p.sat_flag, v, 65504.f);
+        // (split4_mix of fdsr_conv_dev.h written out: through the call the f16x3 instantiations took one more SGPR)
         const float lim = in_pix[i] >= 0 ? 65504.f : 0.f;
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = __builtin_amdgcn_fmed3f(v[e], -lim, lim);
-        typedef _Float16 h2t __attribute__((ext_vector_type(2)));
         uint2 hi, lo;
         {
-          const h2t h0 = {(_Float16)v[0], (_Float16)v[1]}, h1 = {(_Float16)v[2], (_Float16)v[3]};
+          const h2 h0 = {(_Float16)v[0], (_Float16)v[1]}, h1 = {(_Float16)v[2], (_Float16)v[3]};
           hi.x = __builtin_bit_cast(unsigned, h0);
           hi.y = __builtin_bit_cast(unsigned, h1);
         }
@@ -982,7 +929,7 @@ __global__ void __launch_bounds__(512, 2) conv_up2_k32_kernel(const ConvParams p
     if (NP == 2) xoff[c][NP - 1] = xoff[c][0] ^ 64;
   }
 
-  k_f32x4 acc[MB][2][2][2];   // [row][px][pixel half][cout half]
+  f32x4 acc[MB][2][2][2];   // [row][px][pixel half][cout half]
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
@@ -990,7 +937,7 @@ __global__ void __launch_bounds__(512, 2) conv_up2_k32_kernel(const ConvParams p
 #pragma unroll
       for (int ph = 0; ph < 2; ++ph)
 #pragma unroll
-        for (int ch = 0; ch < 2; ++ch) acc[mb][px][ph][ch] = k_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int ch = 0; ch < 2; ++ch) acc[mb][px][ph][ch] = f32x4{0.f, 0.f, 0.f, 0.f};
 
 #pragma unroll
   for (int sl = 0; sl < R; ++sl) load_w(0, sl);
@@ -1020,7 +967,7 @@ __global__ void __launch_bounds__(512, 2) conv_up2_k32_kernel(const ConvParams p
           for (int ch = 0; ch < 2; ++ch) {
             const uint4 xv = Xf[xs][ph][term == 0 ? NP - 1 : 0];
             const uint4 wv = Wf[ws][ch][term == 1 ? NP - 1 : 0];
-            acc[mb][px][ph][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(k_h8, wv), __builtin_bit_cast(k_h8, xv),
+            acc[mb][px][ph][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, wv), __builtin_bit_cast(h8, xv),
                                                                         acc[mb][px][ph][ch], 0, 0, 0);
           }
     } else {
@@ -1064,7 +1011,7 @@ __global__ void __launch_bounds__(512, 2) conv_up2_k32_kernel(const ConvParams p
   // ---- epilogue: out[2 (oy0 + row) + py][2 (ox0 + col) + px], + bias (+ temb), GroupNorm partials of the output ----
   const int cob = co0 + wn * 32 + 4 * g;
   const float winv = p.w_inv_scale_dev ? *p.w_inv_scale_dev : p.w_inv_scale;
-  k_f32x4 add[2];
+  f32x4 add[2];
   bool cok[2];
   const float* tembp = p.temb ? p.temb + (size_t)n * p.temb_stride + p.temb_off : p.bias;   // (all loads unconditional: see conv_k32_kernel)
   const float tmul = p.temb ? 1.f : 0.f;
@@ -1072,14 +1019,12 @@ __global__ void __launch_bounds__(512, 2) conv_up2_k32_kernel(const ConvParams p
   for (int ch = 0; ch < 2; ++ch) {
     const int co = cob + 16 * ch;
     cok[ch] = co < p.Cout;
-    const int cs = cok[ch] ? co : 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) add[ch][r] = p.bias[cs + r] + tmul * tembp[cs + r];
+    add[ch] = epi_add4<false>(p.bias, p.bias_r, tembp, tmul, cok[ch] ? co : 0);
   }
-  k_f32x4 s1[2], s2[2];
+  f32x4 s1[2], s2[2];
 #pragma unroll
-  for (int ch = 0; ch < 2; ++ch) s1[ch] = s2[ch] = k_f32x4{0.f, 0.f, 0.f, 0.f};
-  const bool out16 = prec_is16(PREC);     // bf16 / f16 mode: the upsample conv's output is a 16-bit activation
+  for (int ch = 0; ch < 2; ++ch) s1[ch] = s2[ch] = f32x4{0.f, 0.f, 0.f, 0.f};
+  constexpr bool OUT16 = prec_is16(PREC);   // bf16 / f16 mode: the upsample conv's output is a 16-bit activation
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
@@ -1091,18 +1036,14 @@ __global__ void __launch_bounds__(512, 2) conv_up2_k32_kernel(const ConvParams p
           const int sy = oy0 + wm + mb * WM, sx = ox0 + 16 * ph + c15;
           if (cok[ch] && sy < p.Hin && sx < p.Win) {
             const size_t idx = ((size_t)(n * p.Hout + 2 * sy + py) * p.Wout + 2 * sx + px) * p.Cout + cob + 16 * ch;
-            const k_f32x4 v = acc[mb][px][ph][ch] * winv + add[ch];
-            if (out16) {
-              *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p.out) + idx) = pack4_16<PREC>(v);
-            } else {
-              *reinterpret_cast<k_f32x4*>(p.out + idx) = v;
-            }
+            const f32x4 v = acc[mb][px][ph][ch] * winv + add[ch];
+            put4<PREC, OUT16>(p.out, idx, v);
             s1[ch] += v;
             s2[ch] += v * v;
           }
         }
   if (p.part_out) {
-    float vals[16];
+    float vals[16];   // (as conv_k32_kernel's tail)
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch)
 #pragma unroll

@@ -18,17 +18,11 @@
 //
 // Same ConvParams, same packed weights, same outputs and statistics layout ([N][tiles][C][2], one partial per strip segment) as the
 // other 16-bit kernels; launch_conv_h asks conv_strip_ok() first.
-#include "fdsr_kernels.h"
-#include "fdsr_act_io.h"
+#include "fdsr_conv_dev.h"
 
 #include <type_traits>
 
 namespace fdsr {
-
-typedef float s_f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned s_u32x4 __attribute__((ext_vector_type(4)));   // (native vectors: arrays of HIP's uint4 struct were left in scratch memory)
-typedef _Float16 s_h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 s_b8 __attribute__((ext_vector_type(8)));
 
 // compile-time loop: f(integral_constant<int, I>) for I in [I0, N) -- the step's slots and items are indexed by true constants (a
 // `#pragma unroll` over them gave up on the larger instantiations and left the weight fragments in scratch memory)
@@ -39,8 +33,6 @@ __device__ __forceinline__ void static_for(F&& f) {
     static_for<I + 1, N>(f);
   }
 }
-
-__device__ __forceinline__ float silu_s(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
 #ifndef STRIP_XS      // activation-fragment slots in registers: XS - 1 fragments ahead of their MFMAs
 #define STRIP_XS 4
@@ -135,10 +127,10 @@ template <> struct StripRaw<PREC_F16> {
   }
 };
 template <> struct StripRaw<PREC_F16X3> {
-  s_f32x4 a4, b4;
+  f32x4 a4, b4;
   __device__ __forceinline__ void load(const unsigned char* ptr) {
-    a4 = *reinterpret_cast<const s_f32x4*>(ptr);
-    b4 = *reinterpret_cast<const s_f32x4*>(ptr + 16);
+    a4 = *reinterpret_cast<const f32x4*>(ptr);
+    b4 = *reinterpret_cast<const f32x4*>(ptr + 16);
   }
   __device__ __forceinline__ void pair(int k, float& a, float& b) const {
     a = k < 2 ? a4[2 * k] : b4[2 * k - 4];
@@ -191,12 +183,7 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
   const int H = p.Hout, W = p.Wout;          // stride 1, padding 1: the input has the output's size (launcher)
 
   const int stripsX = W / SW, segs = (H + seg_rows - 1) / seg_rows;
-  int bid;
-  {   // consecutive strips on one XCD (as conv_k32_kernel)
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = b & 7, k = b >> 3;
-    bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k;
-  }
+  int bid = xcd_block_id(blockIdx.x, gridDim.x);   // consecutive strips on one XCD
   const int ncg = p.Cout / 64;               // groups of 64 output channels: one workgroup each (128-cout launches: two read the same rows)
   const int cg = bid % ncg;
   bid /= ncg;
@@ -227,7 +214,7 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
     const int c = 8 * (tid >> 2) + 2 * (tid & 3);
     const float* ps = p.gn_scale + (size_t)n * Cfg::CIN + c;
     const float* ph = p.gn_shift + (size_t)n * Cfg::CIN + c;
-    *reinterpret_cast<s_f32x4*>(gtab + 4 * tid) = s_f32x4{ps[0], ps[1], ph[0], ph[1]};
+    *reinterpret_cast<f32x4*>(gtab + 4 * tid) = f32x4{ps[0], ps[1], ph[0], ph[1]};
   }
   __syncthreads();
   // the two halo columns of a row (2 OPPt octs per tensor): wave w activates slice w (channels 2 w, 2 w + 1 of every oct) of both, lane
@@ -247,7 +234,7 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
 
   StripRaw<PREC> raw[3][NPM];        // three rows in flight: set = (row's step) % 3; passes of tensor 0, then of tensor 1
   StripRawPair<PREC> rawh[3][CAT ? 2 : 1];
-  s_u32x4 rraw[3][RIDER ? NPR : 1];    // the rider's raw row, 16 bytes per pass
+  u32x4 rraw[3][RIDER ? NPR : 1];    // the rider's raw row, 16 bytes per pass
   // Row iy of the input, re-fetched into the register set of the row just staged (the row three steps on): the strip reads every
   // input byte exactly once, so its loads are bound by what is in flight per CU.  Rows outside the image or past the segment are
   // fetched from a clamped row (cache hits) and zeroed when staged.
@@ -279,20 +266,20 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
     rb[0] = reinterpret_cast<const unsigned char*>(p.xr0) + (size_t)n * H * W * CR0_ * 2;
     rb[1] = CR1_ ? reinterpret_cast<const unsigned char*>(p.xr1) + (size_t)n * H * W * CR1_ * 2 : rb[0];
   }
-  auto load_rider = [&](int iy, s_u32x4* set, int r) __attribute__((always_inline)) {
+  auto load_rider = [&](int iy, u32x4* set, int r) __attribute__((always_inline)) {
     const int t = r < NR0 ? 0 : 1;
     const int hi = oy1 - 1, rr = iy < oy0 ? oy0 : (iy > hi ? hi : iy);      // (rider rows are the segment's output rows)
-    set[r] = *reinterpret_cast<const s_u32x4*>(rb[t] + ((unsigned)(rr * W) * (unsigned)((t ? CR1_ : CR0_) * 2) + rsrc[r]));
+    set[r] = *reinterpret_cast<const u32x4*>(rb[t] + ((unsigned)(rr * W) * (unsigned)((t ? CR1_ : CR0_) * 2) + rsrc[r]));
   };
   // GroupNorm apply + Swish (unet.py:89-101) + conversion, in SLICES of two channels (a slice is what the step schedule below places
   // between two MFMAs); a finished oct is written to its swizzled unit(s) of the slot
   struct Staged { unsigned hi[4]; unsigned lo[PREC == PREC_F16X3 ? 4 : 1]; };
   // ... in three stages, one behind each of a slot's three MFMA groups (an in-order wave issues the next MFMA only after the
   // vector instructions in front of it: one lump of ~17 behind three back-to-back MFMAs left the matrix pipe idle for their length).
-  // Same operations in the same order as silu_s(a * sc + sh): bit-identical.
+  // Same operations in the same order as silu_fast(a * sc + sh) (gn_act4 of fdsr_conv_dev.h, cut into the three stages): bit-identical.
   struct ActTmp { float y0, y1, t0, t1; };
   auto act_s0 = [&](float a, float b, const float* gt4, ActTmp& m) __attribute__((always_inline)) {   // GroupNorm apply, exponent argument
-    const s_f32x4 gt = *reinterpret_cast<const s_f32x4*>(gt4);
+    const f32x4 gt = *reinterpret_cast<const f32x4*>(gt4);
     m.y0 = a * gt[0] + gt[2];
     m.y1 = b * gt[1] + gt[3];
     m.t0 = m.y0 * -1.44269504088896340736f;
@@ -307,16 +294,9 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
   auto act_s2 = [&](const ActTmp& m, unsigned& hi, unsigned& lo) __attribute__((always_inline)) {    // Swish product, conversion
     const float a = (STRIP_DIAG & 4) ? m.y0 : m.y0 * m.t0, b = (STRIP_DIAG & 4) ? m.y1 : m.y1 * m.t1;
     if (PREC == PREC_F16X3) {
-      const float ca = __builtin_amdgcn_fmed3f(a, -65504.f, 65504.f), cb = __builtin_amdgcn_fmed3f(b, -65504.f, 65504.f);
-      typedef _Float16 h2t __attribute__((ext_vector_type(2)));
-      const h2t h = {(_Float16)ca, (_Float16)cb};
-      hi = __builtin_bit_cast(unsigned, h);
-      // lo = f16(fma(hi, -1, v)), rounded once (as fdsr_conv_k32.hip)
-      asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(ca));
-      asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(cb));
+      split2_mix(a, b, 65504.f, hi, lo);
     } else if (PREC == PREC_F16) {
-      typedef _Float16 h2t __attribute__((ext_vector_type(2)));
-      const h2t h = {(_Float16)a, (_Float16)b};
+      const h2 h = {(_Float16)a, (_Float16)b};
       hi = __builtin_bit_cast(unsigned, h);
     } else {
       typedef __bf16 b2t __attribute__((ext_vector_type(2)));
@@ -402,28 +382,19 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
     for (int kc = 0; kc < KCR; ++kc) xr[kc] = c15 * RRB + 16 * ((4 * kc + g) ^ strip_swz<RRB>(c15));
   }
 
-  s_f32x4 acc[3][NPH];
+  f32x4 acc[3][NPH];
 #pragma unroll
   for (int a = 0; a < 3; ++a)
 #pragma unroll
-    for (int ph = 0; ph < NPH; ++ph) acc[a][ph] = s_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int ph = 0; ph < NPH; ++ph) acc[a][ph] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // ---- epilogue: lane = pixel c15 (+ 16 ph) of the row, output channels cob .. cob + 3 ----
   const int cob = 64 * cg + 16 * w + 4 * g;     // (in the launch's Cout channels; inside this workgroup's 64: 16 w + 4 g)
-  s_f32x4 add;
-  {
-    const float* tembp = p.temb ? p.temb + (size_t)n * p.temb_stride + p.temb_off : p.bias;   // (unconditional loads)
-    const float tmul = p.temb ? 1.f : 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float a = p.bias[cob + r];
-      if (RIDER) a += p.bias_r[cob + r];
-      add[r] = a + tmul * tembp[cob + r];
-    }
-  }
+  const float* tembp = p.temb ? p.temb + (size_t)n * p.temb_stride + p.temb_off : p.bias;   // (unconditional loads)
+  const f32x4 add = epi_add4<RIDER>(p.bias, p.bias_r, tembp, p.temb ? 1.f : 0.f, cob);
   const float winv = p.w_inv_scale_dev ? *p.w_inv_scale_dev : p.w_inv_scale;
   constexpr int OSZ = Cfg::OSZ, NIT = Cfg::NIT, TILE = Cfg::TILE_BYTES;
-  s_f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
   // The finished row leaves through LDS: a wave owns 16 of the 64 output channels, so its accumulator layout reaches memory in
   // 32-byte pieces (bf16) -- and the residual arrives in the same pieces.  Measured at B = 64: the residual launches took 400 us
   // against 300 us with EITHER their residual loads OR their stores left out, at exactly the algorithmic HBM traffic: the load /
@@ -472,14 +443,14 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
     }
   };
   // one quad (pixel c15 + 16 ph of row oy, four output channels) of a finished row: residual from its tile, result into the row's tile
-  auto finish = [&](int oy, int ph, s_f32x4 a) __attribute__((always_inline)) {
-    s_f32x4 v = a * winv + add;
+  auto finish = [&](int oy, int ph, f32x4 a) __attribute__((always_inline)) {
+    f32x4 v = a * winv + add;
     if (HAS_RES) v += IO::widen(*reinterpret_cast<const Quad*>(rtile + (oy & 1) * TILE + aq + 16 * PB * ph));
     unsigned char* dst = otile + (oy & 1) * TILE + aq + 16 * PB * ph;
     if (OSZ == 2) {
       *reinterpret_cast<uint2*>(dst) = pack4_16<PREC>(v);   // (bf16: one v_cvt_pk_bf16_f32 per pair; f16: saturating)
     } else {
-      *reinterpret_cast<s_f32x4*>(dst) = v;
+      *reinterpret_cast<f32x4*>(dst) = v;
     }
     s1 += v;
     s2 += v * v;
@@ -497,11 +468,11 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
   // spread over the slots (Cfg::slot_of), so that no wave runs a long MFMA-free stretch.  EPI: the step runs the epilogue of a row
   // (steps >= 3 of a segment); FLUSH: it moves a row's tile to memory (steps >= 4).
   uint4 Xf[XS][NP];
-  auto mfma1 = [&](const uint4* wf, const uint4* xf, s_f32x4 c) __attribute__((always_inline)) -> s_f32x4 {
+  auto mfma1 = [&](const uint4* wf, const uint4* xf, f32x4 c) __attribute__((always_inline)) -> f32x4 {
     if (PREC == PREC_F16X3) {   // small terms first: lo(x) hi(w), hi(x) lo(w), hi(x) hi(w)
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(s_h8, wf[0]), __builtin_bit_cast(s_h8, xf[NP - 1]), c, 0, 0, 0);
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(s_h8, wf[NP - 1]), __builtin_bit_cast(s_h8, xf[0]), c, 0, 0, 0);
-      return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(s_h8, wf[0]), __builtin_bit_cast(s_h8, xf[0]), c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, wf[0]), __builtin_bit_cast(h8, xf[NP - 1]), c, 0, 0, 0);
+      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, wf[NP - 1]), __builtin_bit_cast(h8, xf[0]), c, 0, 0, 0);
+      return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, wf[0]), __builtin_bit_cast(h8, xf[0]), c, 0, 0, 0);
     }
     return mfma16_k32<PREC>(wf[0], xf[0], c);
   };
@@ -511,7 +482,7 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
     constexpr int A0 = (ROT + 1) % 3, A1 = ROT, A2 = (ROT + 2) % 3;
     StripRaw<PREC>* rset = raw[(ROT + 1) % 3];             // holds row iy + 1; re-filled with row iy + 4
     StripRawPair<PREC>* hset = rawh[(ROT + 1) % 3];
-    s_u32x4* rrs = rraw[(ROT + 1) % 3];
+    u32x4* rrs = rraw[(ROT + 1) % 3];
     unsigned char* cur = smem_s + (it & 1) * Cfg::SLOT_BYTES;
     unsigned char* nxt = smem_s + ((it & 1) ^ 1) * Cfg::SLOT_BYTES;
     unsigned char* rcur = smem_s + Cfg::RSLOT_OFF + (it & 1) * Cfg::RSLOT_BYTES;
@@ -549,7 +520,7 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
       } else if constexpr (j < J4) {
         constexpr int r = j - J3;
         if constexpr (last) {
-          *reinterpret_cast<s_u32x4*>(rnxt + rdst[r]) = rrs[r];
+          *reinterpret_cast<u32x4*>(rnxt + rdst[r]) = rrs[r];
           load_rider(iy + 4, rrs, r);
         }
       } else if constexpr (last) {
@@ -573,7 +544,7 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
       if constexpr (f < NF) {
         constexpr int ph = f % NPH, kc = (f / NPH) % KCH, kx = f / (NPH * KCH);
         constexpr bool fresh = kx == 0 && kc == 0;         // the first product of a new output row starts from zero
-        const s_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
         acc[A2][ph] = mfma1(Wf[2][kx][kc], Xf[f % XS], acc[A2][ph]);
         static_for<J0, J1e>([&](auto jc) __attribute__((always_inline)) { item(jc, S0{}); });
         if (STRIP_FENCE3) __builtin_amdgcn_sched_barrier(0);
@@ -600,7 +571,7 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
     // rows oy0 - 1 (staged here), oy0, oy0 + 1, oy0 + 2 in flight before the first step; the set of a row = its step % 3
     StripRaw<PREC> first[NPM];
     StripRawPair<PREC> firsth[CAT ? 2 : 1];
-    s_u32x4 firstr[RIDER ? NPR : 1];
+    u32x4 firstr[RIDER ? NPR : 1];
 #pragma unroll
     for (int q = 0; q < NPM; ++q) load_pass(oy0 - 1, first, q);
 #pragma unroll
@@ -631,7 +602,7 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
     for (int t = 0; t < (CAT ? 2 : 1); ++t) stage_halo(firsth[t], t, hok[t] && rok, smem_s, -1);
     if (RIDER) {
 #pragma unroll
-      for (int r = 0; r < NPR; ++r) *reinterpret_cast<s_u32x4*>(smem_s + Cfg::RSLOT_OFF + rdst[r]) = firstr[r];
+      for (int r = 0; r < NPR; ++r) *reinterpret_cast<u32x4*>(smem_s + Cfg::RSLOT_OFF + rdst[r]) = firstr[r];
     }
   }
   __syncthreads();
@@ -667,8 +638,8 @@ __global__ void __launch_bounds__(256, LB) conv_strip_kernel(const ConvParams p,
       for (int m = 8; m >= 1; m >>= 1) vals[e] += __shfl_xor(vals[e], m, 64);
     if (c15 == 0) {
       float* dst = p.part_out + (((size_t)n * (segs * stripsX) + seg * stripsX + sx) * p.Cout + cob) * 2;
-      *reinterpret_cast<s_f32x4*>(dst) = s_f32x4{vals[0], vals[1], vals[2], vals[3]};
-      *reinterpret_cast<s_f32x4*>(dst + 4) = s_f32x4{vals[4], vals[5], vals[6], vals[7]};
+      *reinterpret_cast<f32x4*>(dst) = f32x4{vals[0], vals[1], vals[2], vals[3]};
+      *reinterpret_cast<f32x4*>(dst + 4) = f32x4{vals[4], vals[5], vals[6], vals[7]};
     }
   }
 }

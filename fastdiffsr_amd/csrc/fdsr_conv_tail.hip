@@ -16,29 +16,23 @@
 //                     fp32 FMAs against LDS-broadcast weights: 2 400 VALU per input pixel, no faster than the padded MFMA tile.)
 // Arithmetic: both round like the other convs of their mode (f16x3: three MFMAs per product, fp32 accumulate).
 // Reductions (GroupNorm partials) in a fixed order: reruns are bitwise identical.
-#include "fdsr_kernels.h"
-#include "fdsr_act_io.h"
+#include "fdsr_conv_dev.h"
 
 namespace fdsr {
 
-typedef float t_f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 t_h8 __attribute__((ext_vector_type(8)));
-typedef __bf16 t_b8 __attribute__((ext_vector_type(8)));
-
 namespace {
 
-__device__ __forceinline__ float silu_t(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-
-// 8 fp32 -> the MFMA operand planes: f16x3: hi = f16(v), lo = f16(v - hi); bf16: one plane
+// 8 fp32 -> the MFMA operand planes: f16x3: hi = f16(v), lo = f16(v - hi); bf16: one plane.  (An eight-wide operand straight into
+// MFMA registers, fixed clamp: not split4_2step of fdsr_conv_dev.h, whose quads go to LDS with the padding folded into the clamp.)
 template <int PREC>
 __device__ __forceinline__ void to_planes(const float (&v)[8], uint4 (&pl)[PREC == PREC_F16X3 ? 2 : 1]) {
   if (PREC == PREC_F16) {          // one f16 plane (saturating)
-    t_h8 hi;
+    h8 hi;
 #pragma unroll
     for (int j = 0; j < 8; ++j) hi[j] = (_Float16)__builtin_amdgcn_fmed3f(v[j], -65504.f, 65504.f);
     pl[0] = __builtin_bit_cast(uint4, hi);
   } else if (PREC == PREC_F16X3) {
-    t_h8 hi, lo;
+    h8 hi, lo;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float c = __builtin_amdgcn_fmed3f(v[j], -65504.f, 65504.f);
@@ -48,7 +42,7 @@ __device__ __forceinline__ void to_planes(const float (&v)[8], uint4 (&pl)[PREC 
     pl[0] = __builtin_bit_cast(uint4, hi);
     pl[PREC == PREC_F16X3 ? 1 : 0] = __builtin_bit_cast(uint4, lo);
   } else {
-    t_b8 b;
+    b8 b;
 #pragma unroll
     for (int j = 0; j < 8; ++j) b[j] = (__bf16)v[j];
     pl[0] = __builtin_bit_cast(uint4, b);
@@ -111,7 +105,7 @@ __global__ void __launch_bounds__(256, 2) conv_in8_kernel(const ConvParams p, co
       }
       to_planes<PREC>(v, Wf[cb][i]);
     }
-  t_f32x4 bias4[NCB];
+  f32x4 bias4[NCB];
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -124,12 +118,12 @@ __global__ void __launch_bounds__(256, 2) conv_in8_kernel(const ConvParams p, co
     const int n = tile / per_img, tt = tile % per_img;
     const int ty = tt / tilesX, tx = tt % tilesX;
     const int oy0 = ty * IN_TH + 2 * wave, ox0 = tx * IN_TW;
-    t_f32x4 s1[NCB], s2[NCB];
+    f32x4 s1[NCB], s2[NCB];
 #pragma unroll
-    for (int cb = 0; cb < NCB; ++cb) s1[cb] = s2[cb] = t_f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int cb = 0; cb < NCB; ++cb) s1[cb] = s2[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
     // the six 32-byte gathers of two pixel groups (one row) first, then group by group: convert, multiply, store
     for (int half = 0; half < 2; ++half) {
-    t_f32x4 raw[2][3][2];
+    f32x4 raw[2][3][2];
     bool okm[2][3];
 #pragma unroll
     for (int gq = 0; gq < 2; ++gq) {
@@ -139,7 +133,7 @@ __global__ void __launch_bounds__(256, 2) conv_in8_kernel(const ConvParams p, co
         const int tap = 4 * i + g;
         const int iy = oy + tap / 3 - 1, ix = ox + tap % 3 - 1;
         const bool ok = tap < 9 && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;
-        const t_f32x4* src = reinterpret_cast<const t_f32x4*>(p.x0 + ((size_t)(n * p.Hin + (ok ? iy : 0)) * p.Win + (ok ? ix : 0)) * 8);
+        const f32x4* src = reinterpret_cast<const f32x4*>(p.x0 + ((size_t)(n * p.Hin + (ok ? iy : 0)) * p.Win + (ok ? ix : 0)) * 8);
         raw[gq][i][0] = src[0];
         raw[gq][i][1] = src[1];
         okm[gq][i] = ok;
@@ -158,9 +152,9 @@ __global__ void __launch_bounds__(256, 2) conv_in8_kernel(const ConvParams p, co
         if (PREC == PREC_F16X3 && p.sat_flag) { sat_check(p.sat_flag, raw[grp][i][0], 65504.f); sat_check(p.sat_flag, raw[grp][i][1], 65504.f); }
         to_planes<PREC>(v, Xf[i]);
       }
-      t_f32x4 acc[NCB];
+      f32x4 acc[NCB];
 #pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) acc[cb] = t_f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int cb = 0; cb < NCB; ++cb) acc[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -169,9 +163,9 @@ __global__ void __launch_bounds__(256, 2) conv_in8_kernel(const ConvParams p, co
           if (PREC == PREC_F16X3) {
             const uint4 w1 = Wf[cb][i][NP - 1];
             // small terms first: lo(x) hi(w), hi(x) lo(w), hi(x) hi(w)
-            acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(t_h8, w0), __builtin_bit_cast(t_h8, Xf[i][NP - 1]), acc[cb], 0, 0, 0);
-            acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(t_h8, w1), __builtin_bit_cast(t_h8, Xf[i][0]), acc[cb], 0, 0, 0);
-            acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(t_h8, w0), __builtin_bit_cast(t_h8, Xf[i][0]), acc[cb], 0, 0, 0);
+            acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, w0), __builtin_bit_cast(h8, Xf[i][NP - 1]), acc[cb], 0, 0, 0);
+            acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, w1), __builtin_bit_cast(h8, Xf[i][0]), acc[cb], 0, 0, 0);
+            acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, w0), __builtin_bit_cast(h8, Xf[i][0]), acc[cb], 0, 0, 0);
           } else {
             acc[cb] = mfma16_k32<PREC>(w0, Xf[i][0], acc[cb]);
           }
@@ -181,12 +175,9 @@ __global__ void __launch_bounds__(256, 2) conv_in8_kernel(const ConvParams p, co
         const size_t o = ((size_t)(n * p.Hout + oy) * p.Wout + ox) * Cout + 4 * g;
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
-          const t_f32x4 v = acc[cb] * winv + bias4[cb];
-          if (p.out_bf16) {
-            *reinterpret_cast<uint2*>(reinterpret_cast<unsigned short*>(p.out) + o + 16 * cb) = PREC == PREC_F16 ? pack4_16<PREC_F16>(v) : pack4_16<PREC_BF16>(v);
-          } else {
-            *reinterpret_cast<t_f32x4*>(p.out + o + 16 * cb) = v;
-          }
+          const f32x4 v = acc[cb] * winv + bias4[cb];
+          if (p.out_bf16) put4<PREC == PREC_F16 ? PREC_F16 : PREC_BF16, true>(p.out, o + 16 * cb, v);
+          else put4<PREC, false>(p.out, o + 16 * cb, v);
           s1[cb] += v;
           s2[cb] += v * v;
         }
@@ -355,16 +346,15 @@ __global__ void __launch_bounds__(256, NKS <= 2 ? 4 : 2) conv_out3_kernel(const 
     for (int i = 0; i < NKS; ++i) { rq[i][0] = rn[i][0]; rq[i][1] = rn[i][1]; }
     ok = okn;
     okn = fetch(grp + 4, rn);                                // the next group's rows are in flight while this one is multiplied
-    t_f32x4 acc[2] = {t_f32x4{0.f, 0.f, 0.f, 0.f}, t_f32x4{0.f, 0.f, 0.f, 0.f}};
+    f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int i = 0; i < NKS; ++i) {
       float v[8];
 #pragma unroll
       for (int hq = 0; hq < 2; ++hq) {
-        const t_f32x4 sc = *reinterpret_cast<const t_f32x4*>(gss + 32 * i + kq(g, hq));
-        const t_f32x4 sh = *reinterpret_cast<const t_f32x4*>(gss + C + 32 * i + kq(g, hq));
-        t_f32x4 x = IO::widen(rq[i][hq]) * sc + sh;
-        if (act) { x.x = silu_t(x.x); x.y = silu_t(x.y); x.z = silu_t(x.z); x.w = silu_t(x.w); }
+        const f32x4 sc = *reinterpret_cast<const f32x4*>(gss + 32 * i + kq(g, hq));
+        const f32x4 sh = *reinterpret_cast<const f32x4*>(gss + C + 32 * i + kq(g, hq));
+        const f32x4 x = gn_act4(IO::widen(rq[i][hq]), sc, sh, !act);
 #pragma unroll
         for (int e4 = 0; e4 < 4; ++e4) v[4 * hq + e4] = ok ? x[e4] : 0.f;      // zero padding applies to the ACTIVATED tensor
       }
@@ -373,9 +363,9 @@ __global__ void __launch_bounds__(256, NKS <= 2 ? 4 : 2) conv_out3_kernel(const 
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb) {
         if (PREC == PREC_F16X3) {
-          acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(t_h8, Wf[nb][i][0]), __builtin_bit_cast(t_h8, Xf[NP - 1]), acc[nb], 0, 0, 0);
-          acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(t_h8, Wf[nb][i][NP - 1]), __builtin_bit_cast(t_h8, Xf[0]), acc[nb], 0, 0, 0);
-          acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(t_h8, Wf[nb][i][0]), __builtin_bit_cast(t_h8, Xf[0]), acc[nb], 0, 0, 0);
+          acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, Wf[nb][i][0]), __builtin_bit_cast(h8, Xf[NP - 1]), acc[nb], 0, 0, 0);
+          acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, Wf[nb][i][NP - 1]), __builtin_bit_cast(h8, Xf[0]), acc[nb], 0, 0, 0);
+          acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, Wf[nb][i][0]), __builtin_bit_cast(h8, Xf[0]), acc[nb], 0, 0, 0);
         } else {
           acc[nb] = mfma16_k32<PREC>(Wf[nb][i][0], Xf[0], acc[nb]);
         }

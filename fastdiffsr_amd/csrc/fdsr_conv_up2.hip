@@ -14,17 +14,9 @@
 // a wave owns 32 channels and TH/WM source rows and holds the 8 (px,a,b) weight fragments of the
 // current 16-channel chunk (hi|lo) in 64 VGPRs; per source row it reads 6 A fragments (2 rows x 3
 // column shifts) that feed the 8 tap-products; accumulators: [row][px].
-#include "fdsr_kernels.h"
-#include "fdsr_act_io.h"
+#include "fdsr_conv_dev.h"
 
 namespace fdsr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b4 __attribute__((ext_vector_type(4)));
 
 template <int TH, int WN, int PREC>
 struct ConvUp2Cfg {
@@ -56,12 +48,7 @@ __global__ void __launch_bounds__(512, 2) conv_up2_h_kernel(const ConvParams p) 
   // source-resolution tiling; p.Hin/Win = source dims, p.Hout/Wout = 2x
   const int nco = p.Cout_pad / BN;
   const int tilesX = (p.Win + TW - 1) / TW, tilesY = (p.Hin + TH - 1) / TH;
-  int bid;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = b & 7, k = b >> 3;
-    bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k;
-  }
+  const int bid = xcd_block_id(blockIdx.x, gridDim.x);
   const int cot = bid % nco;
   int pt = bid / nco;
   const int py = pt & 1;          // the two row parities of a source tile are neighbours (shared input in L2)
@@ -101,11 +88,8 @@ __global__ void __launch_bounds__(512, 2) conv_up2_h_kernel(const ConvParams p) 
       unsigned char* dst = buf + (row0 + i * RPP) * ROWB + q * 8;
       if (PREC == PREC_F16X3) {
         if (p.sat_flag) sat_check(p.sat_flag, v, 65504.f);   // raw input (no GroupNorm in front of the upsample conv)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = __builtin_amdgcn_fmed3f(v[e], -lim, lim);   // padding: lim = 0
-        h4 hi = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
-        h4 lo = {(_Float16)(v.x - (float)hi.x), (_Float16)(v.y - (float)hi.y), (_Float16)(v.z - (float)hi.z),
-                 (_Float16)(v.w - (float)hi.w)};
+        h4 hi, lo;
+        split4_2step(v, lim, hi, lo);   // padding: lim = 0
         *reinterpret_cast<h4*>(dst) = hi;
         *reinterpret_cast<h4*>(dst + 32) = lo;
       } else {
@@ -188,12 +172,9 @@ __global__ void __launch_bounds__(512, 2) conv_up2_h_kernel(const ConvParams p) 
   const int co = co0 + wn * 32 + r31;
   const bool cok = co < p.Cout;
   const float winv = p.w_inv_scale_dev ? *p.w_inv_scale_dev : p.w_inv_scale;   // device value: forms re-packed after optimiser steps
-  float add;
-  {   // unconditional loads (clamped channel, noise shift through a 0 / 1 factor)
-    const int cs = cok ? co : 0;
-    const float* tembp = p.temb ? p.temb + (size_t)n * p.temb_stride + p.temb_off : p.bias;
-    add = p.bias[cs] + (p.temb ? 1.f : 0.f) * tembp[cs];
-  }
+  // unconditional loads (clamped channel, noise shift through a 0 / 1 factor)
+  const float* tembp = p.temb ? p.temb + (size_t)n * p.temb_stride + p.temb_off : p.bias;
+  const float add = epi_add1<false>(p.bias, p.bias_r, tembp, p.temb ? 1.f : 0.f, cok ? co : 0);
   float s1 = 0.f, s2 = 0.f;
   const bool interior = (oy0 + TH <= p.Hin) && (ox0 + TW <= p.Win) && (co0 + BN <= p.Cout);
   if (interior) {
@@ -228,6 +209,7 @@ __global__ void __launch_bounds__(512, 2) conv_up2_h_kernel(const ConvParams p) 
         }
   }
   if (p.part_out) {
+    // (the fold of conv_mfma_h_kernel; only the partial's tile index differs)
     float* sp = reinterpret_cast<float*>(smem_u);   // halo buffers are free after the last barrier
     s1 += __shfl_xor(s1, 32, 64);
     s2 += __shfl_xor(s2, 32, 64);

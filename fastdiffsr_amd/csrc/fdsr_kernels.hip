@@ -17,21 +17,12 @@
 //     residual, stored NHWC (each lane owns one output channel: 128-B segments)
 // Everything else on the path (GroupNorm statistics, CLAM/SLAM, the posterior
 // update, layout changes at the boundary) is HBM-bound streaming code.
-#include "fdsr_kernels.h"
-#include "fdsr_act_io.h"
+#include "fdsr_conv_dev.h"
 #include "fdsr_philox.h"
 
 #include <string>
 
 namespace fdsr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float silu_f(float v) {
-  // x * sigmoid(x) (unet.py:57-59); v_exp_f32 + v_rcp_f32, ~3e-7 relative
-  return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v));
-}
 
 // ---------------------------------------------------------------------------
 // convolution
@@ -79,12 +70,7 @@ __global__ void __launch_bounds__(256, 2) conv_mfma_f32_kernel(const ConvParams 
   // one pixel tile and neighbouring pixel tiles are dealt to the same XCD (L2) ----
   const int nco = p.Cout_pad / BN;
   const int tilesX = (p.Wout + TW - 1) / TW, tilesY = (p.Hout + TH - 1) / TH;
-  int bid;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = b & 7, k = b >> 3;
-    bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k;
-  }
+  const int bid = xcd_block_id(blockIdx.x, gridDim.x);
   const int cot = bid % nco;
   int pt = bid / nco;
   const int tx = pt % tilesX;
@@ -158,8 +144,7 @@ __global__ void __launch_bounds__(256, 2) conv_mfma_f32_kernel(const ConvParams 
       if (in_pix[i] == -2) continue;
       f32x4 v = rin[i];
       if (gn && in_pix[i] >= 0) {   // conv zero-pads the ACTIVATED tensor
-        v = v * sc + sh;
-        if (!p.gn_plain) { v.x = silu_f(v.x); v.y = silu_f(v.y); v.z = silu_f(v.z); v.w = silu_f(v.w); }
+        v = gn_act4(v, sc, sh, p.gn_plain);
         if (p.drop_mask) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = ((rmask[i] >> (8 * e)) & 0xffu) ? v[e] * p.drop_scale : 0.f;
@@ -1345,7 +1330,7 @@ __global__ void __launch_bounds__(256) pool2_kernel(const float* __restrict__ x,
       if (sc) {
         v = v * a + b;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = silu_f(v[e]);
+        for (int e = 0; e < 4; ++e) v[e] = silu_fast(v[e]);
       }
       acc += v;
     }

@@ -10,6 +10,7 @@
 // Every reduction is ordered: a step is bitwise reproducible.
 #include "fdsr_train.h"
 #include "fdsr_train_dev.h"
+#include "fdsr_conv_dev.h"
 
 #include <algorithm>
 #include <climits>
@@ -265,7 +266,6 @@ __global__ void __launch_bounds__(256) wgrad_fold_kernel(const float* __restrict
 // 4-pixel x 16-channel block and every lane receives one channel's 4 pixels), two reads per operand half.  A tap only
 // changes the FIRST ROW of the B block, so there is no alignment problem and no shifted copy.  Rows are 128 B; the two
 // 64-byte halves of a row are swapped on rows with bit 1 set, which makes the 4-row blocks bank-conflict free.
-typedef _Float16 th8 __attribute__((ext_vector_type(8)));
 typedef short ts4 __attribute__((ext_vector_type(4)));
 
 template <int KS, int STRIDE, bool UP>
@@ -279,7 +279,7 @@ __device__ __forceinline__ int tr_img_off(int row, int col) {   // byte offset o
   return row * 128 + ((col ^ (((row >> 1) & 1) << 5)) << 1);
 }
 
-__device__ __forceinline__ th8 tr_frag(const unsigned char* plane, int row0, int row_step, int col) {
+__device__ __forceinline__ h8 tr_frag(const unsigned char* plane, int row0, int row_step, int col) {
   // 8 k-values of this lane: rows row0 + {0..3} * row_step (first read) and row0 + {4..7} * row_step (second read);
   // lane 4q+p of its 16-lane group supplies the address of row q, columns col .. col+3 (col already includes 4p)
   typedef ts4 __attribute__((address_space(3))) * lds_ts4;
@@ -288,7 +288,7 @@ __device__ __forceinline__ th8 tr_frag(const unsigned char* plane, int row0, int
   const ts4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ts4)(plane + tr_img_off(row0 + (4 + q) * row_step, col)));
   typedef short ts8 __attribute__((ext_vector_type(8)));
   const ts8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(th8, v);
+  return __builtin_bit_cast(h8, v);
 }
 
 template <int KS, int STRIDE, bool UP>
@@ -396,13 +396,13 @@ __global__ void __launch_bounds__(256, 2) wgrad_h_kernel(const WgradParams p, co
     if (tile + 1 < k.t1) prefetch(tile + 1);
 #pragma unroll 1
     for (int y = 0; y < TH; ++y) {                          // one K-step = one 16-pixel tile row
-      const th8 ah = tr_frag(sDyH, y * TW + k0, 1, colA);
-      const th8 al = tr_frag(sDyL, y * TW + k0, 1, colA);
+      const h8 ah = tr_frag(sDyH, y * TW + k0, 1, colA);
+      const h8 al = tr_frag(sDyL, y * TW + k0, 1, colA);
 #pragma unroll
       for (int t = 0; t < T; ++t) {
         const int rb = (y * STRIDE + t / KS) * HWD + k0 * STRIDE + (t % KS);
-        const th8 bh = tr_frag(sInH, rb, STRIDE, colB);
-        const th8 bl = tr_frag(sInL, rb, STRIDE, colB);
+        const h8 bh = tr_frag(sInH, rb, STRIDE, colB);
+        const h8 bl = tr_frag(sInL, rb, STRIDE, colB);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[t], 0, 0, 0);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[t], 0, 0, 0);
         acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[t], 0, 0, 0);
@@ -442,31 +442,19 @@ struct WgH8Cfg {
   static_assert(LDS_BYTES <= 160 * 1024 && LDS_BYTES_INROW <= 160 * 1024, "LDS budget");
 };
 
-__device__ __forceinline__ th8 tr_frag_at(const unsigned char* a) {   // two transposing reads: rows +0..3 and +4..7 of this lane's block
+__device__ __forceinline__ h8 tr_frag_at(const unsigned char* a) {   // two transposing reads: rows +0..3 and +4..7 of this lane's block
   typedef ts4 __attribute__((address_space(3))) * lds_ts4;
   typedef short ts8 __attribute__((ext_vector_type(8)));
   const ts4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ts4)(a));
   const ts4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ts4)(a + 4 * 128));   // row + 4: same swizzle
   const ts8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(th8, v);
+  return __builtin_bit_cast(h8, v);
 }
 
-// hi = rn_f16(clamp(v)), lo = rn_f16(v - hi) (22 mantissa bits, as fdsr_conv_h.hip): one packed convert and two
-// v_fma_mix per pair, lo = f16(fma(hi, -1, v)) rounded once.  lim = 0 zero-pads.
+// the f16x3 split of a quad (split4_mix, fdsr_conv_dev.h) into the two planes of a staging buffer.  lim = 0 zero-pads.
 __device__ __forceinline__ void put_split(unsigned char* ph, unsigned char* pl, f32x4 v, float lim) {
-  typedef _Float16 h2t __attribute__((ext_vector_type(2)));
-#pragma unroll
-  for (int e = 0; e < 4; ++e) v[e] = __builtin_amdgcn_fmed3f(v[e], -lim, lim);
   uint2 hi, lo;
-  {
-    const h2t h0 = {(_Float16)v[0], (_Float16)v[1]}, h1 = {(_Float16)v[2], (_Float16)v[3]};
-    hi.x = __builtin_bit_cast(unsigned, h0);
-    hi.y = __builtin_bit_cast(unsigned, h1);
-  }
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lo.x) : "v"(hi.x), "v"(v[0]));
-  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo.x) : "v"(hi.x), "v"(v[1]));
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(lo.y) : "v"(hi.y), "v"(v[2]));
-  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo.y) : "v"(hi.y), "v"(v[3]));
+  split4_mix(v, lim, hi, lo);
   *reinterpret_cast<uint2*>(ph) = hi;
   *reinterpret_cast<uint2*>(pl) = lo;
 }
@@ -490,9 +478,9 @@ __device__ __forceinline__ void h8_set_tile(H8At& s, const WgradParams& p, const
 template <class Cfg>
 __device__ __forceinline__ void h8_mfma_row(f32x16 (&acc)[Cfg::T], int baseA, const int (&baseB)[4], const unsigned char* cur, int y) {
   constexpr int KS = Cfg::KS, T = Cfg::T, TW = Cfg::TW, HWD = Cfg::HWD;
-  const th8 ah = tr_frag_at(cur + baseA + y * TW * 128);
-  const th8 al = tr_frag_at(cur + baseA + y * TW * 128 + Cfg::PLANE_DY);
-  th8 bh[2], bl[2];
+  const h8 ah = tr_frag_at(cur + baseA + y * TW * 128);
+  const h8 al = tr_frag_at(cur + baseA + y * TW * 128 + Cfg::PLANE_DY);
+  h8 bh[2], bl[2];
   bh[0] = tr_frag_at(cur + baseB[(y * HWD) & 3] + y * HWD * 128);
   bl[0] = tr_frag_at(cur + baseB[(y * HWD) & 3] + y * HWD * 128 + Cfg::PLANE_IN);
 #pragma unroll

@@ -9,7 +9,7 @@ R=$(cd $(dirname $0)/.. && pwd); C=$R/fastdiffsr_amd/csrc; O=$C/ab; mkdir -p $O
 B=$(basename $F .hip)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -std=c++17 -fPIC -Wno-unused-result -O3 -fno-slp-vectorize "$@" -c $C/$B.hip -o $O/${B}_$TAG.o
 OBJS=""
-for o in $C/*_hip.o $C/*_cpp.o; do
+for o in $C/*_hip.o $C/*_hip_part*.o $C/*_cpp.o; do   # (_part*: fdsr_conv_strip.hip compiles into three objects)
   if [ "$(basename $o)" = "${B}_hip.o" ]; then OBJS="$OBJS $O/${B}_$TAG.o"; else OBJS="$OBJS $o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-z,defs $OBJS -o $O/libfdsr_hip_$TAG.so
