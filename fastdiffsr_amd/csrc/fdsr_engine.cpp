@@ -846,6 +846,19 @@ int fdsr_debug_tensor(fdsr_handle h, const char* name, const float** dev_ptr, in
   return fail(h, FDSR_E_KEY, "no tensor named '%s'", name);
 }
 
+int fdsr_debug_gn_table(fdsr_handle h, const char* conv, const float** dev_ptr, int* n, int* ch) {
+  if (!h || !conv) return fail(h, FDSR_E_INVALID, "null argument");
+  if (!h->plan.bytes) return fail(h, FDSR_E_STATE, "no forward has run yet");
+  for (const Op& op : h->ops)
+    if (op.kind == Op::CONV && op.gn_slot >= 0 && op.name == conv) {
+      if (dev_ptr) *dev_ptr = reinterpret_cast<const float*>(h->plan.gn_off[op.gn_slot]);   // offset; caller adds the workspace base
+      if (n) *n = h->plan.N;
+      if (ch) *ch = op.C0 + op.C1;
+      return FDSR_OK;
+    }
+  return fail(h, FDSR_E_KEY, "no GroupNorm'ed convolution named '%s'", conv);
+}
+
 int fdsr_debug_tensor_elem_bytes(fdsr_handle h, const char* name, int* bytes) {
   if (!h || !name || !bytes) return fail(h, FDSR_E_INVALID, "null argument");
   for (size_t t = 0; t < h->tensors.size(); ++t)

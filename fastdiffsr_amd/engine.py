@@ -403,6 +403,15 @@ class Engine:
             flat = self._ws[o:o + 4 * cnt].view(torch.float32)
         return flat.view(n.value, hh.value, ww.value, ch.value).permute(0, 3, 1, 2).contiguous()
 
+    def debug_gn_table(self, conv):
+        """(scale, shift), each [N, C] fp32: the GroupNorm table convolution op `conv` applied in the last forward"""
+        off = C.c_void_p()
+        n, ch = C.c_int(), C.c_int()
+        _lib.check(self.h, self.lib.fdsr_debug_gn_table(self.h, conv.encode(), C.byref(off), C.byref(n), C.byref(ch)))
+        o, cnt = int(off.value or 0), n.value * ch.value
+        t = self._ws[o:o + 8 * cnt].view(torch.float32).view(2, n.value, ch.value)
+        return t[0].clone(), t[1].clone()
+
     def profile_begin(self):
         _lib.check(self.h, self.lib.fdsr_profile_begin(self.h))
 

@@ -595,6 +595,10 @@ int fdsr_debug_tensor(fdsr_handle h, const char* name, const float** dev_ptr,
 /* Element size of that tensor in the workspace: 4 (fp32), or 2 in bf16 mode, which keeps every
  * activation but the packed input and eps as bf16 in HBM. */
 int fdsr_debug_tensor_elem_bytes(fdsr_handle h, const char* name, int* bytes);
+/* The GroupNorm table the convolution op `conv` ("<p>.res_block.block1", "<p>.res_block.block2", "final_conv") applied in the last
+ * forward: fp32 scale [n][ch] followed by shift [n][ch] (y = x * scale + shift in front of the Swish), as an offset into the
+ * workspace like fdsr_debug_tensor.  A launch that formed its scale / shift itself (option "gn_consumer") leaves the table unwritten. */
+int fdsr_debug_gn_table(fdsr_handle h, const char* conv, const float** dev_ptr, int* n, int* ch);
 /* Timing hooks: record hipEvents on `stream` around every launch of the
  * dominant kernel family (the 3x3 MFMA convolutions) during the next calls,
  * then read back count / total milliseconds / algorithmic FLOPs. */

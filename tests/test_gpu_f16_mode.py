@@ -9,7 +9,8 @@ f16 activations in HBM: the bf16 mode's kernels, bytes and MFMA rate with 11 man
     permutation bitwise;
   * values beyond the f16 range saturate instead of turning into inf;
   * the siblings (SR3, TESR, GDP): their attention kernels' f16 twins, a loop against f16x3 beside bf16.
-The trained-like-weights figure (0.19 dB for bf16) is in tests/test_gpu_trained_weights.py."""
+The trained-like-weights figure (0.19 dB for bf16) is in tests/test_gpu_trained_weights.py.
+(The bf16 / f16 kernels are judged per operator and per element against the modes' own arithmetic in tests/test_gpu_unet_16bit_layerwise.py.)"""
 import math
 
 import numpy as np

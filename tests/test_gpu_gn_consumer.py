@@ -6,7 +6,8 @@ pairs of the groups its K slice touches and forms scale / shift itself in its pr
 
 Here: layer by layer against the oracle with the form on (the default) and against the same forward with it off (the gn_finalize
 launches back): B = 1 and B = 2 maps whose launches split K, concatenated inputs whose groups cross the concat seam (384 channels =
-32 groups of 12), riders, both 16-bit modes; bitwise reruns; the 20-step loop eager and as a replayed graph."""
+32 groups of 12), riders, both 16-bit modes; bitwise reruns; the 20-step loop eager and as a replayed graph.
+(The bf16 / f16 kernels are judged per operator and per element against the modes' own arithmetic in tests/test_gpu_unet_16bit_layerwise.py.)"""
 import pytest
 import torch
 

@@ -3,7 +3,8 @@
 the split-K, partial-tile and rider paths of the form all run), layer by layer against the oracle, in every option setting
 (bits of `k32`: 1 f16x3, 2 bf16, 4 the 16-row tile with a rider, 8 the 2-row tiles of small grids, 16 the sub-pixel upsample convs, 32 / 128 the small-workgroup form of the 64-cout tiles in f16x3 / bf16, 64 / 512 with a rider (rider chunks first), 1024 the 8-wave rider kernels rider-first too; default 1275), against the 32x32x16 kernels on the same input, and through the
 20-step loop.  Same bounds as every other conv kernel: layerwise 1e-4 * max(1, |ref|), loop 1e-3 (north_star); bf16 0.04 layerwise
-(judged on PSNR elsewhere).  Reference: fastdiffsr_modules/unet.py:89-120."""
+(judged on PSNR elsewhere).  Reference: fastdiffsr_modules/unet.py:89-120.
+(The bf16 / f16 kernels are judged per operator and per element against the modes' own arithmetic in tests/test_gpu_unet_16bit_layerwise.py.)"""
 import pytest
 import torch
 

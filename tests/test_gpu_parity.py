@@ -259,7 +259,8 @@ def test_precision_modes_layerwise_and_loop(full, golden_dir, prec, tol_fwd, tol
     """16-bit MFMA convolutions: f16x3 (hi/lo split, fp32-grade) must stay inside the fp32
     parity bounds; bf16 is judged on PSNR (north_star: PSNR within 0.01 dB), not on 1e-3 -- but its layers must stay within
     3 % of the layer's range (measured worst 1.1 %: bf16 has 8 mantissa bits, 2^-9 = 0.2 % per rounding) and the loop's output
-    within 50 dB of the oracle's (a bound that CAN fail: the PSNR-against-HR difference below cannot, at a random-init network's 13 dB)."""
+    within 50 dB of the oracle's (a bound that CAN fail: the PSNR-against-HR difference below cannot, at a random-init network's 13 dB).
+    (The bf16 / f16 kernels are judged per operator and per element against the modes' own arithmetic in tests/test_gpu_unet_16bit_layerwise.py.)"""
     from oracle import fdsr_oracle as O
     cfg, eng, sd = full
     eng.set_precision(prec)

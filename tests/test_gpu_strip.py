@@ -5,7 +5,8 @@ registers, one input row per step, three output rows per fragment read).  Large 
 size: layer by layer against the oracle (maps 128 x 128 and 64 x 192: one and three strips per row, segments
 of 16 .. 128 rows, image borders on both sides of a strip), against the tile kernels on the same input, bitwise reruns, the 20-step
 loop eager and as a hipGraph.  Same bounds as every other conv kernel: layerwise 1e-4 * max(1, |ref|) in f16x3, 0.04 in bf16 (measured worst 0.011) (judged
-on PSNR elsewhere), loop 1e-3 (north_star).  Reference: fastdiffsr_modules/unet.py:89-120."""
+on PSNR elsewhere), loop 1e-3 (north_star).  Reference: fastdiffsr_modules/unet.py:89-120.
+(The bf16 / f16 kernels are judged per operator and per element against the modes' own arithmetic in tests/test_gpu_unet_16bit_layerwise.py.)"""
 import pytest
 import torch
 

@@ -1,7 +1,8 @@
 """The two ends of the UNet on their own kernels in the 16-bit modes (csrc/fdsr_conv_tail.hip): downs.0 (Conv3x3 6 -> inner on the
 packed NHWC-8 input: gather + 16x16x32 MFMA, no LDS; reference unet.py:243) and final_conv (GroupNorm -> Swish -> Conv3x3 inner -> 3
 as fp32 FMAs in scatter form; unet.py:293).  Layer by layer against the oracle on ragged maps (partial tiles in both directions), against
-the general kernels on the same input (option `tail` = 0), bitwise reruns, other widths (inner 32 / 48 / 64), the loop."""
+the general kernels on the same input (option `tail` = 0), bitwise reruns, other widths (inner 32 / 48 / 64), the loop.
+(The bf16 / f16 kernels are judged per operator and per element against the modes' own arithmetic in tests/test_gpu_unet_16bit_layerwise.py.)"""
 import pytest
 import torch
 
