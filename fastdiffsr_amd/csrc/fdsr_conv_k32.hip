@@ -114,6 +114,9 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
   constexpr int TW = Cfg::TW, KC = Cfg::KC, NP = Cfg::NP, ROWB = Cfg::ROWB, HWD = Cfg::HWD, NPIX = Cfg::NPIX;
   constexpr int WM = Cfg::WM, BN = Cfg::BN, MB = Cfg::MB, RPP = Cfg::RPP, NIN = Cfg::NIN, R = Cfg::R, XS = Cfg::XS;
   constexpr bool PIN = TH == 16 ? K32_PIN16 != 0 : K32_PIN != 0;
+  // f16x3: one dependent MFMA chain per accumulator (mfma_step).  Not in the unpinned 16-row tile nor in the 8-wave kernels that run their
+  // rider chunks last: there the fences of the chain order cost registers or scratch, and no launch of the sampling loop takes them.
+  constexpr bool CHAIN = PIN && !(RIDER && !RF);
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_k[];
   unsigned char* sBuf0 = smem_k;
@@ -405,18 +408,20 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
   };
   auto mfma_step = [&](int xs, int ws, int mb) __attribute__((always_inline)) {
     if (PREC == PREC_F16X3) {
-      // small terms first: lo(x) hi(w), hi(x) lo(w), hi(x) hi(w); four independent accumulators between dependent MFMAs
+      // Small terms first: lo(x) hi(w), hi(x) lo(w), hi(x) hi(w).  CHAIN: the three MFMAs of ONE accumulator issue back to back, then
+      // the next accumulator's.  A dependent chain of this instruction issues at full rate (MI355X_MICROARCH.md, cycle constants), and
+      // the loop is power-bound: with the result consumed by the next instruction the kernels hold a 2 - 4 % higher clock at 1 - 3 %
+      // more wave cycles (EXPERIMENTS.md, "One dependent MFMA chain per accumulator").  Otherwise term-major: four accumulators in turn.
+      // Either way an accumulator receives the same addends in the same order.
 #pragma unroll
-      for (int term = 0; term < 3; ++term)
-#pragma unroll
-        for (int ph = 0; ph < 2; ++ph)
-#pragma unroll
-          for (int ch = 0; ch < 2; ++ch) {
-            const uint4 xv = Xf[xs][ph][term == 0 ? NP - 1 : 0];
-            const uint4 wv = Wf[ws][ch][term == 1 ? NP - 1 : 0];
-            acc[mb][ph][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, wv), __builtin_bit_cast(h8, xv),
-                                                                    acc[mb][ph][ch], 0, 0, 0);
-          }
+      for (int i = 0; i < 12; ++i) {
+        const int a = CHAIN ? i / 3 : i % 4, term = CHAIN ? i % 3 : i / 4, ph = a >> 1, ch = a & 1;
+        const uint4 xv = Xf[xs][ph][term == 0 ? NP - 1 : 0];
+        const uint4 wv = Wf[ws][ch][term == 1 ? NP - 1 : 0];
+        acc[mb][ph][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, wv), __builtin_bit_cast(h8, xv),
+                                                                acc[mb][ph][ch], 0, 0, 0);
+        if (CHAIN && term == 2) __builtin_amdgcn_sched_barrier(0);   // (the scheduler otherwise interleaves the four chains again)
+      }
     } else {
 #pragma unroll
       for (int ph = 0; ph < 2; ++ph)
@@ -958,18 +963,20 @@ __global__ void __launch_bounds__(512, 2) conv_up2_k32_kernel(const ConvParams p
   };
   auto mfma_step = [&](int xs, int slot, int mb) {
     const int px = slot >> 2, ws = slot % R;
-    if (PREC == PREC_F16X3) {
+    if (PREC == PREC_F16X3) {   // one dependent chain per accumulator, small terms first (as conv_k32_kernel's CHAIN order)
 #pragma unroll
-      for (int term = 0; term < 3; ++term)
+      for (int ph = 0; ph < 2; ++ph)
 #pragma unroll
-        for (int ph = 0; ph < 2; ++ph)
+        for (int ch = 0; ch < 2; ++ch) {
 #pragma unroll
-          for (int ch = 0; ch < 2; ++ch) {
+          for (int term = 0; term < 3; ++term) {
             const uint4 xv = Xf[xs][ph][term == 0 ? NP - 1 : 0];
             const uint4 wv = Wf[ws][ch][term == 1 ? NP - 1 : 0];
             acc[mb][px][ph][ch] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, wv), __builtin_bit_cast(h8, xv),
                                                                         acc[mb][px][ph][ch], 0, 0, 0);
           }
+          __builtin_amdgcn_sched_barrier(0);
+        }
     } else {
 #pragma unroll
       for (int ph = 0; ph < 2; ++ph)
