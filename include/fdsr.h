@@ -536,6 +536,39 @@ int fdsr_u8_to_tensor(fdsr_handle h, const uint8_t* src_nhwc, float* dst_nchw, i
 int fdsr_resize_bicubic_u8(fdsr_handle h, const uint8_t* src_nhwc, int batch, int in_h, int in_w, int out_h,
                            int out_w, uint8_t* tmp, uint8_t* dst_u8_nhwc, float* dst_f32_nchw, void* hip_stream);
 
+/* -- whole-scene tiling (fastdiffsr_amd/scene.py; DESIGN "Whole-scene sampling") ------------- */
+/* A scene larger than the network takes in one call is sampled as square tiles of `tile` x `tile` pixels that overlap, and the
+ * sampled tiles are blended back with separable linear ramps.  The three calls below are the device side; which tiles there are is
+ * the caller's plan, handed over as two device tables of int32:
+ *   origins [n][2]  (y0, x0) of tile i in the scene; 0 <= y0 <= SH - tile, 0 <= x0 <= SW - tile
+ *   ramps   [n][4]  (top, left, bottom, right): over how many pixels the tile's weight ramps up from that side (0: full weight
+ *                   up to the border), each in [0, tile]
+ * A tile whose origin lies outside these bounds is skipped by every kernel (nothing is read or written for it); ramp lengths are
+ * clamped to [0, tile].  Tables are read when the kernels run: keep them alive and unchanged until then.  h may be NULL.
+ *
+ * fdsr_scene_gather cuts the tiles' inputs out of scene-sized arrays:
+ *   scene_u8 [SH,SW,3] uint8 (the upscaled scene)          -> cond  [n,3,tile,tile] fp32, fdsr_u8_to_tensor's arithmetic with
+ *                                                             (lo, hi) = (-1, 1): ToTensor() * 2 - 1, bit for bit
+ *   field    [planes,3,SH,SW] fp32 or NULL (a noise field) -> noise [planes,n,3,tile,tile], the layout fdsr_sample takes (copies)
+ * noise is required with a field and ignored without one. */
+int fdsr_scene_gather(fdsr_handle h, const uint8_t* scene_u8, const float* field, int planes, int scene_h, int scene_w,
+                      const int32_t* origins, int n_tiles, int tile, float* cond, float* noise, void* hip_stream);
+/* fdsr_scene_blend adds n sampled tiles [n,3,tile,tile] fp32 into acc [3,SH,SW] and wsum [SH,SW] (fp32; the caller zeroes both
+ * once per scene):   acc[c][y][x] = acc + fl(w * v),   wsum[y][x] = wsum + w,   w = fl32(wy(y) * wx(x)), where along an axis
+ *   w1(i) = (i < lead ? (i + 1) / (lead + 1) : 1) * (i >= tile - trail ? (tile - i) / (trail + 1) : 1)       i = 0 .. tile - 1
+ * with (lead, trail) = (top, bottom) for wy and (left, right) for wx, evaluated in fp64 and rounded to fp32 once as the product.
+ * Contract: tile i is one launch on hip_stream, in ascending i; inside a launch every scene pixel belongs to one thread; the
+ * product and each sum are single correctly rounded fp32 operations (no fma), and there are no floating-point atomics.  A scene
+ * pixel therefore receives its contributions in ascending tile index, whatever the grouping of tiles into calls (as long as the
+ * calls pass ascending tiles on one stream): the accumulators are bitwise reproducible and independent of the batching. */
+int fdsr_scene_blend(fdsr_handle h, const float* tiles, const int32_t* origins, const int32_t* ramps, int n_tiles, int tile,
+                     float* acc, float* wsum, int scene_h, int scene_w, void* hip_stream);
+/* fdsr_scene_finish: q = acc / wsum (one fp32 division) -> dst_f32 [3,SH,SW] and / or, through fdsr_tensor2img_u8's arithmetic
+ * with (lo, hi) = (-1, 1) (clamp, map to [0,1], * 255, round half to even), dst_u8 [SH,SW,3].  Either destination may be NULL,
+ * not both.  Every pixel must have been covered by a tile (wsum > 0). */
+int fdsr_scene_finish(fdsr_handle h, const float* acc, const float* wsum, int scene_h, int scene_w, uint8_t* dst_u8,
+                      float* dst_f32, void* hip_stream);
+
 /* f16x3 range guard.  The split-f16 arithmetic clamps every operand to +-65504.  GroupNorm'ed conv inputs are re-scaled
  * before the split, but a RAW input (ResnetBlock res_conv, Down/Upsample convs: unet.py:66-83,112) beyond that range would be
  * clamped silently; the kernels raise a sticky device flag instead.  This call synchronises `hip_stream`, reads and clears the

@@ -1,0 +1,141 @@
+"""Whole-scene sampling rate on the GPU: a synthetic 2048 x 2048 scene through scene.super_resolve_scene (tile 256, overlap 32,
+batch 16: 81 tiles = 5 groups of 16 and a last group of 1) against Engine.sample with explicit noise at B = 16 on the same tile
+shape (the scene's first group of tiles as its input), in one process, f16x3 and f16, in alternating windows.  The ratio is
+tiles/s of the scene over tiles/s of the bare sampler; the parts of a scene run (the noise field, one group's gather and blend, the facade call of a full group and of the last 1-tile group) are
+timed on their own so that a ratio below 1 can be attributed.
+
+    python tools/scene_timing.py [--out profiles/scene_timing.txt]
+
+Synthetic weights (synth.synth_state_dict, the flagship UNet); the cost does not depend on the weight values."""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SCENE, TILE, OVERLAP, BATCH = 2048, 256, 32, 16
+WINDOWS = 6        # per side; a window with a range-guard re-run in it is left out of the mean, so take a few more than three
+
+
+def facade():
+    from fastdiffsr_amd import networks
+    from fastdiffsr_amd.arch import FASTDIFFSR_SCHEDULE_VAL, FASTDIFFSR_UNET, UNetConfig
+    from fastdiffsr_amd.synth import synth_state_dict
+    u = FASTDIFFSR_UNET
+    dev = torch.device('cuda')
+    opt = {'phase': 'val', 'gpu_ids': [0], 'distributed': False, 'datasets': {'train': {'l_resolution': 64}},
+           'model': {'which_model_G': 'fastdiffsr', 'finetune_norm': False,
+                     'unet': {'in_channel': 6, 'out_channel': 3, 'inner_channel': u['inner_channel'], 'norm_groups': u['norm_groups'],
+                              'channel_multiplier': list(u['channel_mults']), 'attn_res': list(u['attn_res']),
+                              'res_blocks': u['res_blocks'], 'dropout': u['dropout']},
+                     'beta_schedule': {'train': dict(FASTDIFFSR_SCHEDULE_VAL), 'val': dict(FASTDIFFSR_SCHEDULE_VAL)},
+                     'diffusion': {'image_size': TILE, 'channels': 3, 'conditional': True}}}
+    netG = networks.define_G(opt).to(dev)
+    netG.set_loss(dev)
+    netG.set_new_noise_schedule(FASTDIFFSR_SCHEDULE_VAL, dev)
+    sd = synth_state_dict(UNetConfig(**dict(u, image_size=TILE)), 0)
+    ck = {'denoise_fn.' + k: torch.from_numpy(v) for k, v in sd.items()}
+    ck.update({k: v.cpu() for k, v in netG.state_dict().items() if not k.startswith('denoise_fn.')})
+    netG.load_state_dict(ck, strict=True)
+    netG.eval()
+    return netG
+
+
+def timed(fn, reps):
+    """Mean seconds of fn() over `reps` calls: host clock around work that ends in a device synchronise."""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'scene_timing.txt'))
+    a = ap.parse_args()
+    from fastdiffsr_amd import scene as S
+    from fastdiffsr_amd.engine import Engine
+    netG = facade()
+    eng = netG.denoise_fn.engine
+    g = torch.Generator(device='cuda').manual_seed(1)
+    scene = torch.randint(0, 256, (SCENE, SCENE, 3), dtype=torch.uint8, device='cuda', generator=g)
+    plan = S.plan_tiles(SCENE, SCENE, TILE, OVERLAP)
+    n = len(plan.origins)
+    origins, ramps = S.plan_tables(plan, 'cuda')
+    T = netG.num_timesteps
+    props = torch.cuda.get_device_properties(0)
+    lines = ['# python tools/scene_timing.py   (synthetic weights, synth.synth_state_dict(FASTDIFFSR_UNET, 0); T = %d)' % T,
+             '# gpu, as the runtime names it: %s, %s, %d CUs, %.0f GiB' % (props.name, getattr(props, 'gcnArchName', '?'),
+                                                                         props.multi_processor_count, props.total_memory / 2 ** 30),
+             '# scene %dx%d, tile %d, overlap %d, batch %d: %d tiles = %d groups of %d and a last group of %d; noise field %.2f GiB' % (
+                 SCENE, SCENE, TILE, OVERLAP, BATCH, n, n // BATCH, BATCH, n % BATCH, S.noise_field_bytes(T, SCENE, SCENE) / 2 ** 30)]
+    for prec in ('f16x3', 'f16'):
+        netG.precision = prec
+        run = lambda: S.super_resolve_scene(netG, scene, tile=TILE, overlap=OVERLAP, batch=BATCH, seed=0)   # noqa: E731
+        for _ in range(3):       # warm-up: 'auto' captures a shape's graph on its second call, the 1-tile group's on the second scene
+            run()
+        eng.set_precision(prec)
+        field = S.scene_noise_field(netG, SCENE, SCENE, 0)
+        cond, noise = S.gather(scene, field, origins[:BATCH], TILE)      # the bare sampler's inputs: the scene's first group
+        out = torch.empty_like(cond)
+        bare = lambda: eng.sample(cond, noise, graph=True, out=out)   # noqa: E731
+        for _ in range(3):
+            bare()
+        t_scene, t_bare = [], []       # (seconds per call, f16x3 range-guard re-runs in the window)
+        for _ in range(WINDOWS):       # A B A B ...
+            for fn, reps, dst in ((run, 2, t_scene), (bare, 10, t_bare)):
+                fb0 = Engine.saturation_fallbacks
+                dt = timed(fn, reps)
+                dst.append((dt, Engine.saturation_fallbacks - fb0))
+        # a window in which the range guard re-ran a call on the fp32 kernels (Engine.on_saturation) timed that re-run too: the rates
+        # compare the windows without one (all of them if there is none)
+        clean = [[t for t, fb in ts if fb == 0] or [t for t, _ in ts] for ts in (t_scene, t_bare)]
+        m_scene, m_bare = sum(clean[0]) / len(clean[0]), sum(clean[1]) / len(clean[1])
+        r_scene, r_bare = n / m_scene, BATCH / m_bare
+        show = lambda ts, k: ' '.join('%.*f%s' % (3 if k == 1 else 2, k * t, '*' * fb) for t, fb in ts)   # noqa: E731
+        lines.append('%-5s scene %7.3f s, %7.2f tiles/s | Engine.sample B=%d explicit noise, graph %7.2f ms per call, %7.2f tiles/s | ratio %.3f  '
+                     '(windows: %s s / %s ms; *: a range-guard re-run inside, left out of the means)' % (
+                         prec, m_scene, r_scene, BATCH, 1e3 * m_bare, r_bare, r_scene / r_bare, show(t_scene, 1), show(t_bare, 1e3)))
+        if prec == 'f16x3':
+            # the blend does not depend on the grouping; the sampler's own bits per image may (the launcher picks kernel forms by grid size)
+            fb0 = Engine.saturation_fallbacks
+            a16 = run()
+            a9 = S.super_resolve_scene(netG, scene, tile=TILE, overlap=OVERLAP, batch=9, seed=0)
+            d = (a16.int() - a9.int()).abs()
+            lines.append('%-5s   batch 16 against batch 9 (same seed): %d of %d uint8 samples differ, max |difference| %d (range-guard re-runs '
+                         'in the two runs: %d)' % (prec, int((d != 0).sum()), d.numel(), int(d.max()), Engine.saturation_fallbacks - fb0))
+            del a16, a9, d
+        # the parts of one scene run
+        t_field = timed(lambda: S.scene_noise_field(netG, SCENE, SCENE, 0), 3)
+        acc = torch.zeros(3, SCENE, SCENE, device='cuda')
+        wsum = torch.zeros(SCENE, SCENE, device='cuda')
+        c16, n16 = S.gather(scene, field, origins[:BATCH], TILE)
+        c1, n1 = S.gather(scene, field, origins[:1], TILE)
+        t_gather = timed(lambda: S.gather(scene, field, origins[:BATCH], TILE), 10)
+        t_blend = timed(lambda: S.blend(c16, origins[:BATCH], ramps[:BATCH], acc, wsum), 10)
+        t_finish = timed(lambda: S.finish(acc + 1, wsum + 1), 5)
+        for _ in range(2):
+            netG.p_sample_loop(c16, noise=n16), netG.p_sample_loop(c1, noise=n1)
+        t_full = timed(lambda: netG.p_sample_loop(c16, noise=n16), 5)
+        t_last = timed(lambda: netG.p_sample_loop(c1, noise=n1), 5)
+        full_groups, rest = n // BATCH, n % BATCH
+        parts = t_field + (full_groups + (1 if rest else 0)) * (t_gather + t_blend) + full_groups * t_full + (t_last if rest == 1 else 0) + t_finish
+        lines.append('%-5s   parts: noise field %.1f ms; per group of %d: gather %.2f ms, blend %.2f ms, p_sample_loop (explicit noise, graph '
+                     'replay) %.2f ms; the last 1-tile group %.2f ms; finish (with two scene-sized adds) %.2f ms; sum of parts %.3f s' % (
+                         prec, 1e3 * t_field, BATCH, 1e3 * t_gather, 1e3 * t_blend, 1e3 * t_full, 1e3 * t_last, 1e3 * t_finish, parts))
+        del field, acc, wsum, c16, n16, c1, n1, cond, noise, out
+        torch.cuda.empty_cache()
+    text = '\n'.join(lines) + '\n'
+    print(text, end='')
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write(text)
+
+
+if __name__ == '__main__':
+    main()
