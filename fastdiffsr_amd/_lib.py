@@ -101,6 +101,10 @@ SYMBOLS = {
                                     C.c_void_p]),
     'fdsr_scene_gather': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    'fdsr_scene_gather_f32': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'fdsr_set_noise_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    'fdsr_nafnet_set_noise_tiles': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    'fdsr_nafnet_randn_tiles': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]),
     'fdsr_scene_blend': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_int, C.c_void_p]),
     'fdsr_scene_finish': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

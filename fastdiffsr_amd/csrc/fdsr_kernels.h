@@ -282,6 +282,15 @@ hipError_t launch_resize_bicubic_u8(const unsigned char* src, unsigned char* tmp
                                     int h, int w, int H, int W, const int* bounds_x, const int* kk_x, int ksize_x,
                                     const int* bounds_y, const int* kk_y, int ksize_y, hipStream_t s);
 
+// Tile-addressed noise (include/fdsr.h: fdsr_set_noise_tiles).  origins == null: the counter of a pixel is its position in the
+// batch, n*H*W + pixel.  Else image n is the W-wide tile at origins[n] = (y0, x0) of a scene_w-wide scene and the counter is the
+// pixel's index in that scene (fdsr_philox.h: tile_counter); the table is read when the kernel runs.
+struct NoiseTiles {
+  const int* origins = nullptr;   // [N][2] int32, device
+  int scene_w = 0;
+  int W = 0;                      // width of the call's images
+};
+
 // one reverse-diffusion update (diffusion.py:157-190) on the packed state tensor
 // xin [N,H,W,CP]: channels [0,3) = cond, [3,6) = x_t.
 struct PosteriorParams {
@@ -290,6 +299,7 @@ struct PosteriorParams {
   const float* noise;  // [N,3,H,W] NCHW or null (t == 0, or engine RNG)
   const unsigned long long* rng;   // device {seed, call counter} or null: draw N(0,1) in the kernel (Philox4x32-10)
   int rng_plane;                   // which of the T noise planes this step draws (the k of noise[k])
+  NoiseTiles tiles;                // how the pixels the kernel draws for are addressed
   float* traj;         // [N,3,H,W] NCHW or null: x_{t-1}
   float* out;          // [N,3,H,W] NCHW or null: res2img(x_0, cond) at the last step
   int N, HW, CP;
@@ -325,6 +335,7 @@ struct PosteriorStepParams {
   float* xin;
   const float* noise;           // [planes][N,3,H,W] base, or null (engine RNG)
   const unsigned long long* rng;   // or null (explicit noise)
+  NoiseTiles tiles;
   float* traj;                  // [slots][N,3,H,W] base, or null
   float* out;
   int N, HW, CP;
@@ -337,9 +348,11 @@ hipError_t launch_posterior_step(const PosteriorStepParams& p, hipStream_t s);
 hipError_t launch_rng_advance(unsigned long long* rng, hipStream_t s);                      // ++call counter
 // plane `plane` of the noise the engine would use, as [N,3,H,W] fp32 (tests; the training step's self-drawn target) ...
 // first_image: the N images are [first_image, first_image + N) of a larger batch and draw those images' pixels
+// tiles: with a table the N images draw the crops of the scene's plane at their origins (first_image is then not applied)
 hipError_t launch_randn_plane(const unsigned long long* rng, float* dst_nchw, int N, int HW, int plane, hipStream_t s,
-                              size_t first_image = 0);
+                              size_t first_image = 0, NoiseTiles tiles = {});
 // ... and x_T = plane 0 written straight into channels 3..5 of the packed UNet input
-hipError_t launch_randn_xin(const unsigned long long* rng, float* xin, int N, int HW, int CP, hipStream_t s, int c_off = 3);
+hipError_t launch_randn_xin(const unsigned long long* rng, float* xin, int N, int HW, int CP, hipStream_t s, int c_off = 3,
+                            NoiseTiles tiles = {});
 
 }  // namespace fdsr

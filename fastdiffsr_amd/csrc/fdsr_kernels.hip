@@ -889,30 +889,32 @@ hipError_t launch_dropout_mask(unsigned char* mask, size_t n, unsigned long long
 }
 
 __global__ void __launch_bounds__(256) randn_plane_kernel(const unsigned long long* __restrict__ rng, float* __restrict__ dst, int HW,
-                                                          int CP, int c_off, int plane, size_t total, size_t pix0) {
+                                                          int CP, int c_off, int plane, size_t total, size_t pix0, const NoiseTiles tiles) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
+  const size_t n = i / HW, pix = i % HW;
   float z[3];
-  randn3(rng, plane, i + pix0, z);   // counter = pixel of the FULL batch (pix0: the first pixel of a shard of a larger batch)
+  // counter = pixel of the FULL batch (pix0: the first pixel of a shard of a larger batch), or of the scene the images are tiles of
+  randn3(rng, plane, tiles.origins ? tile_counter(tiles.origins, tiles.scene_w, tiles.W, n, pix) : i + pix0, z);
   if (CP) {   // NHWC, channels c_off..c_off+2 of the packed input
 #pragma unroll
     for (int c = 0; c < 3; ++c) dst[i * CP + c_off + c] = z[c];
   } else {    // NCHW [N,3,H,W]
-    const size_t n = i / HW, pix = i % HW;
 #pragma unroll
     for (int c = 0; c < 3; ++c) dst[(n * 3 + c) * HW + pix] = z[c];
   }
 }
-hipError_t launch_randn_plane(const unsigned long long* rng, float* dst, int N, int HW, int plane, hipStream_t s, size_t first_image) {
+hipError_t launch_randn_plane(const unsigned long long* rng, float* dst, int N, int HW, int plane, hipStream_t s, size_t first_image,
+                              NoiseTiles tiles) {
   const size_t total = (size_t)N * HW;
   hipLaunchKernelGGL(randn_plane_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rng, dst, HW, 0, 0, plane, total,
-                     first_image * HW);
+                     first_image * HW, tiles);
   return hipGetLastError();
 }
-hipError_t launch_randn_xin(const unsigned long long* rng, float* xin, int N, int HW, int CP, hipStream_t s, int c_off) {
+hipError_t launch_randn_xin(const unsigned long long* rng, float* xin, int N, int HW, int CP, hipStream_t s, int c_off, NoiseTiles tiles) {
   const size_t total = (size_t)N * HW;
   hipLaunchKernelGGL(randn_plane_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, rng, xin, HW, CP, c_off, 0, total,
-                     (size_t)0);
+                     (size_t)0, tiles);
   return hipGetLastError();
 }
 
@@ -921,13 +923,13 @@ hipError_t launch_randn_xin(const unsigned long long* rng, float* xin, int N, in
 // ---------------------------------------------------------------------------
 // one pixel of one step; both posterior kernels below run exactly this arithmetic
 __device__ __forceinline__ void posterior_pixel(size_t i, int HW, int CP, const float* eps, float* xin,
-                                                const float* noise, const unsigned long long* rng, int rng_plane, float* traj,
-                                                float* out, float c_recip, float c_recipm1, float coef1, float coef2, float sigma,
+                                                const float* noise, const unsigned long long* rng, int rng_plane,
+                                                const NoiseTiles& tiles, float* traj, float* out, float c_recip, float c_recipm1, float coef1, float coef2, float sigma,
                                                 int plain_out, int x_off, int x0_pred) {
   const size_t n = i / HW, pix = i % HW;
   float* xs = xin + i * CP;
   float z[3] = {0.f, 0.f, 0.f};
-  if (rng) randn3(rng, rng_plane, i, z);
+  if (rng) randn3(rng, rng_plane, tiles.origins ? tile_counter(tiles.origins, tiles.scene_w, tiles.W, n, pix) : i, z);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float x = xs[x_off + c];
@@ -952,7 +954,7 @@ __global__ void __launch_bounds__(256) posterior_kernel(const PosteriorParams p)
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   const size_t total = (size_t)p.N * p.HW;
   if (i >= total) return;
-  posterior_pixel(i, p.HW, p.CP, p.eps, p.xin, p.noise, p.rng, p.rng_plane, p.traj, p.out, p.c_recip, p.c_recipm1, p.coef1, p.coef2,
+  posterior_pixel(i, p.HW, p.CP, p.eps, p.xin, p.noise, p.rng, p.rng_plane, p.tiles, p.traj, p.out, p.c_recip, p.c_recipm1, p.coef1, p.coef2,
                   p.sigma, p.plain_out, p.x_off, p.x0_pred);
 }
 
@@ -1008,7 +1010,7 @@ __global__ void __launch_bounds__(256) posterior_step_kernel(const PosteriorStep
   const unsigned long long* rng = (!p.noise && r.noise_plane >= 0) ? p.rng : nullptr;
   float* traj = (p.traj && r.traj_slot >= 0) ? p.traj + (size_t)r.traj_slot * img : nullptr;
   float* out = r.is_last ? p.out : nullptr;
-  posterior_pixel(i, p.HW, p.CP, p.eps, p.xin, noise, rng, r.rng_plane, traj, out, r.c_recip, r.c_recipm1, r.coef1, r.coef2, r.sigma,
+  posterior_pixel(i, p.HW, p.CP, p.eps, p.xin, noise, rng, r.rng_plane, p.tiles, traj, out, r.c_recip, r.c_recipm1, r.coef1, r.coef2, r.sigma,
                   p.plain_out, p.x_off, p.x0_pred);
 }
 

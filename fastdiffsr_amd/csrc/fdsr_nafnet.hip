@@ -308,8 +308,9 @@ struct StepTables { const float *theta, *sigma, *sbar; float dt, sqrt_dt; int T;
 // x (in place, NCHW) for step k = ctl[0], t = T - k; rounded operations in the reference's order.
 __global__ void __launch_bounds__(256) naf_tail_kernel(const float* __restrict__ eps, float* __restrict__ x, const float* __restrict__ cond,
                                                        const float* __restrict__ noise, float* __restrict__ traj, const int* __restrict__ ctl,
-                                                       StepTables tb, unsigned long long seed, long long first_image, int mode, int H, int W,
-                                                       int Hp, int Wp, size_t total) {
+                                                       StepTables tb, unsigned long long seed, long long first_image,
+                                                       const int* __restrict__ tiles, int scene_w, int mode, int H, int W, int Hp, int Wp,
+                                                       size_t total) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;   // (n, y, x) of the cropped image
   if (i >= total) return;
   const int px = (int)(i % W), py = (int)((i / W) % H);
@@ -332,7 +333,8 @@ __global__ void __launch_bounds__(256) naf_tail_kernel(const float* __restrict__
       for (int c = 0; c < 3; ++c) z[c] = noise[plane + base + c * HW];
     } else {
       const unsigned long long rng[2] = {seed, 0ull};
-      fdsr::randn3(rng, k, (size_t)first_image * HW + i, z);
+      // the pixel's position among the images of the whole run, or in the scene the images are tiles of (fdsr_nafnet_set_noise_tiles)
+      fdsr::randn3(rng, k, tiles ? fdsr::tile_counter(tiles, scene_w, W, n, (size_t)py * W + px) : (size_t)first_image * HW + i, z);
     }
   }
 #pragma unroll
@@ -367,13 +369,14 @@ __global__ void naf_iota_kernel(float* t, int n) {
   if (i < n) t[i] = (float)i;
 }
 
-__global__ void __launch_bounds__(256) naf_randn_kernel(float* __restrict__ dst, int HW, int plane, unsigned long long seed, size_t pix0, size_t total) {
+__global__ void __launch_bounds__(256) naf_randn_kernel(float* __restrict__ dst, int HW, int plane, unsigned long long seed, size_t pix0, size_t total,
+                                                        const int* __restrict__ tiles, int scene_w, int W) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const unsigned long long rng[2] = {seed, 0ull};
-  float z[3];
-  fdsr::randn3(rng, plane, i + pix0, z);
   const size_t n = i / HW, pix = i % HW;
+  float z[3];
+  fdsr::randn3(rng, plane, tiles ? fdsr::tile_counter(tiles, scene_w, W, n, pix) : i + pix0, z);
 #pragma unroll
   for (int c = 0; c < 3; ++c) dst[(n * 3 + c) * HW + pix] = z[c];
 }
@@ -547,7 +550,10 @@ struct fdsr_nafnet_obj {
   int* d_ctl = nullptr;          // step counter
   // one cached step graph
   struct { const void *cond = nullptr, *noise = nullptr, *out = nullptr, *traj = nullptr, *ws = nullptr; int N = 0, H = 0, W = 0, flags = 0;
-           unsigned long long seed = 0; long long first = 0; hipGraphExec_t exec = nullptr; } graph;
+           unsigned long long seed = 0; long long first = 0; const void* tiles = nullptr; int scene_w = 0; hipGraphExec_t exec = nullptr; } graph;
+  // fdsr_nafnet_set_noise_tiles: the caller's device table of tile origins [tiles_n][2] (null: none) and the scene's width
+  const int32_t* noise_tiles = nullptr;
+  int noise_tiles_n = 0, noise_scene_w = 0;
 };
 
 namespace {
@@ -1126,7 +1132,8 @@ struct Run {
     net();
   }
 
-  void tail(int mode, float* x, const float* cond, const float* noise, float* traj, unsigned long long seed, long long first) {
+  void tail(int mode, float* x, const float* cond, const float* noise, float* traj, unsigned long long seed, long long first,
+            const int32_t* tiles = nullptr, int scene_w = 0) {
     StepTables tb{};
     if (mode) {
       tb.theta = n->d_sde;
@@ -1137,7 +1144,8 @@ struct Run {
       tb.T = n->T;
     }
     const size_t total = (size_t)d.N * d.H * d.W;
-    launch(naf_tail_kernel, dim3(nb(total)), dim3(256), 0, d.eps, x, cond, noise, traj, n->d_ctl, tb, seed, first, mode, d.H, d.W, d.Hp, d.Wp, total);
+    launch(naf_tail_kernel, dim3(nb(total)), dim3(256), 0, d.eps, x, cond, noise, traj, n->d_ctl, tb, seed, first, tiles, scene_w, mode, d.H, d.W, d.Hp,
+           d.Wp, total);
   }
 };
 
@@ -1402,6 +1410,13 @@ int fdsr_nafnet_sample(fdsr_nafnet n, const float* state_nchw, const float* cond
   if (rc) return rc;
   if ((rc = ensure_table(n, st))) return rc;
   const int mode = (flags & FDSR_NAFNET_ODE) ? 2 : 1;
+  // the table counts where the call draws its own noise: explicit noise and the ODE draw nothing
+  const int32_t* tiles = (!noise && mode == 1) ? n->noise_tiles : nullptr;
+  const int scene_w = tiles ? n->noise_scene_w : 0;
+  if (n->noise_tiles && first_image != 0)   // two ways to place an image in a larger whole: one at a time
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_sample: first_image must be 0 under a noise-tile table (got %lld)", (long long)first_image);
+  if (tiles && batch > n->noise_tiles_n)
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_sample: %d images under a noise-tile table of %d", batch, n->noise_tiles_n);
   HIPCHK(nullptr, hipMemcpyAsync(out_nchw, state_nchw, (size_t)batch * 3 * height * width * sizeof(float), hipMemcpyDeviceToDevice, st));
   HIPCHK(nullptr, hipMemsetAsync(n->d_ctl, 0, sizeof(int), st));
   Run r = sample_run(n, batch, height, width, workspace, st, n->d_cur_row, 0);
@@ -1409,7 +1424,7 @@ int fdsr_nafnet_sample(fdsr_nafnet n, const float* state_nchw, const float* cond
     r.launch(naf_row_copy_kernel, dim3(Run::nb(n->R)), dim3(256), 0, n->d_rowtable, n->d_cur_row, n->d_ctl, n->T, n->R);
     r.prep(out_nchw, cond_nchw);
     r.net();
-    r.tail(mode, out_nchw, cond_nchw, noise, traj, seed, first_image);
+    r.tail(mode, out_nchw, cond_nchw, noise, traj, seed, first_image, tiles, scene_w);
     r.launch(naf_advance_kernel, dim3(1), dim3(64), 0, n->d_ctl);
     return r.err;
   };
@@ -1420,12 +1435,12 @@ int fdsr_nafnet_sample(fdsr_nafnet n, const float* state_nchw, const float* cond
   }
   auto& g = n->graph;
   if (!(g.exec && g.cond == cond_nchw && g.noise == noise && g.out == out_nchw && g.traj == traj && g.ws == workspace && g.N == batch &&
-        g.H == height && g.W == width && g.flags == flags && g.seed == seed && g.first == first_image)) {
+        g.H == height && g.W == width && g.flags == flags && g.seed == seed && g.first == first_image && g.tiles == tiles && g.scene_w == scene_w)) {
     drop_graph(n);
     hipGraphExec_t exec = nullptr;
     if ((rc = capture_exec(nullptr, st, step, &exec))) return rc;
     g.cond = cond_nchw; g.noise = noise; g.out = out_nchw; g.traj = traj; g.ws = workspace;
-    g.N = batch; g.H = height; g.W = width; g.flags = flags; g.seed = seed; g.first = first_image; g.exec = exec;
+    g.N = batch; g.H = height; g.W = width; g.flags = flags; g.seed = seed; g.first = first_image; g.tiles = tiles; g.scene_w = scene_w; g.exec = exec;
   }
   for (int k = 0; k < n->T; ++k) HIPCHK(nullptr, hipGraphLaunch(g.exec, st));
   return FDSR_OK;
@@ -1436,7 +1451,27 @@ int fdsr_nafnet_randn(float* dst_nchw, int batch, int height, int width, int pla
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_randn: bad arguments");
   const size_t HW = (size_t)height * width, total = (size_t)batch * HW;
   hipLaunchKernelGGL(naf_randn_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), dst_nchw,
-                     (int)HW, plane, (unsigned long long)seed, (size_t)first_image * HW, total);
+                     (int)HW, plane, (unsigned long long)seed, (size_t)first_image * HW, total, (const int*)nullptr, 0, width);
+  HIPCHK(nullptr, hipGetLastError());
+  return FDSR_OK;
+}
+
+int fdsr_nafnet_set_noise_tiles(fdsr_nafnet n, const int32_t* origins_dev, int n_tiles, int scene_w) {
+  if (!n || (origins_dev && (n_tiles < 1 || scene_w < 1)))
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_set_noise_tiles: a table needs n_tiles >= 1 and scene_w >= 1 (got %d, %d)", n_tiles, scene_w);
+  n->noise_tiles = origins_dev;
+  n->noise_tiles_n = origins_dev ? n_tiles : 0;
+  n->noise_scene_w = origins_dev ? scene_w : 0;
+  return FDSR_OK;
+}
+
+int fdsr_nafnet_randn_tiles(float* dst_nchw, int batch, int height, int width, int plane, uint64_t seed, const int32_t* origins_dev,
+                            int scene_w, void* hip_stream) {
+  if (!dst_nchw || !origins_dev || batch < 1 || height < 1 || width < 1 || plane < 0 || scene_w < 1)
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_randn_tiles: bad arguments");
+  const size_t HW = (size_t)height * width, total = (size_t)batch * HW;
+  hipLaunchKernelGGL(naf_randn_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(hip_stream), dst_nchw,
+                     (int)HW, plane, (unsigned long long)seed, (size_t)0, total, origins_dev, scene_w, width);
   HIPCHK(nullptr, hipGetLastError());
   return FDSR_OK;
 }

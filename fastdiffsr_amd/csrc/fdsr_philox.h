@@ -11,6 +11,14 @@ __device__ __forceinline__ void philox_round(unsigned& c0, unsigned& c1, unsigne
   const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
   c0 = n0; c1 = n1; c2 = n2; c3 = n3;
 }
+// Tile-addressed noise (include/fdsr.h: fdsr_set_noise_tiles): the counter of pixel `pix` = y * W + x of image n, a W-wide tile whose
+// origin in a scene_w-wide scene is origins[n] = (y0, x0): the pixel's index in the scene, (y0 + y) * scene_w + (x0 + x), in 64 bits.
+// It addresses a counter, not memory: an origin outside the scene only draws other numbers.
+__device__ __forceinline__ size_t tile_counter(const int* __restrict__ origins, int scene_w, int W, size_t n, size_t pix) {
+  const long long y = (long long)origins[2 * n] + (long long)(pix / (size_t)W);
+  const long long x = (long long)origins[2 * n + 1] + (long long)(pix % (size_t)W);
+  return (size_t)(y * (long long)scene_w + x);
+}
 // three standard normals for pixel `i` of noise plane `plane` under {seed, calls}
 __device__ __forceinline__ void randn3(const unsigned long long* rng, int plane, size_t i, float out[3]) {
   const unsigned long long seed = rng[0], calls = rng[1];

@@ -85,6 +85,7 @@ struct SampleCall {
   float *out, *traj;
   int N, H, W;
   int every;          // fdsr_sample_stepwise: the trajectory keeps the steps with t % every == 0
+  NoiseTiles tiles;   // the handle's noise-tile table where the call draws its own noise (sample_prepare); else none
   char* ws;
   hipStream_t st;
   bool use_graph;
@@ -103,8 +104,9 @@ int sample_head(fdsr_handle h, const SampleCall& c, bool reset_counter) {
   if (c.noise) {
     HIPCHK(h, launch_nchw_to_nhwc(c.noise, xin, c.N, 3, c.H, c.W, h->CP, x_off, 0, c.st));
   } else {   // the engine draws: a new call counter per sample (also under graph replay), plane 0 = x_T
-    HIPCHK(h, launch_rng_advance(h->d_rng, c.st));
-    HIPCHK(h, launch_randn_xin(h->d_rng, xin, c.N, c.H * c.W, h->CP, c.st, x_off));
+    // tile-addressed noise: the counter stays where it is, so every group of a scene draws from the one field of that counter
+    if (!c.tiles.origins) HIPCHK(h, launch_rng_advance(h->d_rng, c.st));
+    HIPCHK(h, launch_randn_xin(h->d_rng, xin, c.N, c.H * c.W, h->CP, c.st, x_off, c.tiles));
   }
   if (reset_counter) HIPCHK(h, hipMemsetAsync(h->d_step_ctl, 0, sizeof(int), c.st));
   return FDSR_OK;
@@ -146,6 +148,7 @@ int sample_step(fdsr_handle h, const SampleCall& c, int k) {
     pp.xin = reinterpret_cast<float*>(c.ws + h->plan.tensor_off[h->t_in]);
     pp.noise = noise;
     pp.rng = c.noise ? nullptr : h->d_rng;
+    pp.tiles = c.tiles;
     pp.traj = traj;
     pp.out = out;
     pp.N = c.N; pp.HW = c.H * c.W; pp.CP = h->CP;
@@ -226,11 +229,12 @@ int run_sample(fdsr_handle h, const SampleCall& c, int chunk) {
   for (const auto& e : list)
     if (e.cond == c.cond && e.noise == c.noise && e.out == c.out && e.traj == c.traj && e.ws == c.ws &&
         e.temb_table == h->d_temb_table && e.sched == h->d_step_sched && e.N == c.N && e.H == c.H && e.W == c.W &&
-        e.chunk == chunk && e.every == c.every)
+        e.chunk == chunk && e.every == c.every && e.tiles == c.tiles.origins && e.scene_w == c.tiles.scene_w)
       g = &e;
   const int T = h->T;
   if (!g) {
-    SampleGraph ge{c.cond, c.noise, c.out, c.traj, c.ws, h->d_temb_table, h->d_step_sched, c.N, c.H, c.W, chunk, c.every, {}};
+    SampleGraph ge{c.cond, c.noise, c.out, c.traj, c.ws, h->d_temb_table, h->d_step_sched, c.N, c.H, c.W, chunk, c.every,
+                   c.tiles.origins, c.tiles.scene_w, {}};
     auto steps = [&](int n) {
       int r = FDSR_OK;
       for (int k = 0; k < n && !r; ++k) r = sample_step(h, c, DEVICE_STEP);
@@ -272,6 +276,13 @@ int sample_prepare(fdsr_handle h, SampleCall* c, void* workspace, size_t workspa
   c->ws = reinterpret_cast<char*>(workspace);
   if ((rc = apply_plan(h, fdsr_forms::need_sample(h->forms, h->prec, stepwise), c->st))) return rc;   // optimiser steps moved the master copy
   if (!c->noise && (rc = ensure_rng(h))) return rc;
+  if (!c->noise && h->noise_tiles) {
+    if (c->N > h->noise_tiles_n)
+      return fail(h, FDSR_E_INVALID, "a call of %d images under a noise-tile table of %d (fdsr_set_noise_tiles)", c->N, h->noise_tiles_n);
+    c->tiles.origins = h->noise_tiles;
+    c->tiles.scene_w = h->noise_scene_w;
+    c->tiles.W = c->W;
+  }
   if ((flags & FDSR_SAMPLE_GRAPH) && c->st == nullptr)
     return fail(h, FDSR_E_INVALID, "FDSR_SAMPLE_GRAPH needs a non-default stream (stream capture cannot run on the NULL stream)");
   c->use_graph = (flags & FDSR_SAMPLE_GRAPH) && !h->profiling;
@@ -292,7 +303,7 @@ extern "C" {
 
 int fdsr_sample(fdsr_handle h, const float* cond_nchw, const float* noise, float* out_nchw, float* traj_nchw, int batch,
                 int height, int width, void* workspace, size_t workspace_bytes, void* hip_stream, int flags) {
-  SampleCall c{cond_nchw, noise, out_nchw, traj_nchw, batch, height, width, 1};
+  SampleCall c{cond_nchw, noise, out_nchw, traj_nchw, batch, height, width, 1, {}};
   const int rc = sample_prepare(h, &c, workspace, workspace_bytes, hip_stream, flags, false, nullptr);
   return rc ? rc : run_sample(h, c, 0);
 }
@@ -305,7 +316,7 @@ int fdsr_sample_stepwise(fdsr_handle h, const float* cond_nchw, const float* noi
   if (chunk_opt < 0 || every < 1) refusal = "fdsr_sample_opts: chunk_steps >= 0 and traj_every >= 1";
   else if (g_tun.bf16_f16x3_steps != 0)
     refusal = "fdsr_sample_stepwise: the bf16_f16x3_steps probe makes the precision step-dependent; use fdsr_sample";
-  SampleCall c{cond_nchw, noise, out_nchw, traj_nchw, batch, height, width, every};
+  SampleCall c{cond_nchw, noise, out_nchw, traj_nchw, batch, height, width, every, {}};
   const int rc = sample_prepare(h, &c, workspace, workspace_bytes, hip_stream, flags, true, refusal);
   if (rc) return rc;
   if (c.use_graph && h->training && h->n_drop_slots > 0)   // a replayed chunk would repeat its dropout masks
@@ -329,7 +340,25 @@ int fdsr_randn(fdsr_handle h, float* dst_nchw, int batch, int height, int width,
   if (!h || !dst_nchw || batch < 1 || height < 1 || width < 1 || plane < 0) return fail(h, FDSR_E_INVALID, "bad fdsr_randn arguments");
   int rc = ensure_rng(h);
   if (rc) return rc;
-  HIPCHK(h, launch_randn_plane(h->d_rng, dst_nchw, batch, height * width, plane, reinterpret_cast<hipStream_t>(hip_stream)));
+  NoiseTiles tiles;
+  if (h->noise_tiles) {
+    if (batch > h->noise_tiles_n)
+      return fail(h, FDSR_E_INVALID, "fdsr_randn: %d images under a noise-tile table of %d (fdsr_set_noise_tiles)", batch, h->noise_tiles_n);
+    tiles.origins = h->noise_tiles;
+    tiles.scene_w = h->noise_scene_w;
+    tiles.W = width;
+  }
+  HIPCHK(h, launch_randn_plane(h->d_rng, dst_nchw, batch, height * width, plane, reinterpret_cast<hipStream_t>(hip_stream), 0, tiles));
+  return FDSR_OK;
+}
+
+int fdsr_set_noise_tiles(fdsr_handle h, const int32_t* origins_dev, int n_tiles, int scene_w) {
+  if (!h) return FDSR_E_INVALID;
+  if (origins_dev && (n_tiles < 1 || scene_w < 1))
+    return fail(h, FDSR_E_INVALID, "fdsr_set_noise_tiles: a table needs n_tiles >= 1 and scene_w >= 1 (got %d, %d)", n_tiles, scene_w);
+  h->noise_tiles = origins_dev;
+  h->noise_tiles_n = origins_dev ? n_tiles : 0;
+  h->noise_scene_w = origins_dev ? scene_w : 0;
   return FDSR_OK;
 }
 

@@ -208,6 +208,18 @@ int fdsr_scene_gather(fdsr_handle h, const uint8_t* scene_u8, const float* field
   return FDSR_OK;
 }
 
+int fdsr_scene_gather_f32(fdsr_handle h, const float* scene, int scene_h, int scene_w, const int32_t* origins, int n_tiles, int tile,
+                          float* tiles, void* hip_stream) {
+  if (!scene || !origins || !tiles || n_tiles < 1 || bad_scene(scene_h, scene_w, tile))
+    return fail(h, FDSR_E_INVALID, "fdsr_scene_gather_f32: bad arguments (%d tiles of %d in a %dx%d scene)", n_tiles, tile, scene_h,
+                scene_w);
+  // a [3,SH,SW] image is a noise field of one plane, and [1,n,3,t,t] is [n,3,t,t]
+  hipLaunchKernelGGL(scene_gather_noise_kernel, dim3(blocks_for((size_t)n_tiles * 3 * tile * ((tile + 3) / 4))), dim3(NT), 0,
+                     reinterpret_cast<hipStream_t>(hip_stream), scene, origins, tiles, 1, n_tiles, tile, scene_h, scene_w);
+  HIPCHK(h, hipGetLastError());
+  return FDSR_OK;
+}
+
 int fdsr_scene_blend(fdsr_handle h, const float* tiles, const int32_t* origins, const int32_t* ramps, int n_tiles, int tile,
                      float* acc, float* wsum, int scene_h, int scene_w, void* hip_stream) {
   if (!tiles || !origins || !ramps || !acc || !wsum || n_tiles < 1 || bad_scene(scene_h, scene_w, tile) || tile > 32768)

@@ -130,7 +130,7 @@ class ConditionalNAFNet(nn.Module):
         in 'f32', without a schedule) on first use."""
         d = dict(self.__dict__)
         d['_h'], d['_uploaded'], d['_ws'] = None, None, {}
-        for k in ('_graph_stream', '_precision', '_train_precision', '_sde_T'):
+        for k in ('_graph_stream', '_precision', '_train_precision', '_sde_T', '_noise_tiles'):
             d.pop(k, None)
         return d
 
@@ -438,13 +438,36 @@ class ConditionalNAFNet(nn.Module):
         _lib.check(None, _lib.load().fdsr_nafnet_sample(self._handle(), _ptr(x), _ptr(cond), _ptr(noise), int(seed), int(first_image), flags,
                                                         _ptr(out), _ptr(traj), b, h, w, _ptr(ws), ws.numel(), C.c_void_p(st)))
 
+    def set_noise_tiles(self, origins, scene_w):
+        """Tile-addressed noise (include/fdsr.h: fdsr_nafnet_set_noise_tiles): origins [n,2] int32 on the device, (y0, x0) of image
+        i of a call in a scene `scene_w` wide.  Until clear_noise_tiles, what sample draws itself (noise=None) and randn are the
+        crops of the scene's planes at those origins; first_image must then be 0.  The table is read when the kernels run: the
+        module keeps the tensor, and the caller may rewrite it in place between calls."""
+        if not (origins.is_cuda and origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.shape[0] >= 1
+                and origins.is_contiguous()):
+            raise ValueError('origins must be a contiguous CUDA int32 tensor [n,2] with n >= 1')
+        _lib.check(None, _lib.load().fdsr_nafnet_set_noise_tiles(self._handle(), _ptr(origins), int(origins.shape[0]), int(scene_w)))
+        self._noise_tiles = (origins, int(scene_w))
+
+    def clear_noise_tiles(self):
+        _lib.check(None, _lib.load().fdsr_nafnet_set_noise_tiles(self._handle(), None, 0, 0))
+        self._noise_tiles = None
+
     def randn(self, b, h, w, plane, seed, first_image=0, device=None):
-        """Plane `plane` of the engine's own noise stream (include/fdsr.h), [B,3,H,W]."""
+        """Plane `plane` of the engine's own noise stream (include/fdsr.h), [B,3,H,W]; under set_noise_tiles, the B crops of the
+        scene's plane at the table's first B origins (first_image must then be 0)."""
         device = device or next(self.parameters()).device
+        tiles = getattr(self, '_noise_tiles', None)
+        if tiles is not None and (int(first_image) != 0 or b > tiles[0].shape[0]):
+            raise ValueError('randn under a noise-tile table of %d: first_image must be 0 and B at most that (got %d, %d)'
+                             % (tiles[0].shape[0], first_image, b))
         out = torch.empty((b, 3, h, w), dtype=torch.float32, device=device)
         with torch.cuda.device(device):
             st = torch.cuda.current_stream(device).cuda_stream
-            _lib.check(None, _lib.load().fdsr_nafnet_randn(_ptr(out), b, h, w, plane, int(seed), int(first_image), C.c_void_p(st)))
+            if tiles is not None:
+                _lib.check(None, _lib.load().fdsr_nafnet_randn_tiles(_ptr(out), b, h, w, plane, int(seed), _ptr(tiles[0]), tiles[1], C.c_void_p(st)))
+            else:
+                _lib.check(None, _lib.load().fdsr_nafnet_randn(_ptr(out), b, h, w, plane, int(seed), int(first_image), C.c_void_p(st)))
         return out
 
 

@@ -57,6 +57,26 @@ def build_model(opt, device):
     return net.to(device).eval()
 
 
+def reverse_sde_guarded(net, sde, state, what, restore=None, **kwargs):
+    """sde.reverse_sde(state, **kwargs) under the network's precision.  Under 'f16x3' / 'f16' the range guard is read once after
+    the call, and a call that raised it is run again in f32 with a warning that names `what` (the images of the call); restore(),
+    if given, first puts the caller's noise source back where it was before the call.  The network ends in the mode it had."""
+    mode = net.precision
+    sr = sde.reverse_sde(state, **kwargs)
+    if mode in ('f16x3', 'f16'):
+        try:
+            net.check_saturation()
+        except _lib.FdsrSaturated:
+            logging.getLogger('fastdiffsr_amd.ediffsr').warning(
+                '%s left the f16 range under --precision %s: running the batch again in f32', what, mode)
+            net.set_precision('f32')
+            if restore is not None:
+                restore()
+            sr = sde.reverse_sde(state, **kwargs)
+            net.set_precision(mode)
+    return sr
+
+
 def run_dataset(opt, ds, net, sde, device, results, batch=1, rng='torch', seed=0, lpips=None, log=print):
     from PIL import Image
     scale, T = opt['scale'], opt['sde']['T']
@@ -78,21 +98,11 @@ def run_dataset(opt, ds, net, sde, device, results, batch=1, rng='torch', seed=0
         else:
             state = sde.noise_state(mu)
         sde.set_mu(mu)
-        mode = net.precision
-        if mode in ('f16x3', 'f16') and rng == 'torch':
+        restore = None
+        if net.precision in ('f16x3', 'f16') and rng == 'torch':
             rng_state = torch.cuda.get_rng_state(device)      # a re-run in f32 draws the same per-step noise
-        sr = sde.reverse_sde(state)
-        if mode in ('f16x3', 'f16'):
-            try:
-                net.check_saturation()
-            except _lib.FdsrSaturated:
-                logging.getLogger('fastdiffsr_amd.ediffsr').warning(
-                    'images %d..%d left the f16 range under --precision %s: running the batch again in f32', b0, b0 + len(part) - 1, mode)
-                net.set_precision('f32')
-                if rng == 'torch':
-                    torch.cuda.set_rng_state(rng_state, device)
-                sr = sde.reverse_sde(state)
-                net.set_precision(mode)
+            restore = lambda: torch.cuda.set_rng_state(rng_state, device)   # noqa: E731
+        sr = reverse_sde_guarded(net, sde, state, 'images %d..%d' % (b0, b0 + len(part) - 1), restore)
         sr_u8 = M.tensor2img_batch(sr, min_max=(0, 1))
         torch.cuda.synchronize(device)
         times.append((time.time() - tic) / len(part))

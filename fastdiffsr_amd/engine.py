@@ -241,6 +241,21 @@ class Engine:
         _lib.check(self.h, self.lib.fdsr_randn(self.h, _ptr(dst), B, H, W, int(plane), C.c_void_p(st)))
         return dst
 
+    def set_noise_tiles(self, origins, scene_w):
+        """Tile-addressed noise (include/fdsr.h: fdsr_set_noise_tiles): origins [n,2] int32 on the device, (y0, x0) of image i of a
+        call in a scene `scene_w` wide.  Until clear_noise_tiles, what sample draws itself (noise=None) and randn are the crops of
+        the scene's field at those origins, and such a sample leaves the call counter where it is.  The table is read when the
+        kernels run: the engine keeps the tensor, and the caller may rewrite it in place between calls."""
+        if not (origins.is_cuda and origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.shape[0] >= 1
+                and origins.is_contiguous()):
+            raise ValueError('origins must be a contiguous CUDA int32 tensor [n,2] with n >= 1')
+        _lib.check(self.h, self.lib.fdsr_set_noise_tiles(self.h, _ptr(origins), int(origins.shape[0]), int(scene_w)))
+        self._noise_tiles = origins
+
+    def clear_noise_tiles(self):
+        _lib.check(self.h, self.lib.fdsr_set_noise_tiles(self.h, None, 0, 0))
+        self._noise_tiles = None
+
     def set_precision(self, mode):
         """'f32' (exact fp32 MFMA), 'f16x3' (fp32-grade split-f16 MFMA) or 'bf16'."""
         code = _lib.PRECISIONS[mode] if isinstance(mode, str) else int(mode)

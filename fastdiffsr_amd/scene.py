@@ -1,14 +1,16 @@
 """Whole-scene super-resolution: a scene larger than one sampling call is walked as overlapping square tiles.
 
     python -m fastdiffsr_amd.scene -c CONFIG (--lr IN --scale S | --sr IN) -o OUT
-        [--tile 256] [--overlap 32] [--batch 16] [--precision ...] [--rng ...] [--seed 0] [--noise scene|tile]
+        [--tile 256] [--overlap 32] [--batch 16] [--precision ...] [--rng ...] [--seed 0] [--noise scene|tile|stream]
 
 The reference has no such driver (its data are pre-cut patches); this is the layer above `p_sample_loop(x_in, noise=...)`:
 
   plan      `plan_tiles`: tile origins in row-major order and, per tile, over how many pixels its weight ramps up from each side
   noise     `noise='scene'`: ONE field [P,3,SH,SW] for the whole scene; a tile gets its crop, so two overlapping tiles start from
             the same x_T and see the same per-step noise in the pixels they share.  `noise='tile'`: [P,1,3,t,t] per tile from a
-            generator keyed by (seed, tile index), for scenes whose field does not fit.
+            generator keyed by (seed, tile index), for scenes whose field does not fit.  `noise='stream'` (rng='engine'): the
+            field of noise='scene' without the array -- the sampler draws each tile pixel's numbers in its kernels from the
+            pixel's place in the scene (Engine.set_noise_tiles), bit for bit what the crop would hold, at any T and any scene size.
   device    fdsr_scene_gather (scene -> cond / noise tiles), the sampler, fdsr_scene_blend (tiles -> acc, wsum), fdsr_scene_finish
             (acc / wsum -> uint8), csrc/fdsr_scene.hip; nothing of a scene's size crosses PCIe but the input and the result
 
@@ -211,12 +213,22 @@ def super_resolve_scene(diffusion, scene_u8, tile=256, overlap=32, batch=16, noi
     (noise='scene'), or per tile with the key of (seed, tile index) (noise='tile').  The engine's seed and its per-call counter
     stay as the last of these left them: a later p_sample_loop that draws its own noise continues from there, not from where the
     caller's earlier set_seed had it.  Call set_seed again before such a call.  rng='torch' uses a generator of its own and leaves
-    torch's global stream alone."""
+    torch's global stream alone.
+
+    noise='stream' (rng='engine' only; ValueError under rng='torch'): no field is drawn and noise_budget is not consulted.
+    set_seed(seed) once, then per group the group's origins are copied into one device buffer per group size (full groups replay
+    one graph, which reads the buffer when it runs), Engine.set_noise_tiles points the sampler at it and p_sample_loop(cond) draws
+    its own noise: for the tile at (y0, x0) the crop of the field noise='scene' would have drawn, so the result equals
+    noise='scene' bit for bit.  Such calls leave the engine's call counter at 0, where set_seed put it; the table is cleared on the
+    way out.  The f16x3 range guard's re-run of a call (Engine.on_saturation) therefore redraws the SAME noise here: the counter
+    does not move, and the numbers depend on nothing else."""
     import torch
     if not scene_u8.is_cuda or scene_u8.dtype != torch.uint8 or scene_u8.dim() != 3 or scene_u8.shape[-1] != 3:
         raise ValueError('scene_u8 must be a CUDA uint8 tensor of shape [SH,SW,3]')
-    if noise not in ('scene', 'tile'):
-        raise ValueError(f"noise must be 'scene' or 'tile' (got {noise!r})")
+    if noise not in ('scene', 'tile', 'stream'):
+        raise ValueError(f"noise must be 'scene', 'tile' or 'stream' (got {noise!r})")
+    if noise == 'stream' and diffusion.rng != 'engine':
+        raise ValueError(f"noise='stream' draws in the engine's kernels and requires rng='engine' (the facade's rng is {diffusion.rng!r})")
     if int(batch) < 1:
         raise ValueError('batch must be at least 1')
     scene_u8 = scene_u8.contiguous()
@@ -239,11 +251,22 @@ def super_resolve_scene(diffusion, scene_u8, tile=256, overlap=32, batch=16, noi
         acc = torch.zeros(3, sh, sw, device=dev, dtype=torch.float32)
         wsum = torch.zeros(sh, sw, device=dev, dtype=torch.float32)
         group = tiles_per_call(diffusion, batch)
+        # noise='stream': group size -> the device buffer its calls read their origins from; kept with the engine, so that a later
+        # scene finds the graphs this one captured (they key on the buffer's address)
+        tables = eng.__dict__.setdefault('_scene_tables', {})
+        if noise == 'stream':
+            eng.set_seed(seed)
         for k0 in range(0, n, group):
             k1 = min(k0 + group, n)
             cond, nz = gather(scene_u8, field, origins[k0:k1], tile)
-            if field is None:
+            if noise == 'tile':
                 nz = torch.cat([tile_noise(diffusion, tile, seed, k, dev) for k in range(k0, k1)], dim=1)
+            elif noise == 'stream':
+                if (k1 - k0, str(dev)) not in tables:
+                    tables[k1 - k0, str(dev)] = torch.empty(k1 - k0, 2, dtype=torch.int32, device=dev)
+                table = tables[k1 - k0, str(dev)]
+                table.copy_(origins[k0:k1])
+                eng.set_noise_tiles(table, sw)
             out = diffusion.p_sample_loop(cond, noise=nz)
             if out.dim() == 3:                # a call of ONE image comes back without its batch axis from the ddpm / tesr / gdp siblings
                 out = out[None]
@@ -254,6 +277,8 @@ def super_resolve_scene(diffusion, scene_u8, tile=256, overlap=32, batch=16, noi
                 log(f'scene: tiles {k0 + 1}..{k1} of {n}')
         return finish(acc, wsum)
     finally:
+        if noise == 'stream':
+            eng.clear_noise_tiles()
         diffusion.precision = old_precision
         unet.train(was_training)
 
@@ -275,7 +300,8 @@ def parse_args(argv=None):
     ap.add_argument('--precision', default='f16x3', choices=['f32', 'f16x3', 'bf16', 'f16'])
     ap.add_argument('--rng', default=None, choices=['torch', 'engine'])
     ap.add_argument('--seed', type=int, default=0)
-    ap.add_argument('--noise', default='scene', choices=['scene', 'tile'])
+    ap.add_argument('--noise', default='scene', choices=['scene', 'tile', 'stream'],
+                    help="'stream': the field of 'scene' drawn in the sampler's kernels, no array of the scene's size (needs --rng engine)")
     a = ap.parse_args(argv)
     if a.lr is not None and a.scale is None:
         ap.error('--lr requires --scale')
@@ -283,6 +309,8 @@ def parse_args(argv=None):
         ap.error('--scale applies to --lr only')
     if a.scale is not None and a.scale < 1:
         ap.error('--scale must be at least 1')
+    if a.noise == 'stream' and a.rng == 'torch':
+        ap.error('--noise stream requires --rng engine')
     return a
 
 

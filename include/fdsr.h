@@ -177,7 +177,8 @@ int fdsr_sample_stepwise(fdsr_handle h, const float* cond_nchw, const float* noi
  * explicit noise only. */
 /* The generator is Philox4x32-10 (Salmon et al., SC'11); 32-bit counter words (c0, c1, c2, c3) and key words (k0, k1):
  *   sampler noise, plane p      counter (i lo, i hi, p, calls lo)          key (seed lo, seed hi ^ calls hi)     i = n*H*W + pixel
- *   self-drawn training target  the same with p = 0 (fdsr_train_grads_pairs, noise == NULL)
+ *   the same, tile-addressed    the same with i = (y0[n] + y)*scene_w + (x0[n] + x) and `calls` left as it stands (fdsr_set_noise_tiles)
+ *   self-drawn training target  the first row with p = 0 (fdsr_train_grads_pairs, noise == NULL)
  *   dropout keep bytes          counter (quad lo, quad hi, slot, step)     key (seed lo ^ 0x44524F50, seed hi)   quad = NHWC element / 4
  * `calls` is zeroed by fdsr_set_seed; every fdsr_sample / fdsr_sample_stepwise that draws its own noise (a replayed graph too: the
  * counter lives on the device) and every training step that draws its own target adds one BEFORE drawing; fdsr_randn reads it.
@@ -195,6 +196,23 @@ int fdsr_set_seed(fdsr_handle h, uint64_t seed);
 /* Plane `plane` ([B,3,H,W] fp32, device) of the noise drawn under the current call counter
  * (plane 0 = x_T, plane k = step t = T-k).  For tests of the generator. */
 int fdsr_randn(fdsr_handle h, float* dst_nchw, int batch, int height, int width, int plane, void* hip_stream);
+/* Tile-addressed noise: the images of a call are tiles of one scene, and the engine draws for each pixel the number the scene's
+ * own noise field holds there -- without the field.
+ *   origins_dev [n_tiles][2] int32 on the device, (y0, x0) of image i of a call in a scene `scene_w` pixels wide; NULL: off.
+ * While a table is set, every normal that fdsr_sample / fdsr_sample_stepwise draw themselves (noise == NULL: x_T and the per-step
+ * noise) and every fdsr_randn is addressed by the pixel's place in the scene,
+ *   i = (y0[n] + y) * scene_w + (x0[n] + x)       (64-bit; image n, pixel (y, x) of the call)
+ * in place of i = n*H*W + pixel of the table above; planes, key and `calls` are as there.  Such a sampling call does NOT add one to
+ * `calls`: it draws under the counter as it stands, so after fdsr_set_seed every group of tiles draws under calls = 0, the value
+ * under which fdsr_randn(h, dst, 1, SH, SW, p) with no table writes plane p of the whole scene's field.  The tile at (y0, x0)
+ * therefore receives the crop [y0 : y0 + H, x0 : x0 + W] of that field bit for bit, and two tiles see the same numbers in the pixels
+ * they share, whatever T and the scene's size.
+ * The table is read when the kernels run, as the fdsr_scene_* tables are: keep it alive, and a captured graph stays valid while the
+ * caller rewrites the same buffer between replays (the graph caches key on the pointer and scene_w, so setting or clearing a table
+ * captures anew).  A call of more than n_tiles images is FDSR_E_INVALID: the kernels read entries [0, batch) and no others.
+ * The origins address a counter, not memory: one outside the scene cannot fault, it only draws other numbers.
+ * Not affected: an explicit `noise` array, the self-drawn training target (fdsr_train_grads_pairs), the dropout masks. */
+int fdsr_set_noise_tiles(fdsr_handle h, const int32_t* origins_dev, int n_tiles, int scene_w);
 
 /* Arithmetic of the convolutions (everything else is fp32 in every mode):
  *   FDSR_PREC_F32    exact fp32 on v_mfma_f32_32x32x2_f32 (default)
@@ -365,6 +383,16 @@ int fdsr_nafnet_randn(float* dst_nchw, int batch, int height, int width, int pla
                       void* hip_stream);
 int fdsr_upscale_bicubic_f32(const float* src_nchw, float* dst_nchw, int batch, int channels, int height, int width, int scale,
                              void* hip_stream);
+/* Tile-addressed noise for the NAFNet sampler, with fdsr_set_noise_tiles' table and semantics: while one is set, the normals
+ * fdsr_nafnet_sample draws itself (noise == NULL, SDE) have i = (y0[n] + y) * scene_w + (x0[n] + x) in their counter, so the tile at
+ * (y0, x0) draws the crop of what fdsr_nafnet_randn(dst, 1, SH, SW, k, seed, 0) writes for the whole scene.  first_image must be 0 in
+ * every fdsr_nafnet_sample while a table is set, and the batch at most n_tiles: else FDSR_E_INVALID.  The cached graph keys on the
+ * table's pointer and scene_w too; the table is read when the kernels run.  origins_dev == NULL: off.
+ * fdsr_nafnet_randn_tiles is fdsr_nafnet_randn for such tiles (it takes the table itself, as fdsr_nafnet_randn takes no object):
+ * origins_dev [batch][2].  The origins address a counter, not memory: one outside the scene only draws other numbers. */
+int fdsr_nafnet_set_noise_tiles(fdsr_nafnet n, const int32_t* origins_dev, int n_tiles, int scene_w);
+int fdsr_nafnet_randn_tiles(float* dst_nchw, int batch, int height, int width, int plane, uint64_t seed, const int32_t* origins_dev,
+                            int scene_w, void* hip_stream);
 void fdsr_nafnet_destroy(fdsr_nafnet n);
 /* Precision of the NAFNet's GEMMs (every 1x1 / 2x2 / 3x3 convolution that is not depthwise).
  *   fdsr_nafnet_set_precision   FDSR_PREC_F32 (default: the exact kernel above) or FDSR_PREC_F16X3: fp32-grade, the staged fp32
@@ -553,6 +581,10 @@ int fdsr_resize_bicubic_u8(fdsr_handle h, const uint8_t* src_nhwc, int batch, in
  * noise is required with a field and ignored without one. */
 int fdsr_scene_gather(fdsr_handle h, const uint8_t* scene_u8, const float* field, int planes, int scene_h, int scene_w,
                       const int32_t* origins, int n_tiles, int tile, float* cond, float* noise, void* hip_stream);
+/* fdsr_scene_gather_f32: the same cut for an fp32 image, scene [3,SH,SW] -> tiles [n,3,tile,tile], plain copies (the noise
+ * gather with one plane).  For conditioning that is not a uint8 image: EDiffSR's upscaled LQ scene in [0,1]. */
+int fdsr_scene_gather_f32(fdsr_handle h, const float* scene, int scene_h, int scene_w, const int32_t* origins, int n_tiles, int tile,
+                          float* tiles, void* hip_stream);
 /* fdsr_scene_blend adds n sampled tiles [n,3,tile,tile] fp32 into acc [3,SH,SW] and wsum [SH,SW] (fp32; the caller zeroes both
  * once per scene):   acc[c][y][x] = acc + fl(w * v),   wsum[y][x] = wsum + w,   w = fl32(wy(y) * wx(x)), where along an axis
  *   w1(i) = (i < lead ? (i + 1) / (lead + 1) : 1) * (i >= tile - trail ? (tile - i) / (trail + 1) : 1)       i = 0 .. tile - 1

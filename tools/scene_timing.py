@@ -4,9 +4,15 @@ shape (the scene's first group of tiles as its input), in one process, f16x3 and
 tiles/s of the scene over tiles/s of the bare sampler; the parts of a scene run (the noise field, one group's gather and blend, the facade call of a full group and of the last 1-tile group) are
 timed on their own so that a ratio below 1 can be attributed.
 
-    python tools/scene_timing.py [--out profiles/scene_timing.txt]
+Two more sets of rows (--rows picks; --append adds to the file under a header of its own):
+  stream   noise='stream' (drawn in the sampler's kernels, no field) beside noise='scene' (the field drawn once, cropped, passed as
+           explicit noise), both under rng='engine', same scene and process, alternating windows; peak device memory of each
+  ediffsr  EDiffSR (the shipped ConditionalNAFNet setting, IRSDE T = 100, --precision f16, noise='stream'): tiles/s of the same
+           2048 x 2048 scene at batch 16 against the bare ConditionalNAFNet.sample at B = 16 on the scene's first group
 
-Synthetic weights (synth.synth_state_dict, the flagship UNet); the cost does not depend on the weight values."""
+    python tools/scene_timing.py [--out profiles/scene_timing.txt] [--rows base stream ediffsr] [--append]
+
+Synthetic weights (synth.synth_state_dict, the flagship UNet; synth.synth_nafnet); the cost does not depend on the weight values."""
 import argparse
 import os
 import sys
@@ -54,9 +60,102 @@ def timed(fn, reps):
     return (time.perf_counter() - t0) / reps
 
 
+def peak_mib(fn):
+    """Peak device memory over one fn(), MiB: everything resident counts (weights, workspaces, graph buffers, the scene)."""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() / 2 ** 20
+
+
+def stream_rows(netG, scene, lines):
+    """noise='stream' beside noise='scene' under rng='engine': A B A B windows of two scenes each, then the peak memory of one run."""
+    from fastdiffsr_amd import scene as S
+    from fastdiffsr_amd.engine import Engine
+    n = len(S.plan_tiles(SCENE, SCENE, TILE, OVERLAP).origins)
+    netG.rng = 'engine'
+    try:
+        for prec in ('f16x3', 'f16'):
+            netG.precision = prec
+            runs = {m: (lambda m=m: S.super_resolve_scene(netG, scene, tile=TILE, overlap=OVERLAP, batch=BATCH, seed=0, noise=m))
+                    for m in ('scene', 'stream')}
+            for m in runs:
+                for _ in range(3):
+                    runs[m]()
+            # the two modes compute the same scene (tests/test_gpu_scene_stream.py): checked here on the eager loop, and the warmed-up
+            # graph replays of either mode are compared with that result
+            netG.graph = 'off'
+            eager = {m: runs[m]() for m in runs}
+            netG.graph = 'auto'
+            same = '%s; graph replays equal the eager scene: noise=scene %s, noise=stream %s' % (
+                torch.equal(eager['scene'], eager['stream']), torch.equal(runs['scene'](), eager['scene']),
+                torch.equal(runs['stream'](), eager['stream']))
+            del eager
+            ts = {m: [] for m in runs}
+            for _ in range(WINDOWS):
+                for m in runs:
+                    fb0 = Engine.saturation_fallbacks
+                    dt = timed(runs[m], 2)
+                    ts[m].append((dt, Engine.saturation_fallbacks - fb0))
+            mean = {m: (lambda c: sum(c) / len(c))([t for t, fb in ts[m] if fb == 0] or [t for t, _ in ts[m]]) for m in runs}
+            peaks = {m: peak_mib(runs[m]) for m in runs}
+            show = lambda v: ' '.join('%.3f%s' % (t, '*' * fb) for t, fb in v)   # noqa: E731
+            lines.append('%-5s rng=engine  noise=scene %7.3f s, %7.2f tiles/s, peak %6.0f MiB | noise=stream %7.3f s, %7.2f tiles/s, peak %6.0f MiB | '
+                         'stream / scene rate %.3f; uint8 scenes equal: %s  (windows: %s s / %s s; *: a range-guard re-run inside, left out of the means)' % (
+                             prec, mean['scene'], n / mean['scene'], peaks['scene'], mean['stream'], n / mean['stream'], peaks['stream'],
+                             mean['scene'] / mean['stream'], same, show(ts['scene']), show(ts['stream'])))
+    finally:
+        netG.rng = 'torch'
+
+
+EDIFFSR_SETTING = dict(width=64, enc_blk_nums=[14, 1, 1, 1], middle_blk_num=1, dec_blk_nums=[1, 1, 1, 1])   # the shipped options
+EDIFFSR_SDE = dict(max_sigma=50, T=100, schedule='cosine', eps=0.005)
+EDIFFSR_WINDOWS = 2      # a scene is 81 tiles x 100 forwards
+
+
+def ediffsr_row(lines):
+    from fastdiffsr_amd import scene as S
+    from fastdiffsr_amd.ediffsr import ConditionalNAFNet
+    from fastdiffsr_amd.ediffsr import scene as ES
+    from fastdiffsr_amd.ediffsr.model import upscale
+    from fastdiffsr_amd.ediffsr.sde import IRSDE
+    from fastdiffsr_amd.synth import synth_nafnet
+    net = ConditionalNAFNet(**EDIFFSR_SETTING)
+    net.load_state_dict({k: torch.from_numpy(v) for k, v in synth_nafnet(0, **EDIFFSR_SETTING).items()}, strict=True)
+    net = net.to('cuda').eval()
+    net.set_precision('f16')
+    sde = IRSDE(device='cuda', rng='engine', **EDIFFSR_SDE)
+    sde.set_model(net)
+    scale = 4
+    lq = torch.rand(3, SCENE // scale, SCENE // scale, device='cuda', generator=torch.Generator(device='cuda').manual_seed(1))
+    plan = S.plan_tiles(SCENE, SCENE, TILE, OVERLAP)
+    n = len(plan.origins)
+    origins, _ = S.plan_tables(plan, 'cuda')
+    run = lambda: ES.super_resolve_scene(net, sde, lq, scale, tile=TILE, overlap=OVERLAP, batch=BATCH, seed=0)   # noqa: E731
+    mu = ES.gather_f32(upscale(lq[None], scale)[0], origins[:BATCH], TILE)
+    state = mu + net.randn(BATCH, TILE, TILE, EDIFFSR_SDE['T'], 0) * sde.max_sigma
+    bare = lambda: net.sample(state, mu, noise=None, seed=0)   # noqa: E731
+    peak = peak_mib(run)          # the warm-up too
+    bare()
+    t_scene, t_bare = [], []
+    for _ in range(EDIFFSR_WINDOWS):
+        t_scene.append(timed(run, 1))
+        t_bare.append(timed(bare, 2))
+    m_scene, m_bare = sum(t_scene) / len(t_scene), sum(t_bare) / len(t_bare)
+    r_scene, r_bare = n / m_scene, BATCH / m_bare
+    lines.append('ediffsr f16 (width 64, enc 14-1-1-1, T = %d) noise=stream scene %7.3f s, %6.2f tiles/s, peak %6.0f MiB (a field would take %.2f GiB) | '
+                 'ConditionalNAFNet.sample B=%d engine-drawn noise, eager %8.1f ms per call, %6.2f tiles/s | ratio %.3f  (windows: %s s / %s ms)' % (
+                     EDIFFSR_SDE['T'], m_scene, r_scene, peak, S.noise_field_bytes(EDIFFSR_SDE['T'] + 1, SCENE, SCENE) / 2 ** 30, BATCH,
+                     1e3 * m_bare, r_bare, r_scene / r_bare, ' '.join('%.3f' % t for t in t_scene), ' '.join('%.1f' % (1e3 * t) for t in t_bare)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'scene_timing.txt'))
+    ap.add_argument('--rows', nargs='+', default=['base', 'stream', 'ediffsr'], choices=['base', 'stream', 'ediffsr'])
+    ap.add_argument('--append', action='store_true', help='add to --out under this run\'s own header, keeping what is there')
     a = ap.parse_args()
     from fastdiffsr_amd import scene as S
     from fastdiffsr_amd.engine import Engine
@@ -69,12 +168,12 @@ def main():
     origins, ramps = S.plan_tables(plan, 'cuda')
     T = netG.num_timesteps
     props = torch.cuda.get_device_properties(0)
-    lines = ['# python tools/scene_timing.py   (synthetic weights, synth.synth_state_dict(FASTDIFFSR_UNET, 0); T = %d)' % T,
+    lines = ['# python tools/scene_timing.py --rows %s   (synthetic weights, synth.synth_state_dict(FASTDIFFSR_UNET, 0); T = %d)' % (' '.join(a.rows), T),
              '# gpu, as the runtime names it: %s, %s, %d CUs, %.0f GiB' % (props.name, getattr(props, 'gcnArchName', '?'),
                                                                          props.multi_processor_count, props.total_memory / 2 ** 30),
              '# scene %dx%d, tile %d, overlap %d, batch %d: %d tiles = %d groups of %d and a last group of %d; noise field %.2f GiB' % (
                  SCENE, SCENE, TILE, OVERLAP, BATCH, n, n // BATCH, BATCH, n % BATCH, S.noise_field_bytes(T, SCENE, SCENE) / 2 ** 30)]
-    for prec in ('f16x3', 'f16'):
+    for prec in ('f16x3', 'f16') if 'base' in a.rows else ():
         netG.precision = prec
         run = lambda: S.super_resolve_scene(netG, scene, tile=TILE, overlap=OVERLAP, batch=BATCH, seed=0)   # noqa: E731
         for _ in range(3):       # warm-up: 'auto' captures a shape's graph on its second call, the 1-tile group's on the second scene
@@ -130,10 +229,16 @@ def main():
                          prec, 1e3 * t_field, BATCH, 1e3 * t_gather, 1e3 * t_blend, 1e3 * t_full, 1e3 * t_last, 1e3 * t_finish, parts))
         del field, acc, wsum, c16, n16, c1, n1, cond, noise, out
         torch.cuda.empty_cache()
+    if 'stream' in a.rows:
+        stream_rows(netG, scene, lines)
+    del netG, eng, scene
+    torch.cuda.empty_cache()
+    if 'ediffsr' in a.rows:
+        ediffsr_row(lines)
     text = '\n'.join(lines) + '\n'
     print(text, end='')
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
+    with open(a.out, 'a' if a.append else 'w') as f:
         f.write(text)
 
 
