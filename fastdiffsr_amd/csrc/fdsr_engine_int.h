@@ -147,8 +147,7 @@ struct fdsr_engine {
   // (weights, schedule) and the conv epilogues index it with batch stride 0.
   unsigned long long* d_rng = nullptr;   // {seed, call counter}: noise drawn by the engine (fdsr_sample, noise == NULL)
   unsigned long long rng_seed = 0;
-  const int32_t* noise_tiles = nullptr;  // fdsr_set_noise_tiles: the caller's device table of tile origins [noise_tiles_n][2], or null
-  int noise_tiles_n = 0, noise_scene_w = 0;
+  NoiseTileTable noise_tiles;            // fdsr_set_noise_tiles: the caller's device table of tile origins, or none
   int* h_sat = nullptr;            // pinned landing word of fdsr_check_saturation / the training step's own check
   int* d_sat = nullptr;            // f16x3 range guard: sticky flag raised by the raw-input staging paths
   float* d_temb_table = nullptr;

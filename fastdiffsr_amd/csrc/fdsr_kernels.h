@@ -290,6 +290,27 @@ struct NoiseTiles {
   int scene_w = 0;
   int W = 0;                      // width of the call's images
 };
+// The table a handle keeps between fdsr_set_noise_tiles / fdsr_nafnet_set_noise_tiles and its calls (host side; the memory is the
+// caller's).  Which calls it applies to is the call site's to say; how many images it serves and what a cleared one holds is said here.
+struct NoiseTileTable {
+  const int32_t* origins = nullptr;   // [n][2], device; null: no table
+  int n = 0, scene_w = 0;
+  // false: a table (origins_dev != null) needs n_tiles >= 1 and scene_w >= 1, and nothing is stored.  null clears: all zeros.
+  bool set(const int32_t* origins_dev, int n_tiles, int scene_width) {
+    if (origins_dev && (n_tiles < 1 || scene_width < 1)) return false;
+    origins = origins_dev;
+    n = origins_dev ? n_tiles : 0;
+    scene_w = origins_dev ? scene_width : 0;
+    return true;
+  }
+  // *out: how a call of `batch` W-wide images addresses its pixels (no table: by their place in the batch).  false: more images than origins.
+  bool for_call(int batch, int W, NoiseTiles* out) const {
+    *out = NoiseTiles{};
+    if (origins && batch > n) return false;
+    if (origins) *out = NoiseTiles{origins, scene_w, W};
+    return true;
+  }
+};
 
 // one reverse-diffusion update (diffusion.py:157-190) on the packed state tensor
 // xin [N,H,W,CP]: channels [0,3) = cond, [3,6) = x_t.

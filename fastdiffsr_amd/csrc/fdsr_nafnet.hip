@@ -551,9 +551,7 @@ struct fdsr_nafnet_obj {
   // one cached step graph
   struct { const void *cond = nullptr, *noise = nullptr, *out = nullptr, *traj = nullptr, *ws = nullptr; int N = 0, H = 0, W = 0, flags = 0;
            unsigned long long seed = 0; long long first = 0; const void* tiles = nullptr; int scene_w = 0; hipGraphExec_t exec = nullptr; } graph;
-  // fdsr_nafnet_set_noise_tiles: the caller's device table of tile origins [tiles_n][2] (null: none) and the scene's width
-  const int32_t* noise_tiles = nullptr;
-  int noise_tiles_n = 0, noise_scene_w = 0;
+  NoiseTileTable noise_tiles;    // fdsr_nafnet_set_noise_tiles: the caller's device table of tile origins, or none
 };
 
 namespace {
@@ -1411,12 +1409,13 @@ int fdsr_nafnet_sample(fdsr_nafnet n, const float* state_nchw, const float* cond
   if ((rc = ensure_table(n, st))) return rc;
   const int mode = (flags & FDSR_NAFNET_ODE) ? 2 : 1;
   // the table counts where the call draws its own noise: explicit noise and the ODE draw nothing
-  const int32_t* tiles = (!noise && mode == 1) ? n->noise_tiles : nullptr;
-  const int scene_w = tiles ? n->noise_scene_w : 0;
-  if (n->noise_tiles && first_image != 0)   // two ways to place an image in a larger whole: one at a time
+  NoiseTiles call_tiles;
+  if (n->noise_tiles.origins && first_image != 0)   // two ways to place an image in a larger whole: one at a time
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_sample: first_image must be 0 under a noise-tile table (got %lld)", (long long)first_image);
-  if (tiles && batch > n->noise_tiles_n)
-    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_sample: %d images under a noise-tile table of %d", batch, n->noise_tiles_n);
+  if (!noise && mode == 1 && !n->noise_tiles.for_call(batch, width, &call_tiles))
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_sample: %d images under a noise-tile table of %d", batch, n->noise_tiles.n);
+  const int32_t* tiles = call_tiles.origins;
+  const int scene_w = call_tiles.scene_w;
   HIPCHK(nullptr, hipMemcpyAsync(out_nchw, state_nchw, (size_t)batch * 3 * height * width * sizeof(float), hipMemcpyDeviceToDevice, st));
   HIPCHK(nullptr, hipMemsetAsync(n->d_ctl, 0, sizeof(int), st));
   Run r = sample_run(n, batch, height, width, workspace, st, n->d_cur_row, 0);
@@ -1457,11 +1456,8 @@ int fdsr_nafnet_randn(float* dst_nchw, int batch, int height, int width, int pla
 }
 
 int fdsr_nafnet_set_noise_tiles(fdsr_nafnet n, const int32_t* origins_dev, int n_tiles, int scene_w) {
-  if (!n || (origins_dev && (n_tiles < 1 || scene_w < 1)))
+  if (!n || !n->noise_tiles.set(origins_dev, n_tiles, scene_w))
     return fail(nullptr, FDSR_E_INVALID, "fdsr_nafnet_set_noise_tiles: a table needs n_tiles >= 1 and scene_w >= 1 (got %d, %d)", n_tiles, scene_w);
-  n->noise_tiles = origins_dev;
-  n->noise_tiles_n = origins_dev ? n_tiles : 0;
-  n->noise_scene_w = origins_dev ? scene_w : 0;
   return FDSR_OK;
 }
 

@@ -276,13 +276,8 @@ int sample_prepare(fdsr_handle h, SampleCall* c, void* workspace, size_t workspa
   c->ws = reinterpret_cast<char*>(workspace);
   if ((rc = apply_plan(h, fdsr_forms::need_sample(h->forms, h->prec, stepwise), c->st))) return rc;   // optimiser steps moved the master copy
   if (!c->noise && (rc = ensure_rng(h))) return rc;
-  if (!c->noise && h->noise_tiles) {
-    if (c->N > h->noise_tiles_n)
-      return fail(h, FDSR_E_INVALID, "a call of %d images under a noise-tile table of %d (fdsr_set_noise_tiles)", c->N, h->noise_tiles_n);
-    c->tiles.origins = h->noise_tiles;
-    c->tiles.scene_w = h->noise_scene_w;
-    c->tiles.W = c->W;
-  }
+  if (!c->noise && !h->noise_tiles.for_call(c->N, c->W, &c->tiles))   // the table counts where the call draws its own noise
+    return fail(h, FDSR_E_INVALID, "a call of %d images under a noise-tile table of %d (fdsr_set_noise_tiles)", c->N, h->noise_tiles.n);
   if ((flags & FDSR_SAMPLE_GRAPH) && c->st == nullptr)
     return fail(h, FDSR_E_INVALID, "FDSR_SAMPLE_GRAPH needs a non-default stream (stream capture cannot run on the NULL stream)");
   c->use_graph = (flags & FDSR_SAMPLE_GRAPH) && !h->profiling;
@@ -341,24 +336,16 @@ int fdsr_randn(fdsr_handle h, float* dst_nchw, int batch, int height, int width,
   int rc = ensure_rng(h);
   if (rc) return rc;
   NoiseTiles tiles;
-  if (h->noise_tiles) {
-    if (batch > h->noise_tiles_n)
-      return fail(h, FDSR_E_INVALID, "fdsr_randn: %d images under a noise-tile table of %d (fdsr_set_noise_tiles)", batch, h->noise_tiles_n);
-    tiles.origins = h->noise_tiles;
-    tiles.scene_w = h->noise_scene_w;
-    tiles.W = width;
-  }
+  if (!h->noise_tiles.for_call(batch, width, &tiles))
+    return fail(h, FDSR_E_INVALID, "fdsr_randn: %d images under a noise-tile table of %d (fdsr_set_noise_tiles)", batch, h->noise_tiles.n);
   HIPCHK(h, launch_randn_plane(h->d_rng, dst_nchw, batch, height * width, plane, reinterpret_cast<hipStream_t>(hip_stream), 0, tiles));
   return FDSR_OK;
 }
 
 int fdsr_set_noise_tiles(fdsr_handle h, const int32_t* origins_dev, int n_tiles, int scene_w) {
   if (!h) return FDSR_E_INVALID;
-  if (origins_dev && (n_tiles < 1 || scene_w < 1))
+  if (!h->noise_tiles.set(origins_dev, n_tiles, scene_w))
     return fail(h, FDSR_E_INVALID, "fdsr_set_noise_tiles: a table needs n_tiles >= 1 and scene_w >= 1 (got %d, %d)", n_tiles, scene_w);
-  h->noise_tiles = origins_dev;
-  h->noise_tiles_n = origins_dev ? n_tiles : 0;
-  h->noise_scene_w = origins_dev ? scene_w : 0;
   return FDSR_OK;
 }
 

@@ -16,6 +16,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
+from ..scene import check_origins
 from .arch import NAFNetConfig, param_schema, tap_names
 
 
@@ -443,10 +444,7 @@ class ConditionalNAFNet(nn.Module):
         i of a call in a scene `scene_w` wide.  Until clear_noise_tiles, what sample draws itself (noise=None) and randn are the
         crops of the scene's planes at those origins; first_image must then be 0.  The table is read when the kernels run: the
         module keeps the tensor, and the caller may rewrite it in place between calls."""
-        if not (origins.is_cuda and origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.shape[0] >= 1
-                and origins.is_contiguous()):
-            raise ValueError('origins must be a contiguous CUDA int32 tensor [n,2] with n >= 1')
-        _lib.check(None, _lib.load().fdsr_nafnet_set_noise_tiles(self._handle(), _ptr(origins), int(origins.shape[0]), int(scene_w)))
+        _lib.check(None, _lib.load().fdsr_nafnet_set_noise_tiles(self._handle(), _ptr(origins), check_origins(origins), int(scene_w)))
         self._noise_tiles = (origins, int(scene_w))
 
     def clear_noise_tiles(self):

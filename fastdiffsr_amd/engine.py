@@ -7,6 +7,7 @@ import torch
 
 from . import _lib
 from .arch import UNetConfig
+from .scene import check_origins
 
 
 LOSS_TYPES = {'l1': 0, 'l2': 1, 'charbonnier': 2}     # include/fdsr.h: loss_l2 of fdsr_train_grads
@@ -246,10 +247,7 @@ class Engine:
         call in a scene `scene_w` wide.  Until clear_noise_tiles, what sample draws itself (noise=None) and randn are the crops of
         the scene's field at those origins, and such a sample leaves the call counter where it is.  The table is read when the
         kernels run: the engine keeps the tensor, and the caller may rewrite it in place between calls."""
-        if not (origins.is_cuda and origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.shape[0] >= 1
-                and origins.is_contiguous()):
-            raise ValueError('origins must be a contiguous CUDA int32 tensor [n,2] with n >= 1')
-        _lib.check(self.h, self.lib.fdsr_set_noise_tiles(self.h, _ptr(origins), int(origins.shape[0]), int(scene_w)))
+        _lib.check(self.h, self.lib.fdsr_set_noise_tiles(self.h, _ptr(origins), check_origins(origins), int(scene_w)))
         self._noise_tiles = origins
 
     def clear_noise_tiles(self):

@@ -13,6 +13,8 @@ The reference has no such driver (its data are pre-cut patches); this is the lay
             pixel's place in the scene (Engine.set_noise_tiles), bit for bit what the crop would hold, at any T and any scene size.
   device    fdsr_scene_gather (scene -> cond / noise tiles), the sampler, fdsr_scene_blend (tiles -> acc, wsum), fdsr_scene_finish
             (acc / wsum -> uint8), csrc/fdsr_scene.hip; nothing of a scene's size crosses PCIe but the input and the result
+  shared    with ediffsr/scene.py, which imports them: `walk`, `stream_table`, `check_request`, `check_origins`, both gathers and
+            `timed_scene`; a driver keeps its model's side -- what a group's cond / state / noise are, and the sampling call
 
 Every tile is its own sampling chain: GroupNorm statistics are per tile, so a tiled result is NOT the result of one untiled call
 (DESIGN, "Whole-scene sampling").  What holds exactly: reruns are bitwise equal, with a single tile the result is the untiled path
@@ -137,15 +139,22 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def check_origins(origins):
+    """What every reader of a tile table requires of it (the kernels read n pairs of int32 at its address); -> n."""
+    import torch
+    if not (origins.is_cuda and origins.dtype == torch.int32 and origins.dim() == 2 and origins.shape[1] == 2 and origins.shape[0] >= 1
+            and origins.is_contiguous()):
+        raise ValueError('origins must be a contiguous CUDA int32 tensor [n,2] with n >= 1')
+    return int(origins.shape[0])
+
+
 def gather(scene_u8, field, origins, tile):
     """fdsr_scene_gather: scene_u8 [SH,SW,3] uint8, field [P,3,SH,SW] fp32 or None, origins [n,2] int32 (all on the device) ->
     (cond [n,3,t,t], noise [P,n,3,t,t] or None)."""
     import torch
     from . import _lib
     sh, sw, _ = scene_u8.shape
-    n = int(origins.shape[0])
-    if origins.dim() != 2 or origins.shape[1] != 2 or n < 1:
-        raise ValueError(f'origins must be [n,2] with n >= 1 (got {tuple(origins.shape)})')
+    n = check_origins(origins)
     dev = scene_u8.device
     cond = torch.empty(n, 3, tile, tile, device=dev, dtype=torch.float32)
     planes = int(field.shape[0]) if field is not None else 0
@@ -154,6 +163,23 @@ def gather(scene_u8, field, origins, tile):
     _lib.check(None, _lib.load().fdsr_scene_gather(None, _ptr(scene_u8), _ptr(field), planes, sh, sw, _ptr(origins), n, tile,
                                                    _ptr(cond), _ptr(noise), C.c_void_p(st)))
     return cond, noise
+
+
+def gather_f32(scene, origins, tile, out=None):
+    """fdsr_scene_gather_f32: scene [3,SH,SW] fp32, origins [n,2] int32 (on the device) -> tiles [n,3,t,t]."""
+    import torch
+    from . import _lib
+    if not (scene.is_cuda and scene.dtype == torch.float32 and scene.dim() == 3 and scene.shape[0] == 3 and scene.is_contiguous()):
+        raise ValueError('scene must be a contiguous CUDA fp32 tensor [3,SH,SW]')
+    n = check_origins(origins)
+    _, sh, sw = scene.shape
+    if out is None:
+        out = torch.empty(n, 3, tile, tile, device=scene.device, dtype=torch.float32)
+    elif tuple(out.shape) != (n, 3, tile, tile) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != scene.device:
+        raise ValueError(f'out must be a contiguous fp32 tensor [{n},3,{tile},{tile}] on the scene\'s device')
+    st = torch.cuda.current_stream(scene.device).cuda_stream
+    _lib.check(None, _lib.load().fdsr_scene_gather_f32(None, _ptr(scene), sh, sw, _ptr(origins), n, tile, _ptr(out), C.c_void_p(st)))
+    return out
 
 
 def blend(tiles, origins, ramps, acc, wsum):
@@ -188,6 +214,57 @@ def plan_tables(plan, device):
             torch.tensor(plan.ramps, dtype=torch.int32, device=device).reshape(-1, 4).contiguous())
 
 
+def check_request(noise, batch, modes):
+    """The refusals both drivers make of their `noise` and `batch` arguments; modes: the driver's noise modes, its default first."""
+    if noise not in modes:
+        raise ValueError(f'noise must be one of {tuple(modes)} (got {noise!r})')
+    if int(batch) < 1:
+        raise ValueError('batch must be at least 1')
+
+
+def stream_table(owner, origins, scene_w):
+    """noise='stream': `origins` [b,2] copied into the owner's int32 buffer for groups of b and handed to owner.set_noise_tiles.  One
+    buffer per (b, device), kept with the owner (an Engine or a ConditionalNAFNet) from its first use: the samplers' graph caches key
+    on its address, so full groups replay one graph and a later scene finds the graphs an earlier one captured."""
+    import torch
+    tables = owner.__dict__.setdefault('_scene_tables', {})
+    key = (int(origins.shape[0]), str(origins.device))
+    if key not in tables:
+        tables[key] = torch.empty(key[0], 2, dtype=torch.int32, device=origins.device)
+    tables[key].copy_(origins)
+    owner.set_noise_tiles(tables[key], scene_w)
+    return tables[key]
+
+
+def walk(plan, device, group, sample_group, stream=None, log=None):
+    """The scene walk of both drivers: the plan's tiles in groups of `group` in plan order (the last group smaller, never padded),
+    each sampled by sample_group(k0, k1, origins[k0:k1]) -> [k1-k0,3,t,t] fp32 and blended.  -> (acc [3,SH,SW], wsum [SH,SW]).
+    stream: under noise='stream' the engine or network that draws -- each group's origins go into its `stream_table` before
+    sample_group runs, and its table is cleared on the way out, whatever happened.  log: called with one line per group."""
+    import torch
+    n = len(plan.origins)
+    origins, ramps = plan_tables(plan, device)
+    acc = torch.zeros(3, plan.scene_h, plan.scene_w, device=device, dtype=torch.float32)
+    wsum = torch.zeros(plan.scene_h, plan.scene_w, device=device, dtype=torch.float32)
+    try:
+        for k0 in range(0, n, group):
+            k1 = min(k0 + group, n)
+            if stream is not None:
+                stream_table(stream, origins[k0:k1], plan.scene_w)
+            out = sample_group(k0, k1, origins[k0:k1])
+            if out.dim() == 3:                # a call of ONE image comes back without its batch axis from the ddpm / tesr / gdp siblings
+                out = out[None]
+            if out.shape[0] != k1 - k0:
+                raise RuntimeError(f'p_sample_loop returned {out.shape[0]} image(s) for {k1 - k0} tiles')
+            blend(out.contiguous(), origins[k0:k1], ramps[k0:k1], acc, wsum)
+            if log is not None:
+                log(f'scene: tiles {k0 + 1}..{k1} of {n}')
+    finally:
+        if stream is not None:
+            stream.clear_noise_tiles()
+    return acc, wsum
+
+
 def tiles_per_call(diffusion, batch):
     """How many tiles one p_sample_loop call of this facade can sample: `batch`, but 1 for the tesr and gdp siblings, whose
     p_sample_loop returns ret_img[-1] -- the LAST image of its batch -- as the reference's does (their `_result`; val.py refuses
@@ -216,21 +293,17 @@ def super_resolve_scene(diffusion, scene_u8, tile=256, overlap=32, batch=16, noi
     torch's global stream alone.
 
     noise='stream' (rng='engine' only; ValueError under rng='torch'): no field is drawn and noise_budget is not consulted.
-    set_seed(seed) once, then per group the group's origins are copied into one device buffer per group size (full groups replay
-    one graph, which reads the buffer when it runs), Engine.set_noise_tiles points the sampler at it and p_sample_loop(cond) draws
-    its own noise: for the tile at (y0, x0) the crop of the field noise='scene' would have drawn, so the result equals
+    set_seed(seed) once, then per group the walk points the sampler at the group's origins (`stream_table`) and p_sample_loop(cond)
+    draws its own noise: for the tile at (y0, x0) the crop of the field noise='scene' would have drawn, so the result equals
     noise='scene' bit for bit.  Such calls leave the engine's call counter at 0, where set_seed put it; the table is cleared on the
     way out.  The f16x3 range guard's re-run of a call (Engine.on_saturation) therefore redraws the SAME noise here: the counter
     does not move, and the numbers depend on nothing else."""
     import torch
     if not scene_u8.is_cuda or scene_u8.dtype != torch.uint8 or scene_u8.dim() != 3 or scene_u8.shape[-1] != 3:
         raise ValueError('scene_u8 must be a CUDA uint8 tensor of shape [SH,SW,3]')
-    if noise not in ('scene', 'tile', 'stream'):
-        raise ValueError(f"noise must be 'scene', 'tile' or 'stream' (got {noise!r})")
+    check_request(noise, batch, ('scene', 'tile', 'stream'))
     if noise == 'stream' and diffusion.rng != 'engine':
         raise ValueError(f"noise='stream' draws in the engine's kernels and requires rng='engine' (the facade's rng is {diffusion.rng!r})")
-    if int(batch) < 1:
-        raise ValueError('batch must be at least 1')
     scene_u8 = scene_u8.contiguous()
     dev = scene_u8.device
     sh, sw, _ = scene_u8.shape
@@ -238,7 +311,6 @@ def super_resolve_scene(diffusion, scene_u8, tile=256, overlap=32, batch=16, noi
     eng = unet.engine
     eng.workspace_bytes(1, tile, tile)        # a tile the network does not take is refused here, in the engine's own words
     plan = plan_tiles(sh, sw, tile, overlap, multiple=1 << (len(unet.cfg.channel_mults) - 1))
-    n = len(plan.origins)
     if noise == 'scene':
         check_noise_budget(_planes(diffusion), sh, sw, noise_budget)
     old_precision, was_training = diffusion.precision, unet.training
@@ -247,43 +319,42 @@ def super_resolve_scene(diffusion, scene_u8, tile=256, overlap=32, batch=16, noi
     unet.train(False)                         # as DDPM.test does around a sampling call: no live Dropout
     try:
         field = scene_noise_field(diffusion, sh, sw, seed, dev) if noise == 'scene' else None
-        origins, ramps = plan_tables(plan, dev)
-        acc = torch.zeros(3, sh, sw, device=dev, dtype=torch.float32)
-        wsum = torch.zeros(sh, sw, device=dev, dtype=torch.float32)
-        group = tiles_per_call(diffusion, batch)
-        # noise='stream': group size -> the device buffer its calls read their origins from; kept with the engine, so that a later
-        # scene finds the graphs this one captured (they key on the buffer's address)
-        tables = eng.__dict__.setdefault('_scene_tables', {})
         if noise == 'stream':
             eng.set_seed(seed)
-        for k0 in range(0, n, group):
-            k1 = min(k0 + group, n)
-            cond, nz = gather(scene_u8, field, origins[k0:k1], tile)
+
+        def sample_group(k0, k1, origins):
+            cond, nz = gather(scene_u8, field, origins, tile)
             if noise == 'tile':
                 nz = torch.cat([tile_noise(diffusion, tile, seed, k, dev) for k in range(k0, k1)], dim=1)
-            elif noise == 'stream':
-                if (k1 - k0, str(dev)) not in tables:
-                    tables[k1 - k0, str(dev)] = torch.empty(k1 - k0, 2, dtype=torch.int32, device=dev)
-                table = tables[k1 - k0, str(dev)]
-                table.copy_(origins[k0:k1])
-                eng.set_noise_tiles(table, sw)
-            out = diffusion.p_sample_loop(cond, noise=nz)
-            if out.dim() == 3:                # a call of ONE image comes back without its batch axis from the ddpm / tesr / gdp siblings
-                out = out[None]
-            if out.shape[0] != k1 - k0:
-                raise RuntimeError(f'p_sample_loop returned {out.shape[0]} image(s) for {k1 - k0} tiles')
-            blend(out.contiguous(), origins[k0:k1], ramps[k0:k1], acc, wsum)
-            if log is not None:
-                log(f'scene: tiles {k0 + 1}..{k1} of {n}')
-        return finish(acc, wsum)
+            return diffusion.p_sample_loop(cond, noise=nz)    # under 'stream' nz is None: the sampler draws, by the walk's table
+
+        group = tiles_per_call(diffusion, batch)
+        return finish(*walk(plan, dev, group, sample_group, stream=eng if noise == 'stream' else None, log=log))
     finally:
-        if noise == 'stream':
-            eng.clear_noise_tiles()
         diffusion.precision = old_precision
         unet.train(was_training)
 
 
 # -- CLI ------------------------------------------------------------------------------------------------------------------
+def timed_scene(a, run):
+    """The tail of both CLIs: time run() -> the [SH,SW,3] uint8 scene, save it to a.out, print the summary line, return it as a dict."""
+    import torch
+    from PIL import Image
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    t0 = time.perf_counter()
+    out = run()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    sh, sw, _ = out.shape
+    tiles = len(plan_tiles(sh, sw, a.tile, a.overlap).origins)
+    Image.fromarray(out.cpu().numpy()).save(a.out)
+    peak = torch.cuda.max_memory_allocated() / 2 ** 20
+    print(f'scene {sh}x{sw}: {tiles} tiles of {a.tile} (overlap {a.overlap}, batch {a.batch}, noise {a.noise}) in {dt:.3f} s, '
+          f'{tiles / dt:.2f} tiles/s, peak device memory {peak:.0f} MiB -> {a.out}')
+    return dict(tiles=tiles, seconds=dt, tiles_per_second=tiles / dt, peak_mib=peak, out=a.out, shape=(sh, sw))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog='python -m fastdiffsr_amd.scene', description=__doc__,
                                  formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -333,20 +404,8 @@ def main(argv=None):
         h, w, _ = img.shape
         _, up = lr_to_sr(img[None], h * a.scale, w * a.scale, want_u8=True)     # the scene, not the tiles: borders see their neighbours
         img = up[0]
-    sh, sw, _ = img.shape
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    t0 = time.perf_counter()
-    out = super_resolve_scene(diffusion.netG, img, tile=a.tile, overlap=a.overlap, batch=a.batch, noise=a.noise, seed=a.seed,
-                              precision=a.precision)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    tiles = len(plan_tiles(sh, sw, a.tile, a.overlap).origins)
-    Image.fromarray(out.cpu().numpy()).save(a.out)
-    peak = torch.cuda.max_memory_allocated() / 2 ** 20
-    print(f'scene {sh}x{sw}: {tiles} tiles of {a.tile} (overlap {a.overlap}, batch {a.batch}, noise {a.noise}) in {dt:.3f} s, '
-          f'{tiles / dt:.2f} tiles/s, peak device memory {peak:.0f} MiB -> {a.out}')
-    return dict(tiles=tiles, seconds=dt, tiles_per_second=tiles / dt, peak_mib=peak, out=a.out, shape=(sh, sw))
+    return timed_scene(a, lambda: super_resolve_scene(diffusion.netG, img, tile=a.tile, overlap=a.overlap, batch=a.batch, noise=a.noise,
+                                                      seed=a.seed, precision=a.precision))
 
 
 if __name__ == '__main__':

@@ -96,6 +96,51 @@ def test_stream_equals_scene_whatever_the_batch(pair):
     assert torch.equal(_scene(pair, lq, seed=11, noise_budget=1), want)       # 'stream' (the default) has no field to budget
 
 
+def test_a_second_scene_finds_the_first_one_s_tables(pair):
+    """The per-group-size origins buffers stay with the network (scene.stream_table): a second scene writes into the same memory --
+    the address the step graph keys on -- and gives the same bytes."""
+    net, sde = pair
+    lq = _lq(15, 19, 2)
+    first = _scene(pair, lq, seed=11, noise='stream', batch=4)
+    ptrs = {k: t.data_ptr() for k, t in net._scene_tables.items()}
+    assert {k[0] for k in ptrs} >= {4, 1}                     # nine tiles: groups of 4, 4 and 1
+    second = _scene(pair, lq, seed=11, noise='stream', batch=4)
+    assert {k: t.data_ptr() for k, t in net._scene_tables.items()} == ptrs
+    assert torch.equal(second, first) and len(torch.unique(first)) > 16
+
+
+def test_a_group_that_comes_back_short_is_refused(pair, monkeypatch):
+    from fastdiffsr_amd.ediffsr import test as T
+    net, sde = pair
+    real = T.reverse_sde_guarded
+    monkeypatch.setattr(T, 'reverse_sde_guarded', lambda *a, **kw: real(*a, **kw)[:-1])
+    with pytest.raises(RuntimeError, match=r'returned 3 image\(s\) for 4 tiles'):
+        _scene(pair, _lq(15, 19, 2), seed=11, batch=4)
+    assert getattr(net, '_noise_tiles', None) is None         # 'stream': the table is cleared on the way out
+
+
+def test_both_setters_refuse_a_bad_table_in_the_same_words(pair):
+    from fastdiffsr_amd import scene as S
+    from fastdiffsr_amd.arch import UNetConfig
+    from fastdiffsr_amd.engine import Engine
+    net, _ = pair
+    eng = Engine(UNetConfig(in_channel=6, out_channel=3, inner_channel=32, norm_groups=32, channel_mults=(1, 2, 4, 4), attn_res=(),
+                            res_blocks=1, dropout=0.0, image_size=32))
+    good = torch.zeros(4, 2, dtype=torch.int32, device=DEV)
+    bad = {'not int32': good.long(), 'not contiguous': torch.zeros(4, 4, dtype=torch.int32, device=DEV)[:, ::2],
+           '[n,3]': torch.zeros(4, 3, dtype=torch.int32, device=DEV), 'empty': good[:0], 'on the host': good.cpu()}
+    assert tuple(bad['not contiguous'].shape) == (4, 2) and not bad['not contiguous'].is_contiguous()
+    for what, t in bad.items():
+        said = []
+        for call in (lambda: eng.set_noise_tiles(t, 76), lambda: net.set_noise_tiles(t, 76), lambda: S.check_origins(t)):
+            with pytest.raises(ValueError, match='origins must be a contiguous CUDA int32 tensor') as e:
+                call()
+            said.append(str(e.value))
+        assert said[0] == said[1] == said[2], what
+    assert getattr(eng, '_noise_tiles', None) is None and getattr(net, '_noise_tiles', None) is None   # nothing was set
+    assert S.check_origins(good) == 4
+
+
 def test_zero_overlap_tiles_are_their_own_samples(pair):
     from fastdiffsr_amd import metrics as M
     from fastdiffsr_amd.ediffsr.model import upscale

@@ -124,6 +124,20 @@ def test_stream_equals_scene(sh, sw, overlap, batch, graph):
         assert not torch.equal(_run(_facade(), _scene(sh, sw, 3), overlap=overlap, batch=4, noise='stream', seed=12), want)
 
 
+def test_a_second_scene_finds_the_first_one_s_tables():
+    """The per-group-size origins buffers stay with the engine (S.stream_table): a second scene writes into the same memory -- the
+    address the sampler's graphs key on -- and gives the same bytes.  Eagerly: what is checked is the driver's buffer, not a replay."""
+    netG = _facade()
+    eng = netG.denoise_fn.engine
+    scene = _scene(60, 76, 3)
+    first = _run(netG, scene, overlap=8, batch=4, noise='stream', seed=11)
+    ptrs = {k: t.data_ptr() for k, t in eng._scene_tables.items()}
+    assert {k[0] for k in ptrs} >= {4, 1}                     # nine tiles: groups of 4, 4 and 1
+    second = _run(netG, scene, overlap=8, batch=4, noise='stream', seed=11)
+    assert {k: t.data_ptr() for k, t in eng._scene_tables.items()} == ptrs
+    assert torch.equal(second, first) and torch.equal(first, _want(60, 76, 8))
+
+
 def test_stepwise_sibling():
     """ddpm at the smallest T that takes fdsr_sample_stepwise: posterior_step_kernel draws, eagerly and as replayed chunks; 40x56 is
     four tiles, batch 3 a group of three and one of one."""
