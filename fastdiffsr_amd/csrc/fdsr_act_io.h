@@ -18,6 +18,15 @@ __device__ __forceinline__ void sat_check(int* flag, f32x4 v, float lim) {
   const float m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
   if (m > lim) *flag = 1;
 }
+// The same guard for a K loop: the staging folds max|v| of every raw quad into one register per thread (the fmaxf chain of
+// sat_check: a NaN never raises the flag, a halo stand-in pixel counts like any other), and the thread raises the flag with ONE
+// guarded store behind its last K chunk.  A store -- or a branch around one -- inside the loop costs every wait behind it its count.
+__device__ __forceinline__ float sat_fold(float m, f32x4 v) {
+  return fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+}
+__device__ __forceinline__ void sat_raise(int* flag, float m, float lim) {
+  if (flag && m > lim) *flag = 1;
+}
 // the XCD this wave runs on (HW_REG_XCC_ID[3:0]): the shard of the consumer-side GroupNorm tables its workgroup adds to
 __device__ __forceinline__ int xcc_id() {
   unsigned v;

@@ -68,12 +68,18 @@ struct ChunkSrc {
   int cbase;           // the chunk's first channel within its (concatenated) input
   bool gn;             // GroupNorm scale / shift apply
 };
-template <bool RIDER>
+// What a loop knows about the chunks it stages, at compile time: all main chunks, all rider chunks, or either (told apart by
+// kc >= nk at run time).  A loop of one kind carries no test of kc: its loads, waits and staging arithmetic are straight-line.
+enum ChunkKind { CHUNK_MAIN = 0, CHUNK_RIDER = 1, CHUNK_ANY = 2 };
+template <int KIND>
+__device__ __forceinline__ bool chunk_is_rider(int kc, int nk) { return KIND == CHUNK_ANY ? kc >= nk : KIND == CHUNK_RIDER; }
+
+template <bool RIDER, int KIND = (RIDER ? CHUNK_ANY : CHUNK_MAIN)>
 __device__ __forceinline__ ChunkSrc chunk_src(const ConvParams& p, int kc, int KC, int nk, int q, bool gn) {
   ChunkSrc s;
   s.cbase = kc * KC;
   s.gn = gn;
-  if (RIDER && kc >= nk) {
+  if (RIDER && chunk_is_rider<KIND>(kc, nk)) {
     s.cbase -= nk * KC;
     s.gn = false;
     if (s.cbase < p.Cr0) { s.base = p.xr0; s.Cs = p.Cr0; s.cc = s.cbase + q * 4; }

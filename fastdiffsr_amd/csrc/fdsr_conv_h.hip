@@ -130,6 +130,7 @@ __global__ void __launch_bounds__(512, 2) conv_mfma_h_kernel(const ConvParams p)
   Quad rin[NIN];
   Quad rin2[RIDER ? NIN : 1];   // second prefetch set: the short rider chunks fetch two chunks ahead
   f32x4 rsc = {1.f, 1.f, 1.f, 1.f}, rsh = {0.f, 0.f, 0.f, 0.f};
+  float satm = 0.f;   // f16x3 range guard: max |v| over the raw quads this thread staged (fdsr_act_io.h)
   const int nk = p.Cin_pad / KC;               // main chunks; chunks nk .. nk + nkr - 1 are the rider's (raw second input, centre tap)
   auto prefetch_to = [&](int kc, Quad* rin) {
     const ChunkSrc src = chunk_src<RIDER>(p, kc, KC, nk, q, gn);
@@ -150,8 +151,8 @@ __global__ void __launch_bounds__(512, 2) conv_mfma_h_kernel(const ConvParams p)
       f32x4 v = IO::widen(rin[i]);
       if (gn && !(RIDER && kc >= nk)) {
         v = gn_act4(v, sc, sh, p.gn_plain);
-      } else if (PREC == PREC_F16X3 && p.sat_flag) {
-        sat_check(p.sat_flag, v, 65504.f);             // a raw input the split below would clamp: tell the host
+      } else if (PREC == PREC_F16X3) {
+        satm = sat_fold(satm, v);                      // a raw input the split below would clamp: tell the host (behind the K loops)
       }
       const float keep = in_pix[i] >= 0 ? 1.f : 0.f;   // conv zero-pads the ACTIVATED tensor
       const float lim = in_pix[i] >= 0 ? 65504.f : 0.f;   // f16 range clamp and zero padding in one med3
@@ -310,6 +311,7 @@ __global__ void __launch_bounds__(512, 2) conv_mfma_h_kernel(const ConvParams p)
       if (kc + 1 < kc1) rider_chunk(kc + 1, rin2, rin);
     }
   }
+  if (PREC == PREC_F16X3) sat_raise(p.sat_flag, satm, 65504.f);   // the range guard's one store, behind the last K chunk
 
   // ---- epilogue.  Interior tiles take a branch-free path: per-element bounds branches make the
   // compiler wait vmcnt(0) before every store.  Each lane also sums its outputs per channel

@@ -108,7 +108,7 @@ __device__ __forceinline__ int k32_slot(int slot, int hx) {
 // GNB: the GroupNorm-backward epilogue of the training step's input-gradient launches (ConvParams::gb_*)
 // DROP: train-mode Dropout between the Swish and the convolution applied in the staging (ConvParams::drop_mask; f16x3 training forwards)
 // GNC: GroupNorm scale / shift formed HERE, in the prologue, from the producers' fixed-point pair sums (ConvParams::gs0; small grids)
-template <int TH, int WN, int PREC, bool RIDER, int NW = 8, bool RF = (NW == 4), bool GNB = false, bool DROP = false, bool GNC = false>   // RF: rider chunks first (launches without a K split)
+template <int TH, int WN, int PREC, bool RIDER, int NW = 8, bool RF = (NW == 4), bool GNB = false, bool DROP = false, bool GNC = false, bool GS_ = false>   // RF: rider chunks first (launches without a K split); GS_: every main chunk is GroupNorm'ed + Swish'ed (the launcher's choice)
 __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p) {
   using Cfg = ConvK32Cfg<TH, WN, PREC, NW>;
   constexpr int TW = Cfg::TW, KC = Cfg::KC, NP = Cfg::NP, ROWB = Cfg::ROWB, HWD = Cfg::HWD, NPIX = Cfg::NPIX;
@@ -260,9 +260,21 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
     }
     __syncthreads();
   };
-  auto prefetch_rng = [&](int kc, QM* rin, auto i0_tag, auto i1_tag, bool load_gn) __attribute__((always_inline)) {
-    constexpr int I0 = decltype(i0_tag)::value, I1 = decltype(i1_tag)::value;
-    const ChunkSrc src = chunk_src<RIDER>(p, kc, KC, nk, q, gn);
+  // What a K loop knows of the chunks it fetches and stages is a compile-time tag, so that nothing in it tests kc or a launch-uniform
+  // field of ConvParams: the chunk kind as a tag (ChunkKind: K_ANY keeps the run-time test kc >= nk for the loops that mix the two),
+  // and how a main chunk is activated as the kernel's GS -- true: GroupNorm + Swish, what every main chunk of the sampling loop is (the
+  // launcher picks that instantiation: k32_gs); false: p.gn_scale / p.gn_plain decide, as launch-uniform branches.
+  typedef std::integral_constant<int, CHUNK_MAIN> K_MAIN;
+  typedef std::integral_constant<int, CHUNK_RIDER> K_RIDER;
+  typedef std::integral_constant<int, CHUNK_ANY> K_ANY;
+  typedef std::integral_constant<int, RIDER && !RFIRST ? CHUNK_ANY : CHUNK_MAIN> K_NEXT;   // the chunk a main chunk stages for its successor
+  // (conv_k32_gnc_ok / conv_k32_drop_ok: such a launch has GroupNorm + Swish in front.  Of the dropout kernels only the 4-wave ones
+  // take it: they sit at 256 VGPRs and spilled on the test they need not make; the 16-row one spills WITH it)
+  constexpr bool GS = GS_ || GNC || (DROP && NW == 4);
+  float satm = 0.f;   // f16x3 range guard: max |v| over the raw quads this thread staged (sat_fold); the flag is raised once, behind the K loops
+  auto prefetch_rng = [&](int kc, QM* rin, auto i0_tag, auto i1_tag, bool load_gn, auto kind_tag) __attribute__((always_inline)) {
+    constexpr int I0 = decltype(i0_tag)::value, I1 = decltype(i1_tag)::value, KIND = decltype(kind_tag)::value;
+    const ChunkSrc src = chunk_src<RIDER, KIND>(p, kc, KC, nk, q, GS || gn);
     if (!GNC && src.gn && load_gn) {
       rsc = *reinterpret_cast<const f32x4*>(p.gn_scale + (size_t)n * Cin + src.cbase + q * 4);
       rsh = *reinterpret_cast<const f32x4*>(p.gn_shift + (size_t)n * Cin + src.cbase + q * 4);
@@ -272,14 +284,15 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
       const size_t pi = (size_t)(in_pix[i] < 0 ? 0 : in_pix[i]);
       rin[i - I0].q = IO::load4(src.base, pi * src.Cs + src.cc);
       if (DROP)   // the dropout bytes of these four channels ([N][H][W][C0], single input); a rider chunk reads element 0 (unused): a select, not a branch
-        rin[i - I0].m = *reinterpret_cast<const unsigned*>(p.drop_mask + ((RIDER && kc >= nk) ? (size_t)0 : pi * src.Cs + src.cc));
+        rin[i - I0].m = *reinterpret_cast<const unsigned*>(p.drop_mask + ((RIDER && chunk_is_rider<KIND>(kc, nk)) ? (size_t)0 : pi * src.Cs + src.cc));
     }
   };
-  auto prefetch_to = [&](int kc, QM* rin) __attribute__((always_inline)) { prefetch_rng(kc, rin, I_0{}, I_N{}, true); };
-  auto stage_rng = [&](int kc, unsigned char* buf, const QM* rin, auto i0_tag, auto i1_tag) __attribute__((always_inline)) {
-    constexpr int I0 = decltype(i0_tag)::value, I1 = decltype(i1_tag)::value;
+  auto prefetch_to = [&](int kc, QM* rin, auto kind_tag) __attribute__((always_inline)) { prefetch_rng(kc, rin, I_0{}, I_N{}, true, kind_tag); };
+  auto stage_rng = [&](int kc, unsigned char* buf, const QM* rin, auto i0_tag, auto i1_tag, auto kind_tag) __attribute__((always_inline)) {
+    constexpr int I0 = decltype(i0_tag)::value, I1 = decltype(i1_tag)::value, KIND = decltype(kind_tag)::value;
+    const bool rider = RIDER && chunk_is_rider<KIND>(kc, nk);
     f32x4 sc = rsc, sh = rsh;
-    if (GNC && !(RIDER && kc >= nk)) {   // this chunk's four channels of the LDS table the prologue built
+    if (GNC && !rider) {   // this chunk's four channels of the LDS table the prologue built
       sc = *reinterpret_cast<const f32x4*>(gnc_sc + (kc * KC - gnc_lo + q * 4));
       sh = *reinterpret_cast<const f32x4*>(gnc_sh + (kc * KC - gnc_lo + q * 4));
     }
@@ -290,17 +303,17 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
       if (K32_DIAG & 16) v = sc;
       if ((K32_DIAG & 1) && gn) {
         v = v + sh;
-      } else if (gn && !(RIDER && kc >= nk)) {
+      } else if ((GS || gn) && !rider) {
         // (gn_act4 / drop4 of fdsr_conv_dev.h written out: through the calls the 16-row f16x3 tile gained an s_waitcnt vmcnt(0))
         v = v * sc + sh;
-        if (!p.gn_plain) { v.x = silu_fast(v.x); v.y = silu_fast(v.y); v.z = silu_fast(v.z); v.w = silu_fast(v.w); }
+        if (GS || !p.gn_plain) { v.x = silu_fast(v.x); v.y = silu_fast(v.y); v.z = silu_fast(v.z); v.w = silu_fast(v.w); }
         if (DROP) {   // train-mode Dropout(p) behind the Swish: keep bytes are 0 / 1
           const unsigned m = rin[i - I0].m;
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] *= (float)((m >> (8 * e)) & 0xffu) * p.drop_scale;
         }
-      } else if (PREC == PREC_F16X3 && p.sat_flag) {
-        sat_check(p.sat_flag, v, 65504.f);
+      } else if (PREC == PREC_F16X3) {
+        satm = sat_fold(satm, v);   // a raw input: no store here (fdsr_act_io.h)
       }
       const int sd = sbase + i * (RPP * ROWB) + 16 * ((q >> 1) ^ (int)((skeys >> (3 * i)) & 7u));
       unsigned char* dst = buf + sd;
@@ -328,17 +341,17 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
       }
     }
   };
-  auto stage_from = [&](int kc, unsigned char* buf, const QM* rin) __attribute__((always_inline)) { stage_rng(kc, buf, rin, I_0{}, I_N{}); };
+  auto stage_from = [&](int kc, unsigned char* buf, const QM* rin, auto kind_tag) __attribute__((always_inline)) { stage_rng(kc, buf, rin, I_0{}, I_N{}, kind_tag); };
 
   // ---- weight fragments: ring slot s holds tap t with t % R == s; [cout half][plane] ----
   const uint4* wq = reinterpret_cast<const uint4*>(p.wq);
   const int nkt = RIDER ? nk + nkr : nk;
   uint4 Wf[R][2][NP];
   const int wlane = 32 * (g & 1) + c15;          // + 16 ch: unit within the 32x32x16-order block
-  auto load_w = [&](int kc, int tap, int slot) __attribute__((always_inline)) {
+  auto load_w = [&](int kc, int tap, int slot, auto kind_tag) __attribute__((always_inline)) {
     if (K32_DIAG & 32) kc = 0;   // (timing probe: every chunk multiplies chunk 0's fragments -- what a weight fetch that never misses would buy)
     const uint4* src = wq + ((((size_t)cot * nk16 + 2 * kc + (g >> 1)) * WN + wn) * 9 + tap) * (Cfg::WNP * 64) + wlane;
-    if (RIDER && kc >= nk)   // the 1x1 conv's own fragments [cot][kc16][wn]
+    if (RIDER && chunk_is_rider<decltype(kind_tag)::value>(kc, nk))   // the 1x1 conv's own fragments [cot][kc16][wn]
       src = reinterpret_cast<const uint4*>(p.wq_r) + (((size_t)cot * p.nkr + 2 * (kc - nk) + (g >> 1)) * WN + wn) * (Cfg::WNP * 64) + wlane;
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch)
@@ -364,36 +377,43 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
       for (int ch = 0; ch < 2; ++ch) acc[mb][ph][ch] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   const int kc0 = ksi * nkt / SK, kc1 = (ksi + 1) * nkt / SK;   // this slice's chunks
-  if (RFIRST || (RIDER && kc0 >= nk)) load_w(RFIRST ? nk : kc0, 0, 0);
+  if (RFIRST) load_w(nk, 0, 0, K_RIDER{});
+  else if (RIDER && kc0 >= nk) load_w(kc0, 0, 0, K_RIDER{});
   else {
 #pragma unroll
-    for (int t = 0; t < R; ++t) load_w(kc0, t, t);
+    for (int t = 0; t < R; ++t) load_w(kc0, t, t, K_MAIN{});
   }
   // GNC: the table's loads go out here, beside the weights and the first chunk's input; the fold and the two barriers follow the first fetch
   const int gm0 = RFIRST ? 0 : (kc0 < nk ? kc0 : nk), gm1 = RIDER ? (kc1 < nk ? kc1 : nk) : kc1;   // this workgroup's main chunks
   const bool gnc_on = GNC && gm1 > gm0;
   if (gnc_on) gnc_issue(gm0 * KC, gm1 * KC < Cin ? gm1 * KC : Cin);
   if (RFIRST) {   // (never split in K: kc0 = 0, kc1 = nk + nkr)
+    // The scale / shift of main chunk 0 go out here, ahead of everything the rider chunks wait for: the rider loop's prefetches are
+    // then plain loads of either kind -- a guarded load in a loop costs every wait behind it its count.
+    if (!GNC && (GS || gn)) {
+      rsc = *reinterpret_cast<const f32x4*>(p.gn_scale + (size_t)n * Cin + q * 4);
+      rsh = *reinterpret_cast<const f32x4*>(p.gn_shift + (size_t)n * Cin + q * 4);
+    }
     {
       QM r0[NIN];
-      prefetch_to(nk, r0);
+      prefetch_to(nk, r0, K_RIDER{});
       if (gnc_on) gnc_finish();
-      stage_from(nk, sBuf0, r0);
+      stage_from(nk, sBuf0, r0, K_RIDER{});
     }
-    prefetch_to(nkr > 1 ? nk + 1 : 0, rr1);   // the second rider chunk -- or, after a single one, the first main chunk (fetched whole)
+    prefetch_rng(nkr > 1 ? nk + 1 : 0, rr1, I_0{}, I_N{}, false, K_ANY{});   // the second rider chunk -- or, after a single one, the first main chunk (fetched whole)
   } else if (SPLIT) {
     {   // the first chunk is fetched whole (the accumulators are not live yet)
       QM r0[NIN];
-      prefetch_to(kc0, r0);
+      prefetch_to(kc0, r0, K_NEXT{});
       if (gnc_on) gnc_finish();
-      stage_from(kc0, sBuf0, r0);
+      stage_from(kc0, sBuf0, r0, K_NEXT{});
     }
-    if (RIDER && kc0 >= nk && kc0 + 1 < kc1) prefetch_to(kc0 + 1, rr1);   // (a slice that starts among the rider chunks)
+    if (RIDER && kc0 >= nk && kc0 + 1 < kc1) prefetch_to(kc0 + 1, rr1, K_RIDER{});   // (a slice that starts among the rider chunks)
   } else {
-    prefetch_to(kc0, rin);
+    prefetch_to(kc0, rin, K_NEXT{});
     if (gnc_on) gnc_finish();
-    stage_from(kc0, sBuf0, rin);
-    if (kc0 + 1 < kc1) prefetch_to(kc0 + 1, rin);
+    stage_from(kc0, sBuf0, rin, K_NEXT{});
+    if (kc0 + 1 < kc1) prefetch_to(kc0 + 1, rin, K_NEXT{});
   }
   __syncthreads();
 
@@ -460,7 +480,9 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
     constexpr bool LAST = decltype(last_tag)::value;   // the peeled final chunk: nothing to fetch or stage for a next one
     unsigned char* cur = ((kc - kc0 + par0) & 1) ? sBuf1 : sBuf0;
     unsigned char* nxt = ((kc - kc0 + par0) & 1) ? sBuf0 : sBuf1;
-    const bool more = LAST ? false : (kc + 1 < (RFIRST ? nk : kc1));
+    // (rider-first: the peeled loop runs its copies without LAST for kc < kcm - 1 <= nk - 1 only -- said here, the compiler does not
+    // prove it from kcm, and the test cut the loop body into blocks with a full drain at the back edge)
+    const bool more = LAST ? false : (RFIRST ? (PEEL ? true : kc + 1 < nk) : kc + 1 < kc1);
     const bool next_rider = RIDER && !RFIRST && kc + 1 >= nk;
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx)
@@ -482,21 +504,21 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
         if (PIN) __builtin_amdgcn_sched_barrier(0);
       }
       // this tap's ring slot is free: fetch the tap that will use it next
-      if (tap + R < 9) load_w(kc, tap + R, tap % R);
-      else if (more && (tap + R - 9 == 0 || !next_rider)) load_w(kc + 1, tap + R - 9, tap % R);
+      if (tap + R < 9) load_w(kc, tap + R, tap % R, K_MAIN{});
+      else if (more && (tap + R - 9 == 0 || !next_rider)) load_w(kc + 1, tap + R - 9, tap % R, K_NEXT{});
       if (SPLIT) {   // the other halo buffer is filled in two halves, each fetched four taps before it is staged
-        if (tap == 0 && more) prefetch_rng(kc + 1, rin, I_0{}, I_A{}, true);
+        if (tap == 0 && more) prefetch_rng(kc + 1, rin, I_0{}, I_A{}, true, K_NEXT{});
         if (tap == 3 && more) {
-          if (!(K32_DIAG & 2)) stage_rng(kc + 1, nxt, rin, I_0{}, I_A{});
-          prefetch_rng(kc + 1, rin, I_A{}, I_N{}, false);
+          if (!(K32_DIAG & 2)) stage_rng(kc + 1, nxt, rin, I_0{}, I_A{}, K_NEXT{});
+          prefetch_rng(kc + 1, rin, I_A{}, I_N{}, false, K_NEXT{});
         }
         if (tap == 7 && more) {
-          if (!(K32_DIAG & 2)) stage_rng(kc + 1, nxt, rin, I_A{}, I_N{});
-          if (next_rider && kc + 2 < kc1) prefetch_to(kc + 2, rr1);   // the rider loop expects its second chunk in flight
+          if (!(K32_DIAG & 2)) stage_rng(kc + 1, nxt, rin, I_A{}, I_N{}, K_NEXT{});
+          if (next_rider && kc + 2 < kc1) prefetch_to(kc + 2, rr1, K_RIDER{});   // the rider loop expects its second chunk in flight
         }
       } else if (tap == 4 && more) {   // mid-chunk: fill the other halo buffer
-        stage_from(kc + 1, nxt, rin);
-        if (kc + 2 < kc1) prefetch_to(kc + 2, rin);
+        stage_from(kc + 1, nxt, rin, K_NEXT{});
+        if (kc + 2 < kc1) prefetch_to(kc + 2, rin, K_NEXT{});
       }
       if (LAST && res_early) {   // the staging registers are free from the start, a weight-ring slot after each of taps 6, 7, 8
         if (tap == 0) load_res(I_0{}, I_7{});
@@ -507,41 +529,46 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
     }
     __syncthreads();
   };
+  // one rider chunk's MFMAs: centre tap only, the 1x1 conv's fragments in ring slot 0
+  auto rider_mfma = [&](unsigned char* cur) __attribute__((always_inline)) {
+#pragma unroll
+    for (int pl = 0; pl < NP; ++pl) xptr[1][pl] = cur + xoff[1][pl];
+#pragma unroll
+    for (int mb = 0; mb < XS - 1 && mb < MB; ++mb) load_x(mb, 1, 1, mb);
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) {
+      if (mb + XS - 1 < MB) load_x((mb + XS - 1) % XS, 1, 1, mb + XS - 1);
+      mfma_step(mb % XS, 0, mb);
+    }
+  };
   if (RFIRST) {
-    // rider chunks first: centre tap only, the 1x1 conv's fragments in ring slot 0, the next chunk fetched whole into rr1 one chunk
-    // ahead (the CU's other workgroup covers the latency); the last one stages the first MAIN chunk and primes the weight ring
-    for (int v = 0; v < nkr; ++v) {
-      unsigned char* cur = (v & 1) ? sBuf1 : sBuf0;
-      unsigned char* nxt = (v & 1) ? sBuf0 : sBuf1;
-#pragma unroll
-      for (int pl = 0; pl < NP; ++pl) xptr[1][pl] = cur + xoff[1][pl];
-#pragma unroll
-      for (int mb = 0; mb < XS - 1 && mb < MB; ++mb) load_x(mb, 1, 1, mb);
-#pragma unroll
-      for (int mb = 0; mb < MB; ++mb) {
-        if (mb + XS - 1 < MB) load_x((mb + XS - 1) % XS, 1, 1, mb + XS - 1);
-        mfma_step(mb % XS, 0, mb);
-      }
-      if (v + 1 < nkr) {
-        load_w(nk + v + 1, 0, 0);
-        stage_from(nk + v + 1, nxt, rr1);
-        prefetch_to(v + 2 < nkr ? nk + v + 2 : 0, rr1);
-      } else {
-#pragma unroll
-        for (int t = 0; t < R; ++t) load_w(0, t, t);
-        stage_from(0, nxt, rr1);
-      }
+    // rider chunks first: the next chunk is fetched whole into rr1 one chunk ahead (the CU's other workgroup covers the latency).
+    // Every chunk this loop stages is a rider chunk: raw, no scale / shift, no store; the loads of its prefetch are unconditional
+    // (the last pass fetches main chunk 0 through the same loads).  The last rider chunk is run behind the loop.
+    for (int v = 0; v + 1 < nkr; ++v) {
+      rider_mfma((v & 1) ? sBuf1 : sBuf0);
+      load_w(nk + v + 1, 0, 0, K_RIDER{});
+      stage_from(nk + v + 1, (v & 1) ? sBuf0 : sBuf1, rr1, K_RIDER{});
+      prefetch_rng(v + 2 < nkr ? nk + v + 2 : 0, rr1, I_0{}, I_N{}, false, K_ANY{});
       __syncthreads();
     }
-    {   // the accumulators leave the rider's weight scale for the main conv's (a power of two: exact)
-      const float ratio = (p.w_inv_scale_r_dev ? *p.w_inv_scale_r_dev : p.w_inv_scale_r) / (p.w_inv_scale_dev ? *p.w_inv_scale_dev : p.w_inv_scale);
+  }
+  if (RFIRST) {
+    // The last rider chunk primes the weight ring and stages main chunk 0; from there on the code is the rider-less kernel's.
+    const int v = nkr - 1;
+    rider_mfma((v & 1) ? sBuf1 : sBuf0);
 #pragma unroll
-      for (int mb = 0; mb < MB; ++mb)
+    for (int t = 0; t < R; ++t) load_w(0, t, t, K_MAIN{});
+    stage_from(0, (v & 1) ? sBuf0 : sBuf1, rr1, K_MAIN{});
+    __syncthreads();
+    // the accumulators leave the rider's weight scale for the main conv's (a power of two: exact)
+    const float ratio = (p.w_inv_scale_r_dev ? *p.w_inv_scale_r_dev : p.w_inv_scale_r) / (p.w_inv_scale_dev ? *p.w_inv_scale_dev : p.w_inv_scale);
 #pragma unroll
-        for (int ph = 0; ph < 2; ++ph)
+    for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
-          for (int ch = 0; ch < 2; ++ch) acc[mb][ph][ch] *= ratio;
-    }
+      for (int ph = 0; ph < 2; ++ph)
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch) acc[mb][ph][ch] *= ratio;
   }
   if (PEEL) {
     for (int kc = kc0; kc < kcm - 1; ++kc) main_chunk(kc, std::false_type{});
@@ -564,23 +591,14 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
     // (on entry the first set holds chunk k0 + 1, as the main loop leaves it; two of the three weight-ring slots are free by now).
     const int k0 = kc0 > nk ? kc0 : nk;
     constexpr int AH = K32_RIDER2 && NW == 8 ? 2 : 1;
-    if (AH == 2 && k0 + 2 < kc1) prefetch_to(k0 + 2, rin2);
+    if (AH == 2 && k0 + 2 < kc1) prefetch_to(k0 + 2, rin2, K_RIDER{});
     auto rider_chunk = [&](int kc, QM* r1) __attribute__((always_inline)) {   // r1 holds chunk kc + 1
-      unsigned char* cur = ((kc - kc0) & 1) ? sBuf1 : sBuf0;
       unsigned char* nxt = ((kc - kc0) & 1) ? sBuf0 : sBuf1;
-#pragma unroll
-      for (int pl = 0; pl < NP; ++pl) xptr[1][pl] = cur + xoff[1][pl];
-#pragma unroll
-      for (int mb = 0; mb < XS - 1 && mb < MB; ++mb) load_x(mb, 1, 1, mb);
-#pragma unroll
-      for (int mb = 0; mb < MB; ++mb) {
-        if (mb + XS - 1 < MB) load_x((mb + XS - 1) % XS, 1, 1, mb + XS - 1);
-        mfma_step(mb % XS, 0, mb);
-      }
+      rider_mfma(((kc - kc0) & 1) ? sBuf1 : sBuf0);
       if (kc + 1 < kc1) {
-        load_w(kc + 1, 0, 0);
-        stage_from(kc + 1, nxt, r1);
-        if (kc + 1 + AH < kc1) prefetch_to(kc + 1 + AH, r1);
+        load_w(kc + 1, 0, 0, K_RIDER{});
+        stage_from(kc + 1, nxt, r1, K_RIDER{});
+        if (kc + 1 + AH < kc1) prefetch_to(kc + 1 + AH, r1, K_RIDER{});
       }
       __syncthreads();
     };
@@ -594,6 +612,8 @@ __global__ void __launch_bounds__(64 * NW, 2) conv_k32_kernel(const ConvParams p
       for (int kc = k0; kc < kc1; ++kc) rider_chunk(kc, rfirst);
     }
   }
+
+  if (PREC == PREC_F16X3) sat_raise(p.sat_flag, satm, 65504.f);   // the range guard's one store, behind the last K chunk
 
   // ---- epilogue: lane = pixel c15 (+ 16 ph) of row wm + mb*WM, output channels cob + 16 ch + 0..3 ----
   // bias (+ the rider's) + noise shift of this lane's output channels.  Every load is issued unconditionally (a clamped channel, the
@@ -876,6 +896,7 @@ __global__ void __launch_bounds__(512, 2) conv_up2_k32_kernel(const ConvParams p
   using IO = ActIO<PREC>;
   typedef typename IO::Quad Quad;
   Quad rin[NIN];
+  float satm = 0.f;   // f16x3 range guard: max |v| this thread staged
   auto prefetch = [&](int kc) {
     const size_t coff = (size_t)kc * KC + q * 4;
 #pragma unroll
@@ -888,7 +909,7 @@ __global__ void __launch_bounds__(512, 2) conv_up2_k32_kernel(const ConvParams p
       f32x4 v = IO::widen(rin[i]);
       const int sd = sbase + i * (RPP * ROWB) + 16 * ((q >> 1) ^ (int)((skeys >> (3 * i)) & 7u));
       if (PREC == PREC_F16X3) {
-        if (p.sat_flag) sat_check(p.sat_flag, v, 65504.f);
+        satm = sat_fold(satm, v);   // raw input: the range guard's store follows the K loop (fdsr_act_io.h)
         // (split4_mix of fdsr_conv_dev.h written out: through the call the f16x3 instantiations took one more SGPR)
         const float lim = in_pix[i] >= 0 ? 65504.f : 0.f;
 #pragma unroll
@@ -1014,6 +1035,7 @@ __global__ void __launch_bounds__(512, 2) conv_up2_k32_kernel(const ConvParams p
     }
     __syncthreads();
   }
+  if (PREC == PREC_F16X3) sat_raise(p.sat_flag, satm, 65504.f);
 
   // ---- epilogue: out[2 (oy0 + row) + py][2 (ox0 + col) + px], + bias (+ temb), GroupNorm partials of the output ----
   const int cob = co0 + wn * 32 + 4 * g;
@@ -1130,10 +1152,10 @@ bool conv_k32_ok(int TH, int WN, int prec, const ConvParams& p) {
   return true;
 }
 
-template <int TH, int WN, int PREC, bool RIDER, int NW = 8, bool RF = (NW == 4), bool GNB = false, bool DROP = false, bool GNC = false>
+template <int TH, int WN, int PREC, bool RIDER, int NW = 8, bool RF = (NW == 4), bool GNB = false, bool DROP = false, bool GNC = false, bool GS_ = false>
 static hipError_t launch_k32_t(const ConvParams& q, int nwg, hipStream_t s) {
   using Cfg = ConvK32Cfg<TH, WN, PREC, NW>;
-  hipLaunchKernelGGL((conv_k32_kernel<TH, WN, PREC, RIDER, NW, RF, GNB, DROP, GNC>), dim3(nwg), dim3(Cfg::NT), (size_t)Cfg::LDS_BYTES + (GNC ? K32_GNC_LDS : 0), s, q);
+  hipLaunchKernelGGL((conv_k32_kernel<TH, WN, PREC, RIDER, NW, RF, GNB, DROP, GNC, GS_>), dim3(nwg), dim3(Cfg::NT), (size_t)Cfg::LDS_BYTES + (GNC ? K32_GNC_LDS : 0), s, q);
   return hipGetLastError();
 }
 
@@ -1153,6 +1175,10 @@ static bool k32_gnb_ok(int prec, const ConvParams& q) {
 // The small-workgroup form (NW = 4, two workgroups per CU) of the 64-cout launches: 6-row tiles (what two double-buffered f16x3 halo
 // images per CU leave room for).  Large grids only: a small grid wants all eight waves of a CU on its one
 // tile.  launch_conv_h asks before it picks a tile of its own; tiles / nwg are computed here.
+// f16x3: a launch whose main chunks are all GroupNorm'ed + Swish'ed (every stride-1 3x3 launch of the sampling loop) takes the
+// instantiation that knows it at compile time (GS_): no test of gn_scale / gn_plain, no range-guard arithmetic in its main loop
+static bool k32_gs(const ConvParams& q) { return q.gn_scale && !q.gn_plain; }
+
 static int k32_small_rows(int prec, bool rider) { return prec_is16(prec) && !rider ? 8 : 6; }   // (the bf16 8-row tile with a rider spills 27 VGPRs)
 
 bool conv_k32_small_ok(ConvKind kind, int prec, const ConvParams& p) {
@@ -1180,8 +1206,10 @@ hipError_t launch_conv_k32_small(int prec, const ConvParams& p, hipStream_t s, i
     if (!conv_k32_drop_ok(prec, q)) return hipErrorInvalidValue;
     return q.xr0 ? launch_k32_t<6, 2, PREC_F16X3, true, 4, true, false, true>(q, nwg, s) : launch_k32_t<6, 2, PREC_F16X3, false, 4, true, false, true>(q, nwg, s);
   }
-  if (prec == PREC_F16X3)
+  if (prec == PREC_F16X3) {
+    if (k32_gs(q)) return q.xr0 ? launch_k32_t<6, 2, PREC_F16X3, true, 4, true, false, false, false, true>(q, nwg, s) : launch_k32_t<6, 2, PREC_F16X3, false, 4, true, false, false, false, true>(q, nwg, s);
     return q.xr0 ? launch_k32_t<6, 2, PREC_F16X3, true, 4>(q, nwg, s) : launch_k32_t<6, 2, PREC_F16X3, false, 4>(q, nwg, s);
+  }
   if (prec == PREC_F16) return q.xr0 ? launch_k32_t<6, 2, PREC_F16, true, 4>(q, nwg, s) : launch_k32_t<8, 2, PREC_F16, false, 4>(q, nwg, s);
   return q.xr0 ? launch_k32_t<6, 2, PREC_BF16, true, 4>(q, nwg, s) : launch_k32_t<8, 2, PREC_BF16, false, 4>(q, nwg, s);
 }
@@ -1221,6 +1249,12 @@ hipError_t launch_conv_k32(int TH, int WN, int prec, const ConvParams& q, int nw
       return q.xr0 ? launch_k32_t<TH_, WN_, PREC_F16X3, true, 8, true, false, true>(q, nwg, s)                  \
                    : launch_k32_t<TH_, WN_, PREC_F16X3, false, 8, false, false, true>(q, nwg, s);               \
     }                                                                                                           \
+    if (prec == PREC_F16X3 && k32_gs(q)) {                                                                      \
+      if (q.xr0 && q.ksplit <= 1 && (g_tun.k32 & FDSR_K32_RIDER_FIRST_8WAVE))                                   \
+        return launch_k32_t<TH_, WN_, PREC_F16X3, true, 8, true, false, false, false, true>(q, nwg, s);         \
+      return q.xr0 ? launch_k32_t<TH_, WN_, PREC_F16X3, true, 8, false, false, false, false, true>(q, nwg, s)   \
+                   : launch_k32_t<TH_, WN_, PREC_F16X3, false, 8, false, false, false, false, true>(q, nwg, s); \
+    }                                                                                                           \
     if (q.xr0 && q.ksplit <= 1 && (g_tun.k32 & FDSR_K32_RIDER_FIRST_8WAVE))                                                           \
       return prec == PREC_F16X3 ? launch_k32_t<TH_, WN_, PREC_F16X3, true, 8, true>(q, nwg, s)                  \
                                 : prec == PREC_F16 ? launch_k32_t<TH_, WN_, PREC_F16, true, 8, true>(q, nwg, s) : launch_k32_t<TH_, WN_, PREC_BF16, true, 8, true>(q, nwg, s);                  \
@@ -1234,9 +1268,9 @@ hipError_t launch_conv_k32(int TH, int WN, int prec, const ConvParams& q, int nw
   return hipErrorInvalidValue;
 }
 
-template <int TH, int WN, int PREC, bool RIDER, int NW = 8, bool RF = (NW == 4), bool GNB = false, bool DROP = false, bool GNC = false>
+template <int TH, int WN, int PREC, bool RIDER, int NW = 8, bool RF = (NW == 4), bool GNB = false, bool DROP = false, bool GNC = false, bool GS_ = false>
 static hipError_t init_k32_t() {
-  auto kfn = conv_k32_kernel<TH, WN, PREC, RIDER, NW, RF, GNB, DROP, GNC>;
+  auto kfn = conv_k32_kernel<TH, WN, PREC, RIDER, NW, RF, GNB, DROP, GNC, GS_>;
   return hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
@@ -1262,6 +1296,9 @@ hipError_t kernels_k32_init() {
   if ((e = init_k32_t<TH_, WN_, PREC_BF16, true>()) != hipSuccess) return e;                \
   if ((e = init_k32_t<TH_, WN_, PREC_F16, true>()) != hipSuccess) return e;                \
   if ((e = init_k32_t<TH_, WN_, PREC_F16X3, true, 8, true>()) != hipSuccess) return e;     \
+  if ((e = init_k32_t<TH_, WN_, PREC_F16X3, false, 8, false, false, false, false, true>()) != hipSuccess) return e; \
+  if ((e = init_k32_t<TH_, WN_, PREC_F16X3, true, 8, false, false, false, false, true>()) != hipSuccess) return e;  \
+  if ((e = init_k32_t<TH_, WN_, PREC_F16X3, true, 8, true, false, false, false, true>()) != hipSuccess) return e;   \
   if ((e = init_k32_t<TH_, WN_, PREC_F16X3, false, 8, false, true>()) != hipSuccess) return e; \
   if ((e = init_k32_t<TH_, WN_, PREC_F16X3, false, 8, false, false, true>()) != hipSuccess) return e; \
   if ((e = init_k32_t<TH_, WN_, PREC_F16X3, true, 8, true, false, true>()) != hipSuccess) return e; \
@@ -1283,6 +1320,8 @@ hipError_t kernels_k32_init() {
 #undef X
   if ((e = init_k32_t<6, 2, PREC_F16X3, false, 4>()) != hipSuccess) return e;
   if ((e = init_k32_t<6, 2, PREC_F16X3, true, 4>()) != hipSuccess) return e;
+  if ((e = init_k32_t<6, 2, PREC_F16X3, false, 4, true, false, false, false, true>()) != hipSuccess) return e;
+  if ((e = init_k32_t<6, 2, PREC_F16X3, true, 4, true, false, false, false, true>()) != hipSuccess) return e;
   if ((e = init_k32_t<6, 2, PREC_F16X3, false, 4, true, true>()) != hipSuccess) return e;
   if ((e = init_k32_t<6, 2, PREC_F16X3, false, 4, true, false, true>()) != hipSuccess) return e;
   if ((e = init_k32_t<6, 2, PREC_F16X3, true, 4, true, false, true>()) != hipSuccess) return e;

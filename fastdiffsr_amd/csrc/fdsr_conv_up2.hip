@@ -72,6 +72,7 @@ __global__ void __launch_bounds__(512, 2) conv_up2_h_kernel(const ConvParams p) 
   }
   using IO = ActIO<PREC>;
   typename IO::Quad rin[NIN];
+  float satm = 0.f;   // f16x3 range guard: max |v| this thread staged (fdsr_act_io.h)
   auto prefetch = [&](int kc) {
     const size_t coff = (size_t)kc * KC + q * 4;
 #pragma unroll
@@ -87,7 +88,7 @@ __global__ void __launch_bounds__(512, 2) conv_up2_h_kernel(const ConvParams p) 
       const float lim = in_pix[i] >= 0 ? 65504.f : 0.f;
       unsigned char* dst = buf + (row0 + i * RPP) * ROWB + q * 8;
       if (PREC == PREC_F16X3) {
-        if (p.sat_flag) sat_check(p.sat_flag, v, 65504.f);   // raw input (no GroupNorm in front of the upsample conv)
+        satm = sat_fold(satm, v);   // raw input (no GroupNorm in front of the upsample conv); the guard's store follows the K loop
         h4 hi, lo;
         split4_2step(v, lim, hi, lo);   // padding: lim = 0
         *reinterpret_cast<h4*>(dst) = hi;
@@ -167,6 +168,7 @@ __global__ void __launch_bounds__(512, 2) conv_up2_h_kernel(const ConvParams p) 
     }
     __syncthreads();
   }
+  if (PREC == PREC_F16X3) sat_raise(p.sat_flag, satm, 65504.f);
 
   // ---- epilogue: out[(2(oy0+row)+py)][2(ox0+col)+px], + bias (+ temb), GN partials of the output ----
   const int co = co0 + wn * 32 + r31;
