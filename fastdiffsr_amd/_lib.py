@@ -41,6 +41,16 @@ class FdsrNafnetConfig(C.Structure):
                 ('dec_blk_nums', C.c_int32 * FDSR_NAFNET_MAX_LEVELS)]
 
 
+FDSR_SWINIR_MAX_LAYERS = 8
+FDSR_SWINIR_GRAPH = 1
+
+
+class FdsrSwinirConfig(C.Structure):
+    _fields_ = [('embed_dim', C.c_int32), ('n_layers', C.c_int32), ('depths', C.c_int32 * FDSR_SWINIR_MAX_LAYERS),
+                ('num_heads', C.c_int32 * FDSR_SWINIR_MAX_LAYERS), ('window_size', C.c_int32), ('mlp_hidden', C.c_int32),
+                ('upscale', C.c_int32), ('patch_norm', C.c_int32), ('img_range', C.c_float), ('mean', C.c_float * 3)]
+
+
 class FdsrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f'libfdsr_hip error {code}: {msg}')
@@ -123,6 +133,15 @@ SYMBOLS = {
     'fdsr_fid_features_u8': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_size_t, C.c_void_p]),
     'fdsr_fid_destroy': (None, [C.c_void_p]),
+    'fdsr_swinir_create': (C.c_int, [C.POINTER(FdsrSwinirConfig), C.POINTER(C.c_void_p)]),
+    'fdsr_swinir_load': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    'fdsr_swinir_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    'fdsr_swinir_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                      C.c_int]),
+    'fdsr_swinir_debug_tensor': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                           C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'fdsr_swinir_to_u8': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'fdsr_swinir_destroy': (None, [C.c_void_p]),
     'fdsr_nafnet_create': (C.c_int, [C.POINTER(FdsrNafnetConfig), C.POINTER(C.c_void_p)]),
     'fdsr_nafnet_num_weights': (C.c_int, [C.c_void_p]),
     'fdsr_nafnet_weight_info': (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),

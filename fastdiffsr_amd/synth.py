@@ -111,6 +111,38 @@ def synth_inception_fid(seed: int = 0) -> "OrderedDict[str, np.ndarray]":
     return out
 
 
+def synth_swinir(cfg, seed: int = 0) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights for SwinIR, keyed and ordered as swinir.arch.param_schema(cfg), every tensor from its own key.  Not
+    the reference's init: trunc_normal_(std=.02) gives nearly flat attention, under which a wrong mask, bias index or roll
+    disappears.  Here the q and k rows of qkv are N(0, 1.5 / C), so the logits q k^T / sqrt(head_dim) have a spread of about
+    1.5; the bias table is N(0, 1); every LayerNorm has weight 1 + 0.2 N and bias 0.1 N; proj and fc2 are damped (variance
+    0.1 / fan_in and 0.6 / fan_in: fc2 strong enough that the tanh form of GELU shows at the output) and the RSTB convolutions N(0, 0.5 / fan_in), so the residual stream stays O(1) through
+    all 36 blocks; the other weights are N(0, g / fan_in) with g between 1 and 4, biases 0.05 N (qkv 0.1 N)."""
+    from .swinir.arch import param_schema as swin_schema
+    c = cfg.embed_dim
+    out = OrderedDict()
+    for k, shape in swin_schema(cfg).items():
+        x = _rng('swinir:' + k, seed).standard_normal(size=shape, dtype=np.float64)
+        fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else 1
+        norm = '.norm' in k or k.startswith('norm.')
+        if k.endswith('relative_position_bias_table'):
+            pass
+        elif norm and k.endswith('.weight'):
+            x = 1.0 + 0.2 * x
+        elif norm:
+            x *= 0.1
+        elif k.endswith('.bias'):
+            x *= 0.1 if '.qkv.' in k else 0.05
+        elif '.qkv.' in k:
+            x *= np.sqrt(np.r_[np.full(2 * c, 1.5), np.ones(c)] / fan_in)[:, None]
+        else:
+            gain = {'proj': 0.1, 'fc1': 2.0, 'fc2': 0.6, 'conv': 0.5, 'conv_first': 4.0, 'conv_after_body': 1.0, '0': 2.0, '2': 2.0,
+                    '4': 2.0, 'conv_last': 1.0}[k.split('.')[-2]]
+            x *= np.sqrt(gain / fan_in)
+        out[k] = x.astype(np.float32)
+    return out
+
+
 def synth_nafnet(seed: int = 0, width: int = 16, enc_blk_nums=(2, 1, 1, 1), middle_blk_num: int = 1, dec_blk_nums=(1, 1, 1, 1),
                  img_channel: int = 3) -> "OrderedDict[str, np.ndarray]":
     """Synthetic weights for EDiffSR's ConditionalNAFNet, keyed and ordered as ediffsr.arch.param_schema.  The reference

@@ -313,6 +313,58 @@ int fdsr_fid_features_u8(fdsr_fid f, const uint8_t* img_nhwc, int batch, int hei
                          void* workspace, size_t workspace_bytes, void* hip_stream);
 void fdsr_fid_destroy(fdsr_fid f);
 
+/* -- SwinIR (MSI_SR_model/model/swinir.py: GeneratorResNet) inference ---------------------------------------------------
+ * An object of its own, independent of fdsr_handle: upsampler 'pixelshuffle', resi_connection '1conv', patch_size 1, no
+ * absolute position embedding, three input channels, eval mode.  Exact fp32, NHWC inside: every Linear and every 3x3
+ * convolution is one GEMM kernel on v_mfma_f32_32x32x2_f32 (a k-ordered chain per output, no split-K, no atomics), LayerNorm
+ * over channels (eps 1e-5) one wave per token, shifted-window attention one workgroup per (image, window) with the roll, the
+ * window partition, the relative-position bias and the -100 region mask folded in.  Reruns are bitwise identical and an
+ * image's result depends neither on B nor on its position in the batch.
+ *   fdsr_swinir_create           validates the configuration without touching the device.  FDSR_E_INVALID outside the envelope:
+ *                                window_size 8; head_dim = embed_dim / num_heads[i] an integer <= 32; embed_dim <= 512;
+ *                                1..FDSR_SWINIR_MAX_LAYERS layers of depth >= 1; upscale 2, 3, 4 or 8; img_range > 0.
+ *   fdsr_swinir_load             a host fp32 tensor under the reference's state_dict name and shape (conv_first.weight,
+ *                                layers.0.residual_group.blocks.1.attn.relative_position_bias_table, ...); the buffers
+ *                                relative_position_index and attn_mask are functions of the geometry and are not taken.  Any
+ *                                other name or shape: FDSR_E_KEY.  Host-synchronous; drops every captured graph.
+ *   fdsr_swinir_workspace_bytes  for a batch of height x width inputs.  FDSR_E_INVALID where the input cannot be reflect-padded
+ *                                to a multiple of the window (F.pad's rule: the padding is smaller than the side).
+ *   fdsr_swinir_forward          x_nchw [B][3][H][W] fp32 in [0, 1] -> out_nchw [B][3][H upscale][W upscale].  flags:
+ *                                FDSR_SWINIR_GRAPH replays the forward as one captured, linear hipGraph (hip_stream must be a
+ *                                created stream); one graph is kept per (B, H, W), captured anew when x, out or the workspace
+ *                                move.  Stream-ordered otherwise.
+ *   fdsr_swinir_debug_tensor     runs the forward up to a named tap and copies it out as NHWC [B][dims3[0]][dims3[1]][dims3[2]] at
+ *                                the padded size: conv_first, patch_embed.norm, layers.I.blocks.J.attn / .mlp (a block after its
+ *                                attention / MLP residual), layers.I (an RSTB's output), conv_after_body, upsample.K (after the
+ *                                K-th pixel shuffle).  Unknown name: FDSR_E_KEY; capacity_floats too small: FDSR_E_INVALID.
+ *   fdsr_swinir_to_u8            the reference's save_img1: (x * 255) clamped to [0, 255], truncated; NCHW fp32 -> NHWC uint8.
+ * FDSR_E_STATE if a tensor is missing; FDSR_E_WORKSPACE if the workspace (256-byte aligned) is too small.  Messages:
+ * fdsr_last_error(NULL). */
+#define FDSR_SWINIR_MAX_LAYERS 8
+#define FDSR_SWINIR_GRAPH 1
+typedef struct fdsr_swinir_config {
+  int32_t embed_dim;
+  int32_t n_layers;                          /* len(depths) == len(num_heads), 1..FDSR_SWINIR_MAX_LAYERS */
+  int32_t depths[FDSR_SWINIR_MAX_LAYERS];
+  int32_t num_heads[FDSR_SWINIR_MAX_LAYERS];
+  int32_t window_size;
+  int32_t mlp_hidden;                        /* int(embed_dim * mlp_ratio) */
+  int32_t upscale;
+  int32_t patch_norm;                        /* 0: no LayerNorm in patch_embed */
+  float img_range;
+  float mean[3];
+} fdsr_swinir_config;
+typedef struct fdsr_swinir_obj* fdsr_swinir;
+int fdsr_swinir_create(const fdsr_swinir_config* cfg, fdsr_swinir* out);
+int fdsr_swinir_load(fdsr_swinir s, const char* name, const float* host_f32, const int64_t* shape, int ndim);
+int fdsr_swinir_workspace_bytes(fdsr_swinir s, int batch, int height, int width, size_t* bytes);
+int fdsr_swinir_forward(fdsr_swinir s, const float* x_nchw, int batch, int height, int width, float* out_nchw, void* workspace,
+                        size_t workspace_bytes, void* hip_stream, int flags);
+int fdsr_swinir_debug_tensor(fdsr_swinir s, const char* name, const float* x_nchw, int batch, int height, int width, float* out_nhwc,
+                             size_t capacity_floats, int* dims3, void* workspace, size_t workspace_bytes, void* hip_stream);
+int fdsr_swinir_to_u8(const float* src_nchw, uint8_t* dst_nhwc, int batch, int height, int width, void* hip_stream);
+void fdsr_swinir_destroy(fdsr_swinir s);
+
 /* -- EDiffSR: ConditionalNAFNet noise predictor + IR-SDE reverse process (EDiffSR/codes: DenoisingNAFNet_arch.py,
  * module_util.py, utils/sde_utils.py) --------------------------------------------------------------------------------
  * An object of its own, independent of fdsr_handle.  fp32 activations (NHWC inside), every 1x1 / 2x2 / 3x3 convolution a GEMM
