@@ -51,6 +51,15 @@ class FdsrSwinirConfig(C.Structure):
                 ('upscale', C.c_int32), ('patch_norm', C.c_int32), ('img_range', C.c_float), ('mean', C.c_float * 3)]
 
 
+FDSR_HAT_MAX_LAYERS = 8
+FDSR_HAT_GRAPH = 1
+
+
+class FdsrHatConfig(C.Structure):
+    _fields_ = FdsrSwinirConfig._fields_ + [('compress_ratio', C.c_int32), ('squeeze_factor', C.c_int32), ('conv_scale', C.c_float),
+                                            ('overlap_win_size', C.c_int32)]
+
+
 class FdsrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f'libfdsr_hip error {code}: {msg}')
@@ -142,6 +151,14 @@ SYMBOLS = {
                                            C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_void_p]),
     'fdsr_swinir_to_u8': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'fdsr_swinir_destroy': (None, [C.c_void_p]),
+    'fdsr_hat_create': (C.c_int, [C.POINTER(FdsrHatConfig), C.POINTER(C.c_void_p)]),
+    'fdsr_hat_load': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    'fdsr_hat_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    'fdsr_hat_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                   C.c_int]),
+    'fdsr_hat_debug_tensor': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                        C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'fdsr_hat_destroy': (None, [C.c_void_p]),
     'fdsr_nafnet_create': (C.c_int, [C.POINTER(FdsrNafnetConfig), C.POINTER(C.c_void_p)]),
     'fdsr_nafnet_num_weights': (C.c_int, [C.c_void_p]),
     'fdsr_nafnet_weight_info': (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),

@@ -1,0 +1,785 @@
+// HAT (MSI_SR_model/model/hat.py: GeneratorResNet, upsampler='pixelshuffle', resi_connection='1conv', patch_size 1, ape=False)
+// inference in exact fp32 on gfx950.
+//
+//   x    = (reflect_pad(img, to a multiple of 16) - mean) * img_range                      NCHW -> NHWC       swin_input_kernel
+//   f    = conv_first(x);  t = patch_embed.norm(f)
+//   per RHAG: depth HABs, one OCAB, t = conv(t) + t_in
+//     HAB:   n = norm1(t);  t += proj(window_attention(qkv(n))) + conv_scale * gate * cab,   cab = conv(gelu(conv(n))),
+//            gate = sigmoid(W2 relu(W1 mean_HW(cab) + b1) + b2);   t += fc2(gelu(fc1(norm2(t))))
+//     OCAB:  n = norm1(t);  t += proj(attention(q of 16 x 16 windows, k / v of the 24 x 24 windows around them));  t += mlp(norm2(t))
+//   y    = conv_after_body(norm(t)) + f;  y = leaky_relu(conv_before_upsample(y), 0.01)
+//   y    = pixel_shuffle(conv(y)) per factor of two, ONE convolution for every stage (one conv + PixelShuffle(3) at scale 3);
+//          out = conv_last(y) / img_range + mean at the PADDED size times the scale (the reference does not crop), NCHW
+//
+// The token GEMM, LayerNorm and the input kernel are fdsr_swin_common.h's.  New here:
+//   hat_attn_kernel<OCA>  one workgroup per (image, window, head, block of 32 queries).  The block's full score rows stay in
+//                         LDS ([key][query], 256 or 576 keys): exact max / exp / sum / divide.  k, and after the softmax v, stream
+//                         through LDS in chunks of 128 keys.  The roll, the partition, the region ids, the -100 mask, the bias
+//                         (gathered and transposed at load) and the out-of-image test of an OCA key are addresses and LDS
+//                         contents.  An OCA key outside the image is a zero k and a zero v: its logit is its bias alone and it
+//                         counts in the denominator.
+//   two GEMM epilogues    EPI_COLSUM stores the tile and leaves the column sums of each wave's 64 rows in a small buffer;
+//                         EPI_HAB writes acc + bias + shortcut + conv_scale * gate[b][c] * cab[m][c].
+//   hat_gate_kernel       per image: the partial sums in row order, / HW, the two 1x1 layers, ReLU, sigmoid.
+// Every output element has one fixed summation order (no atomics, no split-K): reruns are bitwise equal and an image's result
+// depends neither on B nor on its place in the batch.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "fdsr_engine_int.h"
+#include "fdsr_swin_common.h"
+
+using namespace fdsr_int;
+
+namespace {
+
+constexpr int WS = 16, WT = WS * WS;       // the window and its tokens
+constexpr int WSE = 24, WKT = WSE * WSE;   // the overlapping window (overlap_ratio 0.5) and its keys
+constexpr int QB = 32;                     // queries of one workgroup: a score row pitch of 32 keeps the two k rows of an MFMA operand read 32 banks apart
+constexpr int KC = 128;                    // keys per staged chunk
+constexpr int KP = KC + 32;                // pitch of the [d][key] chunk
+constexpr int NBUF = 10;
+
+enum HatEpi { EPI_COLSUM = EPI_EXT, EPI_HAB = EPI_EXT + 1 };
+
+struct HatGemmArgs : GemmArgs {
+  float* colsum;        // EPI_COLSUM: [M / 64][N]
+  const float* gate;    // EPI_HAB: [B][N]
+  const float* cab;     // EPI_HAB: [M][N]
+  float conv_scale;
+};
+
+}  // namespace
+
+namespace {
+
+template <int EPI, class ARGS>
+__device__ void gemm_epilogue_ext(const ARGS& p, const f32x16 (&acc)[2], int row0, int co, int h, float bias) {
+  if constexpr (EPI == EPI_COLSUM) {
+    // M is a multiple of 256 here (whole 16 x 16 windows): every row of the tile exists and 64 rows never span two images
+    float s = 0.f;
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int om = row0 + mb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+        const float v = acc[mb][i] + bias;
+        p.out[(size_t)om * p.N + co] = v;
+        s += v;
+      }
+    s += __shfl_xor(s, 32, 64);   // the other 32 rows of this column
+    if (h == 0) p.colsum[(size_t)(row0 >> 6) * p.N + co] = s;
+  } else {
+    const int HW = p.H * p.W;
+#pragma unroll
+    for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int om = row0 + mb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+        if (om >= p.M) continue;
+        const size_t o = (size_t)om * p.N + co;
+        const float v = acc[mb][i] + bias;
+        // shortcut + attn_x + conv_x * conv_scale, conv_x = cab * gate
+        p.out[o] = __fadd_rn(__fadd_rn(p.res[o], v), __fmul_rn(__fmul_rn(p.cab[o], p.gate[(size_t)(om / HW) * p.N + co]), p.conv_scale));
+      }
+  }
+}
+
+// ChannelAttention's gate of one image: mean over the map from the 64-row partial sums, in row order; Conv1x1 C -> Cs, ReLU,
+// Conv1x1 Cs -> C, sigmoid.  w1 [Cs][C], w2 [C][Cs] as the checkpoint holds them.
+__global__ void __launch_bounds__(256) hat_gate_kernel(const float* __restrict__ colsum, const float* __restrict__ w1, const float* __restrict__ b1,
+                                                       const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ gate,
+                                                       int tiles, int C, int Cs, float hw) {
+  __shared__ float sMean[LN_MAX_C], sHid[LN_MAX_C];
+  const int b = blockIdx.x, t = threadIdx.x;
+  for (int c = t; c < C; c += 256) {
+    float s = 0.f;
+    for (int k = 0; k < tiles; ++k) s += colsum[((size_t)b * tiles + k) * C + c];
+    sMean[c] = s / hw;
+  }
+  __syncthreads();
+  for (int r = t; r < Cs; r += 256) {
+    float a = 0.f;
+    for (int c = 0; c < C; ++c) a += w1[(size_t)r * C + c] * sMean[c];
+    sHid[r] = fmaxf(a + b1[r], 0.f);
+  }
+  __syncthreads();
+  for (int c = t; c < C; c += 256) {
+    float a = 0.f;
+    for (int r = 0; r < Cs; ++r) a += w2[(size_t)c * Cs + r] * sHid[r];
+    gate[(size_t)b * C + c] = 1.f / (1.f + expf(-(a + b2[c])));
+  }
+}
+
+// the tap 'cab': the gated CAB output, which the forward never stores (proj's epilogue forms it)
+__global__ void __launch_bounds__(256) hat_gate_mul_kernel(const float* __restrict__ cab, const float* __restrict__ gate, float* __restrict__ y,
+                                                           int HW, int C, size_t total) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const size_t m = i / C;
+  y[i] = __fmul_rn(cab[i], gate[(m / HW) * C + (i - m * C)]);
+}
+
+// Attention of one (image, window, head, block of QB queries).  qkv: [B][H W][3 C], a token's row is q | k | v, each head-major.
+// Query token (ty, tx) of window (wy, wx) is the pixel ((wy 16 + ty + shift) mod H, (wx 16 + tx + shift) mod W) -- torch.roll
+// by -shift, then window_partition -- and the output goes back to the same pixel.
+//   OCA = false: the keys are the window's own 256 tokens; biasT [heads][256 keys][256 queries]; shift > 0: tokens of different
+//                regions of the rolled image (three slices per axis: [0, H - 16), [H - 16, H - shift), [H - shift, H)) get -100.
+//   OCA = true:  shift = 0; key (ky, kx), 0 <= ky, kx < 24, is the pixel (wy 16 - 4 + ky, wx 16 - 4 + kx) -- nn.Unfold(24, stride
+//                16, padding 4) of the qkv output -- and a zero k and v outside the image; biasT [heads][576 keys][256 queries].
+template <bool OCA>
+__global__ void __launch_bounds__(256) hat_attn_kernel(const float* __restrict__ qkv, const float* __restrict__ biasT, float* __restrict__ out,
+                                                       int H, int W, int C, int heads, int hd, int shift, float scale) {
+  constexpr int NK = OCA ? WKT : WT;
+  __shared__ float sSt[NK * QB];    // [key][query]: the scores, then the probabilities
+  __shared__ float sQt[HD * QB];    // [d][query], q * scale
+  __shared__ float sKV[HD * KP];    // a chunk of k as [d][key] (pitch KP), then of v as [key][d]
+  __shared__ float sRed[8 * QB];
+  __shared__ int sKPix[NK];         // the pixel of a key, -1 outside the image
+  __shared__ int sKRid[OCA ? 1 : NK];
+  __shared__ int sQPix[QB], sQRid[QB];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int nwx = W / WS, nwin = nwx * (H / WS);
+  int bx = blockIdx.x;
+  const int qb = bx % (WT / QB);
+  bx /= WT / QB;
+  const int head = bx % heads;
+  bx /= heads;
+  const int win = bx % nwin, b = bx / nwin;
+  const int wy = win / nwx, wx = win - wy * nwx;
+
+  auto region = [&](int ys, int xs) {
+    const int rh = ys < H - WS ? 0 : ys < H - shift ? 1 : 2, rw = xs < W - WS ? 0 : xs < W - shift ? 1 : 2;
+    return shift > 0 ? rh * 3 + rw : 0;
+  };
+  for (int kk = t; kk < NK; kk += 256) {
+    if (OCA) {
+      const int ky = kk / WSE, py = wy * WS - (WSE - WS) / 2 + ky, px = wx * WS - (WSE - WS) / 2 + (kk - ky * WSE);
+      sKPix[kk] = (py >= 0 && py < H && px >= 0 && px < W) ? py * W + px : -1;
+    } else {
+      const int ys = wy * WS + (kk >> 4), xs = wx * WS + (kk & 15);
+      sKPix[kk] = ((ys + shift) % H) * W + (xs + shift) % W;
+      sKRid[kk] = region(ys, xs);
+    }
+  }
+  if (t < QB) {
+    const int q = qb * QB + t, ys = wy * WS + (q >> 4), xs = wx * WS + (q & 15);
+    sQPix[t] = ((ys + shift) % H) * W + (xs + shift) % W;
+    sQRid[t] = region(ys, xs);
+  }
+  __syncthreads();
+  const size_t img = (size_t)b * H * W;
+  const int r31 = lane & 31, h = lane >> 5;
+
+  // q by token (lane = token: conflict-free transposed stores)
+  {
+    const int i = t & 31, d0 = (t >> 5) * 4;
+    const float* row = qkv + (img + sQPix[i]) * 3 * C + head * hd;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int d = d0 + e;
+      sQt[d * QB + i] = d < hd ? row[d] * scale : 0.f;
+    }
+  }
+  // St[j][i] = sum_d k[j][d] q[i][d] + bias (+ mask), a chunk of keys at a time: wave w owns keys [32 w, 32 w + 32) of the chunk
+  const float* bh = biasT + (size_t)head * NK * WT;
+  for (int c0 = 0; c0 < NK; c0 += KC) {
+    __syncthreads();   // the previous chunk's operand reads are done
+    {
+      const int jj = t & (KC - 1), d0 = (t >> 7) * 16;
+      const int pix = c0 + jj < NK ? sKPix[c0 + jj] : -1;
+      const float* row = qkv + (img + (pix < 0 ? 0 : pix)) * 3 * C + C + head * hd;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int d = d0 + e;
+        sKV[d * KP + jj] = (pix >= 0 && d < hd) ? row[d] : 0.f;
+      }
+    }
+    __syncthreads();
+    const int j0 = c0 + wave * 32;
+    if (j0 < NK) {
+      f32x16 acc;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+      for (int s = 0; s < HD / 2; ++s) {
+        const int kr = 2 * s + h;
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sKV[kr * KP + wave * 32 + r31], sQt[kr * QB + r31], acc, 0, 0, 0);
+      }
+      const int ri = sQRid[r31], qg = qb * QB + r31;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int j = j0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        float v = acc[r] + bh[(size_t)j * WT + qg];
+        if (!OCA && sKRid[j] != ri) v += -100.f;
+        sSt[j * QB + r31] = v;
+      }
+    }
+  }
+  __syncthreads();
+  // row softmax: thread (part, i) covers the keys j = part (mod 8) of query i; the eight partial results combine in order
+  {
+    const int i = t & 31, part = t >> 5;
+    float m = sSt[part * QB + i];
+    for (int j = part + 8; j < NK; j += 8) m = fmaxf(m, sSt[j * QB + i]);
+    sRed[part * QB + i] = m;
+    __syncthreads();
+    m = sRed[i];
+#pragma unroll
+    for (int q = 1; q < 8; ++q) m = fmaxf(m, sRed[q * QB + i]);
+    __syncthreads();
+    float s = 0.f;
+    for (int j = part; j < NK; j += 8) {
+      const float e = expf(sSt[j * QB + i] - m);
+      sSt[j * QB + i] = e;
+      s += e;
+    }
+    sRed[part * QB + i] = s;
+    __syncthreads();
+    s = sRed[i];
+#pragma unroll
+    for (int q = 1; q < 8; ++q) s += sRed[q * QB + i];
+    for (int j = part; j < NK; j += 8) sSt[j * QB + i] = sSt[j * QB + i] / s;
+  }
+  // O[i][d] = sum_j P[i][j] v[j][d], the keys in order (one chain per output): wave 0 owns the 32 queries
+  f32x16 o;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) o[i] = 0.f;
+  for (int c0 = 0; c0 < NK; c0 += KC) {
+    __syncthreads();   // the probabilities are written; the previous chunk's reads are done
+    {
+      const int d = t & 31;
+#pragma unroll
+      for (int e = 0; e < KC / 8; ++e) {
+        const int jj = (t >> 5) + 8 * e;
+        const int pix = c0 + jj < NK ? sKPix[c0 + jj] : -1;
+        sKV[jj * HD + d] = (pix >= 0 && d < hd) ? qkv[(img + pix) * 3 * C + 2 * C + head * hd + d] : 0.f;
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {
+      const int n = NK - c0 < KC ? NK - c0 : KC;
+      for (int s = 0; s < n / 2; ++s) {
+        const int kr = 2 * s + h;
+        o = __builtin_amdgcn_mfma_f32_32x32x2f32(sSt[(c0 + kr) * QB + r31], sKV[kr * HD + r31], o, 0, 0, 0);
+      }
+    }
+  }
+  if (wave == 0 && r31 < hd) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
+      out[(img + sQPix[i]) * C + head * hd + r31] = o[r];
+    }
+  }
+}
+
+enum Kind { LINEAR, CONV, LNORM, RPB_SA, RPB_OCA, GATE };
+
+// One named module of the checkpoint: LINEAR / CONV / LNORM / GATE own name.weight and name.bias, RPB_* own the tensor `name`
+struct LayerDesc {
+  std::string name;
+  Kind kind;
+  int cin, cout;   // LNORM: cout = C;  RPB_*: cout = heads
+  bool rpb() const { return kind == RPB_SA || kind == RPB_OCA; }
+  int tensors() const { return rpb() ? 1 : 2; }
+  std::string tensor_name(int j) const { return rpb() ? name : name + (j == 0 ? ".weight" : ".bias"); }
+  std::vector<int64_t> shape(int j) const {
+    if (kind == RPB_SA) return {(2 * WS - 1) * (2 * WS - 1), cout};
+    if (kind == RPB_OCA) return {(WS + WSE - 1) * (WS + WSE - 1), cout};
+    if (j == 1 || kind == LNORM) return {cout};
+    if (kind == CONV) return {cout, cin, 3, 3};
+    if (kind == GATE) return {cout, cin, 1, 1};
+    return {cout, cin};
+  }
+};
+
+struct Walker {
+  Mode mode;
+  fdsr_hat_config cfg{};
+  std::vector<LayerDesc>* table = nullptr;      // TABLE: appended to
+  std::vector<std::string>* taps = nullptr;     // TABLE: the tap names, appended to
+  size_t need[NBUF] = {};                       // SIZE: floats per image of each buffer
+  int N = 0, Hin = 0, Win = 0;
+  const float* img = nullptr;                   // RUN: the input, NCHW
+  float* dst = nullptr;                         // RUN: the output, NCHW (null: a debug walk, which ends at `stop`)
+  float* buf[NBUF] = {};
+  float* const* w = nullptr;
+  float* const* b = nullptr;
+  hipStream_t st = nullptr;
+  int li = 0;                                   // the next layer's index (load order)
+  int reuse = -1;                               // >= 0: the next gemm runs this layer again (the shared upsampling convolution)
+  const char* stop = nullptr;                   // RUN: the tap to end at
+  bool done = false;
+  T tapped{};
+  int err = FDSR_OK;
+
+  bool live() const { return mode == RUN && err == FDSR_OK && !done; }
+  bool stops_at(const std::string& name) const { return live() && stop && name == stop; }
+  void touch(const T& t) { need[t.buf] = std::max(need[t.buf], (size_t)t.H * t.W * t.C); }
+  void check(hipError_t e) {
+    if (e != hipSuccess && err == FDSR_OK) err = fail(nullptr, FDSR_E_HIP, "fdsr_hat: kernel launch failed: %s", hipGetErrorString(e));
+  }
+  void tap(const std::string& name, const T& t) {
+    if (mode == TABLE) taps->push_back(name);
+    if (stops_at(name)) { done = true; tapped = t; }
+  }
+  int layer(const std::string& name, Kind kind, int cin, int cout) {
+    if (reuse >= 0) {
+      const int idx = reuse;
+      reuse = -1;
+      return idx;
+    }
+    if (mode == TABLE) table->push_back(LayerDesc{name, kind, cin, cout});
+    return li++;
+  }
+
+  template <int GATHER, int EPI>
+  void launch_gemm(const HatGemmArgs& a, bool vec) {
+    if constexpr (EPI >= EPI_EXT) check(launch_swin_gemm<GATHER, EPI>(a, vec, st));
+    else check(launch_swin_gemm<GATHER, EPI>(static_cast<const GemmArgs&>(a), vec, st));
+  }
+
+  // out = epilogue(gather(in) . W + bias).  res: the EPI_RES / EPI_HAB addend.  r: the EPI_SHUFFLE factor.  cab, aux: EPI_HAB's
+  // CAB output and gate, EPI_COLSUM's partial sums (aux).
+  T gemm(const std::string& name, Kind kind, int epi, const T& in, int cout, int ob, const T* res = nullptr, int r = 1, const T* cab = nullptr,
+         int aux = -1) {
+    const int idx = layer(name, kind, in.C, cout);
+    T out{ob, in.H * r, in.W * r, cout / (r * r)};
+    if (mode == SIZE && epi != EPI_NCHW) touch(out);
+    if (!live()) return out;
+    HatGemmArgs a{};
+    a.x = buf[in.buf];
+    a.w = w[idx];
+    a.bias = b[idx];
+    a.res = res ? buf[res->buf] : nullptr;
+    a.out = epi == EPI_NCHW ? dst : buf[ob];
+    a.M = N * in.H * in.W;
+    a.N = cout;
+    a.K = kind == CONV ? 9 * in.C : in.C;
+    a.Kpad = gemm_kpad(kind == CONV, in.C);
+    a.Npad = gemm_npad(cout);
+    a.H = in.H;
+    a.W = in.W;
+    a.Cin = in.C;
+    a.r = r;
+    a.Hc = in.H;          // no crop: the reference returns the padded size
+    a.Wc = in.W;
+    a.slope = 0.01f;      // nn.LeakyReLU()'s default
+    a.range = cfg.img_range;
+    for (int c = 0; c < 3; ++c) a.mean[c] = cfg.mean[c];
+    a.colsum = epi == EPI_COLSUM ? buf[aux] : nullptr;
+    a.gate = epi == EPI_HAB ? buf[aux] : nullptr;
+    a.cab = cab ? buf[cab->buf] : nullptr;
+    a.conv_scale = cfg.conv_scale;
+    const bool vec = in.C % 4 == 0;
+    if (kind == LINEAR) {
+      if (epi == EPI_NONE) launch_gemm<ROWS, EPI_NONE>(a, vec);
+      else if (epi == EPI_GELU) launch_gemm<ROWS, EPI_GELU>(a, vec);
+      else if (epi == EPI_RES) launch_gemm<ROWS, EPI_RES>(a, vec);
+      else launch_gemm<ROWS, EPI_HAB>(a, vec);
+    } else {
+      if (epi == EPI_NONE) launch_gemm<CONV3, EPI_NONE>(a, vec);
+      else if (epi == EPI_GELU) launch_gemm<CONV3, EPI_GELU>(a, vec);
+      else if (epi == EPI_COLSUM) launch_gemm<CONV3, EPI_COLSUM>(a, vec);
+      else if (epi == EPI_LRELU) launch_gemm<CONV3, EPI_LRELU>(a, vec);
+      else if (epi == EPI_RES) launch_gemm<CONV3, EPI_RES>(a, vec);
+      else if (epi == EPI_SHUFFLE) launch_gemm<CONV3, EPI_SHUFFLE>(a, vec);
+      else launch_gemm<CONV3, EPI_NCHW>(a, vec);
+    }
+    return out;
+  }
+
+  T norm(const std::string& name, const T& in, int ob) {
+    const int idx = layer(name, LNORM, in.C, in.C);
+    T out{ob, in.H, in.W, in.C};
+    if (mode == SIZE) touch(out);
+    if (!live()) return out;
+    const int M = N * in.H * in.W;
+    hipLaunchKernelGGL(swin_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, buf[in.buf], w[idx], b[idx], buf[ob], M, in.C);
+    check(hipGetLastError());
+    return out;
+  }
+
+  // attention over the q | k | v rows of `qkv`, into `ob`
+  T attention(const std::string& name, bool oca, const T& qkv, int heads, int shift, int ob) {
+    const int idx = layer(name, oca ? RPB_OCA : RPB_SA, 0, heads);
+    const int C = qkv.C / 3;
+    T out{ob, qkv.H, qkv.W, C};
+    if (mode == SIZE) touch(out);
+    if (!live()) return out;
+    const int hd = C / heads;
+    const unsigned blocks = (unsigned)(N * (qkv.H / WS) * (qkv.W / WS) * heads * (WT / QB));
+    const float scale = 1.f / sqrtf((float)hd);
+    if (oca) hipLaunchKernelGGL(hat_attn_kernel<true>, dim3(blocks), dim3(256), 0, st, buf[qkv.buf], w[idx], buf[ob], qkv.H, qkv.W, C, heads, hd, 0, scale);
+    else hipLaunchKernelGGL(hat_attn_kernel<false>, dim3(blocks), dim3(256), 0, st, buf[qkv.buf], w[idx], buf[ob], qkv.H, qkv.W, C, heads, hd, shift, scale);
+    check(hipGetLastError());
+    return out;
+  }
+
+  // the gate of `cab` [N][H][W][C] from its partial column sums (buffer 8), into buffer 9
+  void gate(const std::string& name, const T& cab) {
+    const int Cs = cab.C / cfg.squeeze_factor;
+    const int i1 = layer(name + ".1", GATE, cab.C, Cs), i2 = layer(name + ".3", GATE, Cs, cab.C);
+    if (mode == SIZE) {
+      need[8] = std::max(need[8], (size_t)(cab.H * cab.W / 64) * cab.C);
+      need[9] = std::max(need[9], (size_t)cab.C);
+    }
+    if (!live()) return;
+    hipLaunchKernelGGL(hat_gate_kernel, dim3((unsigned)N), dim3(256), 0, st, buf[8], w[i1], b[i1], w[i2], b[i2], buf[9], cab.H * cab.W / 64, cab.C, Cs,
+                       (float)(cab.H * cab.W));
+    check(hipGetLastError());
+  }
+
+  T mlp(const std::string& p, const T& y) {
+    T n2 = norm(p + ".norm2", y, 4);
+    T hid = gemm(p + ".mlp.fc1", LINEAR, EPI_GELU, n2, cfg.mlp_hidden, 5);
+    return gemm(p + ".mlp.fc2", LINEAR, EPI_RES, hid, y.C, 3, &y);
+  }
+
+  // The whole network.  Buffers: 0 the packed input, 1 conv_first's output (kept for conv_after_body), 2 / 3 the tokens (a
+  // RHAG's input stays in 2 while its blocks work in 3), 4 a LayerNorm's or an attention's output, 5 qkv / the MLP's hidden rows,
+  // 6 / 7 the CAB's hidden map and output, 8 its partial column sums, 9 the gate; the reconstruction tail alternates between 4
+  // and 5.
+  void walk() {
+    const int C = cfg.embed_dim;
+    const int Hp = round_up(std::max(Hin, 1), WS), Wp = round_up(std::max(Win, 1), WS);
+    T x{0, Hp, Wp, 3};
+    if (mode == SIZE) touch(x);
+    if (live()) {
+      const size_t total = (size_t)N * Hp * Wp * 3;
+      hipLaunchKernelGGL(swin_input_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, img, buf[0], Hin, Win, Hp, Wp, cfg.mean[0],
+                         cfg.mean[1], cfg.mean[2], cfg.img_range, total);
+      check(hipGetLastError());
+    }
+    const T f = gemm("conv_first", CONV, EPI_NONE, x, C, 1);
+    tap("conv_first", f);
+    T a{2, Hp, Wp, C};
+    if (cfg.patch_norm) {
+      a = norm("patch_embed.norm", f, 2);
+    } else {
+      if (mode == SIZE) touch(a);
+      if (live()) check(hipMemcpyAsync(buf[2], buf[1], (size_t)N * Hp * Wp * C * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    tap("patch_embed.norm", a);
+    for (int i = 0; i < cfg.n_layers; ++i) {
+      const std::string lp = "layers." + std::to_string(i), gp = lp + ".residual_group";
+      const int heads = cfg.num_heads[i];
+      T cur = a;
+      for (int j = 0; j < cfg.depths[i]; ++j) {
+        const std::string bp = gp + ".blocks." + std::to_string(j), tp = lp + ".blocks." + std::to_string(j);
+        T n1 = norm(bp + ".norm1", cur, 4);
+        T qkv = gemm(bp + ".attn.qkv", LINEAR, EPI_NONE, n1, 3 * C, 5);
+        T mid = gemm(bp + ".conv_block.cab.0", CONV, EPI_GELU, n1, C / cfg.compress_ratio, 6);
+        T cab = gemm(bp + ".conv_block.cab.2", CONV, EPI_COLSUM, mid, C, 7, nullptr, 1, nullptr, 8);
+        gate(bp + ".conv_block.cab.3.attention", cab);
+        if (stops_at(tp + ".cab")) {
+          const size_t total = (size_t)N * Hp * Wp * C;
+          hipLaunchKernelGGL(hat_gate_mul_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, buf[7], buf[9], buf[6], Hp * Wp, C, total);
+          check(hipGetLastError());
+        }
+        if (mode == SIZE) touch(T{6, Hp, Wp, C});
+        tap(tp + ".cab", T{6, Hp, Wp, C});
+        T o = attention(bp + ".attn.relative_position_bias_table", false, qkv, heads, j % 2 ? WS / 2 : 0, 4);
+        T y = gemm(bp + ".attn.proj", LINEAR, EPI_HAB, o, C, 3, &cur, 1, &cab, 9);
+        tap(tp + ".attn", y);
+        cur = mlp(bp, y);
+        tap(tp + ".mlp", cur);
+      }
+      {
+        const std::string op = gp + ".overlap_attn";
+        T n1 = norm(op + ".norm1", cur, 4);
+        T qkv = gemm(op + ".qkv", LINEAR, EPI_NONE, n1, 3 * C, 5);
+        T o = attention(op + ".relative_position_bias_table", true, qkv, heads, 0, 4);
+        T y = gemm(op + ".proj", LINEAR, EPI_RES, o, C, 3, &cur);
+        tap(lp + ".ocab.attn", y);
+        cur = mlp(op, y);
+        tap(lp + ".ocab.mlp", cur);
+      }
+      a = gemm(lp + ".conv", CONV, EPI_RES, cur, C, 2, &a);
+      tap(lp, a);
+    }
+    T n = norm("norm", a, 4);
+    T y = gemm("conv_after_body", CONV, EPI_RES, n, C, 3, &f);
+    tap("conv_after_body", y);
+    y = gemm("conv_before_upsample.0", CONV, EPI_LRELU, y, NUM_FEAT, 4);
+    int ob = 5;
+    if (cfg.upscale == 3) {
+      y = gemm("upsample.upsampling.0", CONV, EPI_SHUFFLE, y, 9 * NUM_FEAT, ob, nullptr, 3);
+      tap("upsample.0", y);
+    } else {
+      // Upsample repeats ONE list of modules: the same Conv2d(64, 256) runs in every stage
+      int shared = -1;
+      for (int k = 0; (1 << k) < cfg.upscale; ++k, ob = 9 - ob) {
+        reuse = shared;
+        y = gemm("upsample.upsampling.0", CONV, EPI_SHUFFLE, y, 4 * NUM_FEAT, ob, nullptr, 2);
+        if (k == 0) shared = li - 1;
+        tap("upsample." + std::to_string(k), y);
+      }
+    }
+    gemm("conv_last", CONV, EPI_NCHW, y, 3, 0);
+  }
+};
+
+struct Plan { size_t off[NBUF]; size_t bytes; };
+
+struct Graph { int B, H, W; const void *x, *out, *ws; hipGraphExec_t exec; };
+
+}  // namespace
+
+struct fdsr_hat_obj {
+  fdsr_hat_config cfg{};
+  std::vector<LayerDesc> table;
+  std::vector<std::string> taps;
+  std::vector<unsigned char> have;   // [layer * 2 + j]
+  // device: LINEAR / CONV packed [Kpad][Npad] + bias [Npad]; LNORM gamma + beta; GATE as the checkpoint holds it; RPB_* biasT [heads][keys][256]
+  std::vector<float*> w, b;
+  std::vector<Graph> graphs;
+};
+
+namespace {
+
+Walker walker(fdsr_hat s, Mode mode, int B, int H, int W) {
+  Walker wk{mode};
+  wk.cfg = s->cfg;
+  wk.N = B;
+  wk.Hin = H;
+  wk.Win = W;
+  return wk;
+}
+
+Plan make_plan(fdsr_hat s, int B, int H, int W) {
+  Walker wk = walker(s, SIZE, B, H, W);
+  wk.walk();
+  Plan pl{};
+  size_t off = 0;
+  for (int i = 0; i < NBUF; ++i) {
+    pl.off[i] = off;
+    off = align_up(off + (size_t)B * wk.need[i] * sizeof(float), 256);
+  }
+  pl.bytes = off;
+  return pl;
+}
+
+void drop_graphs(fdsr_hat s) {
+  for (Graph& g : s->graphs)
+    if (g.exec) (void)hipGraphExecDestroy(g.exec);
+  s->graphs.clear();
+}
+
+// F.pad's rule for 'reflect': the padding must be smaller than the side it mirrors
+int check_shape(const char* fn, int B, int H, int W) {
+  if (B < 1 || H < 1 || W < 1) return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, B, H, W);
+  const int ph = round_up(H, WS) - H, pw = round_up(W, WS) - W;
+  if (ph >= H || pw >= W)
+    return fail(nullptr, FDSR_E_INVALID, "%s: a %dx%d image cannot be reflect-padded by (%d, %d) to a multiple of the window", fn, H, W, ph, pw);
+  return FDSR_OK;
+}
+
+// everything a forward or a debug walk checks, then the walker ready to run
+int prepare(fdsr_hat s, const char* fn, const float* x, int B, int H, int W, void* ws, size_t ws_bytes, void* stream, Walker* out) {
+  if (!s || !x || !ws) return fail(nullptr, FDSR_E_INVALID, "%s: null argument", fn);
+  int rc = check_shape(fn, B, H, W);
+  if (rc) return rc;
+  for (size_t L = 0; L < s->table.size(); ++L)
+    for (int j = 0; j < s->table[L].tensors(); ++j)
+      if (!s->have[L * 2 + j]) return fail(nullptr, FDSR_E_STATE, "%s: tensor '%s' is missing", fn, s->table[L].tensor_name(j).c_str());
+  const Plan pl = make_plan(s, B, H, W);
+  if (ws_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(ws) & 255))
+    return fail(nullptr, FDSR_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes) or not 256-byte aligned", fn, ws_bytes, pl.bytes);
+  Walker wk = walker(s, RUN, B, H, W);
+  wk.img = x;
+  for (int i = 0; i < NBUF; ++i) wk.buf[i] = reinterpret_cast<float*>(static_cast<char*>(ws) + pl.off[i]);
+  wk.w = s->w.data();
+  wk.b = s->b.data();
+  wk.st = reinterpret_cast<hipStream_t>(stream);
+  *out = wk;
+  return FDSR_OK;
+}
+
+// upsample.upsampling.{2,4}.* name the tensor of upsample.upsampling.0.* again (one Conv2d in every stage)
+std::string canonical_name(fdsr_hat s, const char* name) {
+  static const char prefix[] = "upsample.upsampling.";
+  std::string nm(name);
+  if (s->cfg.upscale == 3 || nm.compare(0, sizeof(prefix) - 1, prefix) != 0) return nm;
+  const size_t dot = nm.find('.', sizeof(prefix) - 1);
+  if (dot == std::string::npos) return nm;
+  const std::string idx = nm.substr(sizeof(prefix) - 1, dot - (sizeof(prefix) - 1));
+  for (int k = 1; (1 << k) < s->cfg.upscale; ++k)
+    if (idx == std::to_string(2 * k)) return prefix + std::string("0") + nm.substr(dot);
+  return nm;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fdsr_hat_create(const fdsr_hat_config* cfg, fdsr_hat* out) {
+  if (!cfg || !out) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: null argument");
+  const fdsr_hat_config& c = *cfg;
+  if (c.window_size != WS) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: window_size %d is not supported (16 only)", c.window_size);
+  if (c.overlap_win_size != WSE)
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: overlap window %d is not supported (24 only: overlap_ratio 0.5)", c.overlap_win_size);
+  if (c.n_layers < 1 || c.n_layers > FDSR_HAT_MAX_LAYERS)
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: %d layers (1..%d)", c.n_layers, FDSR_HAT_MAX_LAYERS);
+  if (c.embed_dim < 1 || c.embed_dim > LN_MAX_C || c.mlp_hidden < 1)
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: embed_dim %d (1..%d), mlp hidden width %d", c.embed_dim, LN_MAX_C, c.mlp_hidden);
+  if (c.compress_ratio < 1 || c.embed_dim % c.compress_ratio)
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: embed_dim %d is not divisible by compress_ratio %d", c.embed_dim, c.compress_ratio);
+  if (c.squeeze_factor < 1 || c.embed_dim / c.squeeze_factor < 1)
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: squeeze_factor %d leaves no channel of embed_dim %d", c.squeeze_factor, c.embed_dim);
+  for (int i = 0; i < c.n_layers; ++i) {
+    if (c.depths[i] < 1 || c.num_heads[i] < 1 || c.embed_dim % c.num_heads[i])
+      return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: layer %d: depth %d, embed_dim %d over %d heads", i, c.depths[i], c.embed_dim,
+                  c.num_heads[i]);
+    if (c.embed_dim / c.num_heads[i] > HD)
+      return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: layer %d: head_dim %d is not supported (at most %d)", i, c.embed_dim / c.num_heads[i],
+                  HD);
+  }
+  if (c.upscale != 2 && c.upscale != 3 && c.upscale != 4 && c.upscale != 8)
+    return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: upscale %d is not supported (2, 3, 4, 8)", c.upscale);
+  if (!(c.img_range > 0.f)) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: img_range must be positive");
+  fdsr_hat s = new (std::nothrow) fdsr_hat_obj();
+  if (!s) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: out of host memory");
+  s->cfg = c;
+  Walker wk = walker(s, TABLE, 1, WS, WS);
+  wk.table = &s->table;
+  wk.taps = &s->taps;
+  wk.walk();
+  s->have.assign(s->table.size() * 2, 0);
+  s->w.assign(s->table.size(), nullptr);
+  s->b.assign(s->table.size(), nullptr);
+  *out = s;
+  return FDSR_OK;
+}
+
+void fdsr_hat_destroy(fdsr_hat s) {
+  if (!s) return;
+  drop_graphs(s);
+  for (float* p : s->w)
+    if (p) (void)hipFree(p);
+  for (float* p : s->b)
+    if (p) (void)hipFree(p);
+  delete s;
+}
+
+int fdsr_hat_load(fdsr_hat s, const char* name, const float* host_f32, const int64_t* shape, int ndim) {
+  if (!s || !name || !host_f32 || (ndim > 0 && !shape) || ndim < 0) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_load: bad arguments");
+  const std::string nm = canonical_name(s, name);
+  int layer = -1, j = -1;
+  for (size_t L = 0; L < s->table.size() && layer < 0; ++L)
+    for (int q = 0; q < s->table[L].tensors(); ++q)
+      if (s->table[L].tensor_name(q) == nm) { layer = (int)L; j = q; break; }
+  if (layer < 0) return fail(nullptr, FDSR_E_KEY, "fdsr_hat_load: unknown tensor '%s'", name);
+  const LayerDesc& L = s->table[layer];
+  const std::vector<int64_t> want = L.shape(j);
+  if (ndim != (int)want.size() || !std::equal(want.begin(), want.end(), shape))
+    return fail(nullptr, FDSR_E_KEY, "fdsr_hat_load: '%s' has the wrong shape", name);
+  std::vector<float> packed;
+  if (L.kind == RPB_SA) {
+    // biasT[head][j][i] = table[(yi - yj + 15) * 31 + (xi - xj + 15)][head]: the gather of relative_position_index_SA, once
+    packed.resize((size_t)L.cout * WT * WT);
+    for (int hh = 0; hh < L.cout; ++hh)
+      for (int kj = 0; kj < WT; ++kj)
+        for (int qi = 0; qi < WT; ++qi) {
+          const int idx = ((qi >> 4) - (kj >> 4) + WS - 1) * (2 * WS - 1) + ((qi & 15) - (kj & 15) + WS - 1);
+          packed[((size_t)hh * WT + kj) * WT + qi] = host_f32[(size_t)idx * L.cout + hh];
+        }
+  } else if (L.kind == RPB_OCA) {
+    // relative_position_index_OCA is ((ky - qy) - 7) * 39 + ((kx - qx) - 7), -880 .. 640, and indexes a 1521-row table: the
+    // negative values count from its end
+    const int side = WS + WSE - 1, rows = side * side, off = WS - WSE + 1;
+    packed.resize((size_t)L.cout * WKT * WT);
+    for (int hh = 0; hh < L.cout; ++hh)
+      for (int kj = 0; kj < WKT; ++kj)
+        for (int qi = 0; qi < WT; ++qi) {
+          int idx = ((kj / WSE) - (qi >> 4) + off) * side + ((kj % WSE) - (qi & 15) + off);
+          if (idx < 0) idx += rows;
+          packed[((size_t)hh * WKT + kj) * WT + qi] = host_f32[(size_t)idx * L.cout + hh];
+        }
+  } else if (L.kind == LNORM) {
+    packed.assign(host_f32, host_f32 + L.cout);
+  } else if (L.kind == GATE) {
+    packed.assign(host_f32, host_f32 + (j == 1 ? (size_t)L.cout : (size_t)L.cout * L.cin));
+  } else {
+    pack_gemm_tensor(L.kind == CONV, j == 1, L.cin, L.cout, host_f32, packed);
+  }
+  float*& dst = j == 0 ? s->w[layer] : s->b[layer];
+  // a running forward may still read the old values: loading is host-synchronous, as in the sibling families
+  HIPCHK(nullptr, hipDeviceSynchronize());
+  drop_graphs(s);
+  if (!dst) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&dst), packed.size() * sizeof(float)));
+  HIPCHK(nullptr, hipMemcpy(dst, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+  s->have[(size_t)layer * 2 + j] = 1;
+  return FDSR_OK;
+}
+
+int fdsr_hat_workspace_bytes(fdsr_hat s, int batch, int height, int width, size_t* bytes) {
+  if (!s || !bytes) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_workspace_bytes: null argument");
+  const int rc = check_shape("fdsr_hat_workspace_bytes", batch, height, width);
+  if (rc) return rc;
+  *bytes = make_plan(s, batch, height, width).bytes;
+  return FDSR_OK;
+}
+
+int fdsr_hat_forward(fdsr_hat s, const float* x_nchw, int batch, int height, int width, float* out_nchw, void* workspace, size_t workspace_bytes,
+                     void* hip_stream, int flags) {
+  if (!out_nchw || (flags & ~FDSR_HAT_GRAPH)) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_forward: bad arguments");
+  if ((flags & FDSR_HAT_GRAPH) && !hip_stream) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_forward: FDSR_HAT_GRAPH needs a created stream");
+  Walker wk{RUN};
+  int rc = prepare(s, "fdsr_hat_forward", x_nchw, batch, height, width, workspace, workspace_bytes, hip_stream, &wk);
+  if (rc) return rc;
+  wk.dst = out_nchw;
+  if (!(flags & FDSR_HAT_GRAPH)) {
+    wk.walk();
+    return wk.err;
+  }
+  // one graph per (B, H, W); other pointers under the same shape capture anew
+  Graph* g = nullptr;
+  for (Graph& q : s->graphs)
+    if (q.B == batch && q.H == height && q.W == width) g = &q;
+  if (g && !(g->x == x_nchw && g->out == out_nchw && g->ws == workspace)) {
+    (void)hipGraphExecDestroy(g->exec);
+    s->graphs.erase(s->graphs.begin() + (g - s->graphs.data()));
+    g = nullptr;
+  }
+  if (!g) {
+    hipGraphExec_t exec = nullptr;
+    if ((rc = capture_exec(nullptr, wk.st, [&]() -> int { wk.walk(); return wk.err; }, &exec))) return rc;
+    s->graphs.push_back(Graph{batch, height, width, x_nchw, out_nchw, workspace, exec});
+    g = &s->graphs.back();
+  }
+  HIPCHK(nullptr, hipGraphLaunch(g->exec, wk.st));
+  return FDSR_OK;
+}
+
+int fdsr_hat_debug_tensor(fdsr_hat s, const char* name, const float* x_nchw, int batch, int height, int width, float* out_nhwc,
+                          size_t capacity_floats, int* dims3, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  if (!name || !out_nhwc || !dims3) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_debug_tensor: null argument");
+  Walker wk{RUN};
+  const int rc = prepare(s, "fdsr_hat_debug_tensor", x_nchw, batch, height, width, workspace, workspace_bytes, hip_stream, &wk);
+  if (rc) return rc;
+  // the name is checked before anything runs: a walk that meets no tap would end in conv_last's store
+  const bool known = std::find(s->taps.begin(), s->taps.end(), std::string(name)) != s->taps.end();
+  if (!known) return fail(nullptr, FDSR_E_KEY, "fdsr_hat_debug_tensor: unknown tap '%s'", name);
+  wk.stop = name;
+  wk.walk();
+  if (wk.err) return wk.err;
+  if (!wk.done) return fail(nullptr, FDSR_E_KEY, "fdsr_hat_debug_tensor: tap '%s' was not reached", name);
+  const T& tp = wk.tapped;
+  const size_t count = (size_t)batch * tp.H * tp.W * tp.C;
+  if (count > capacity_floats) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_debug_tensor: '%s' needs %zu floats", name, count);
+  dims3[0] = tp.H; dims3[1] = tp.W; dims3[2] = tp.C;
+  HIPCHK(nullptr, hipMemcpyAsync(out_nhwc, wk.buf[tp.buf], count * sizeof(float), hipMemcpyDeviceToDevice, wk.st));
+  return FDSR_OK;
+}
+
+}  // extern "C"

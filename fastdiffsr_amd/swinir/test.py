@@ -52,7 +52,9 @@ def _batches(paths, imgs, n):
         i = j
 
 
-def run(model, classes, out_dir, scale, from_hr, batch=1, graph=False, max_images=None, log=print):
+def run(model, classes, out_dir, scale, from_hr, batch=1, graph=False, max_images=None, log=print, label='SwinIR '):
+    """The flow, for any model of this package that maps [B,3,h,w] in [0, 1] to [B,3,>=h*scale,>=w*scale] (fastdiffsr_amd.hat.test
+    runs it too): the result is cut to (h*scale, w*scale) -- HAT, like its reference, returns the padded size."""
     from PIL import Image
     device = next(model.parameters()).device
     left = max_images if max_images is not None else float('inf')
@@ -77,7 +79,7 @@ def run(model, classes, out_dir, scale, from_hr, batch=1, graph=False, max_image
             else:
                 lr_u8 = u8
             x = M.u8_to_tensor(lr_u8, min_max=(0, 1))                  # ToTensor()
-            sr_u8 = to_u8(model(x, graph=graph))
+            sr_u8 = to_u8(model(x, graph=graph)[:, :, :x.shape[2] * scale, :x.shape[3] * scale])
             if from_hr:
                 sums = [M.image_metric_sums(t, hr_u8).cpu().numpy() for t in (sr_u8, bic_u8)]
                 for i in range(len(part)):
@@ -88,17 +90,17 @@ def run(model, classes, out_dir, scale, from_hr, batch=1, graph=False, max_image
                 Image.fromarray(host[i]).save(os.path.join(out_dir, cls, os.path.splitext(os.path.basename(p))[0] + '.png'))
         log('[%s] %d images' % (cls or '.', len(paths)))
         if rows:
-            results[cls] = _report(rows, log)
+            results[cls] = _report(rows, log, label)
             rows_all += rows
     if rows_all:
         log('[all] %d images' % len(rows_all))
-        results['all'] = _report(rows_all, log)
+        results['all'] = _report(rows_all, log, label)
     return results
 
 
-def _report(rows, log):
+def _report(rows, log, label='SwinIR '):
     out = {}
-    for which, label in (('bic', 'Bicubic'), ('sr', 'SwinIR ')):
+    for which, label in (('bic', 'Bicubic'), ('sr', label)):
         out[which] = {k: float(np.mean([r[which][k] for r in rows])) for k in FIELDS}
         log('  %s MSE %.4f  PSNR %.4f  SSIM %.4f  ERGAS %.4f' % ((label,) + tuple(out[which][k] for k in FIELDS)))
     return out

@@ -143,6 +143,45 @@ def synth_swinir(cfg, seed: int = 0) -> "OrderedDict[str, np.ndarray]":
     return out
 
 
+def synth_hat(cfg, seed: int = 0) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights for HAT, keyed and ordered as hat.arch.param_schema(cfg) (one entry for the shared upsampling
+    convolution), every tensor from its own key, in the spirit of synth_swinir: the q and k rows of both qkv kinds are
+    N(0, 1.5 / C) (a logit spread of about 1.5 in the window attention and in the overlapping cross-attention), both bias tables
+    N(0, 1), LayerNorms 1 + 0.2 N / 0.1 N, proj damped (variance 0.1 / fan_in) and the RHAG convolutions N(0, 0.2 / fan_in) so
+    that the residual stream stays O(1) through every HAB and OCAB (below 40 at every tap of the full configuration).  fc1 and
+    fc2 are strong (4 / fan_in and 2.5 / fan_in: pre-activations of about 2, where the erf and tanh forms of GELU differ most,
+    so that the tanh form shows at the output by more than 100 times the fp32 noise).  The CAB is made to matter although
+    conv_scale is 0.01: its second convolution is N(0, 8 / fan_in) with a bias of 0.5 N, so the pooled channel means are not
+    all near zero, and the two 1x1 layers of the gate have gains 16 and 8, so the gate's logits spread over a few units (a
+    sigmoid that is dropped, or a pool over the wrong area, moves the gate visibly)."""
+    from .hat.arch import param_schema as hat_schema
+    c = cfg.embed_dim
+    out = OrderedDict()
+    for k, shape in hat_schema(cfg).items():
+        x = _rng('hat:' + k, seed).standard_normal(size=shape, dtype=np.float64)
+        fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else 1
+        norm = '.norm' in k or k.startswith('norm.')
+        if k.endswith('relative_position_bias_table'):
+            pass
+        elif norm and k.endswith('.weight'):
+            x = 1.0 + 0.2 * x
+        elif norm:
+            x *= 0.1
+        elif k.endswith('.bias'):
+            x *= 0.5 if '.cab.2.' in k else 0.1 if ('.qkv.' in k or '.attention.' in k) else 0.05
+        elif '.qkv.' in k:
+            x *= np.sqrt(np.r_[np.full(2 * c, 1.5), np.ones(c)] / fan_in)[:, None]
+        else:
+            if '.cab.' in k:
+                gain = {'0': 2.0, '2': 8.0, '1': 16.0, '3': 8.0}[k.split('.')[-2]]
+            else:
+                gain = {'proj': 0.1, 'fc1': 4.0, 'fc2': 2.5, 'conv': 0.2, 'conv_first': 4.0, 'conv_after_body': 1.0, '0': 2.0,
+                        'conv_last': 1.0}[k.split('.')[-2]]
+            x *= np.sqrt(gain / fan_in)
+        out[k] = x.astype(np.float32)
+    return out
+
+
 def synth_nafnet(seed: int = 0, width: int = 16, enc_blk_nums=(2, 1, 1, 1), middle_blk_num: int = 1, dec_blk_nums=(1, 1, 1, 1),
                  img_channel: int = 3) -> "OrderedDict[str, np.ndarray]":
     """Synthetic weights for EDiffSR's ConditionalNAFNet, keyed and ordered as ediffsr.arch.param_schema.  The reference

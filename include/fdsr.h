@@ -365,6 +365,61 @@ int fdsr_swinir_debug_tensor(fdsr_swinir s, const char* name, const float* x_nch
 int fdsr_swinir_to_u8(const float* src_nchw, uint8_t* dst_nhwc, int batch, int height, int width, void* hip_stream);
 void fdsr_swinir_destroy(fdsr_swinir s);
 
+/* -- HAT (MSI_SR_model/model/hat.py: GeneratorResNet) inference ------------------------------------------------------------
+ * An object of its own, in the shape of fdsr_swinir: upsampler 'pixelshuffle', resi_connection '1conv', patch_size 1, no
+ * absolute position embedding, three input channels, eval mode.  Exact fp32, NHWC inside, on the GEMM / LayerNorm kernels of
+ * the SwinIR family plus: attention over 16 x 16 windows (256 keys, shift 8 and the -100 region mask on odd blocks) and the
+ * overlapping cross-attention (256 queries against the 24 x 24 = 576 keys around the window, zero k and v outside the image),
+ * one workgroup per (image, window, head, 32 queries) with the full score rows in LDS; the CAB's two 3x3 convolutions, its
+ * channel-attention gate from fixed-order partial sums over the padded map, and conv_scale folded into proj's epilogue.
+ * Reruns are bitwise identical and an image's result depends neither on B nor on its position in the batch.
+ *   fdsr_hat_create           validates the configuration without touching the device.  FDSR_E_INVALID outside the envelope:
+ *                             window_size 16; overlap_win_size 24 (overlap_ratio 0.5); head_dim = embed_dim / num_heads[i] an
+ *                             integer <= 32; embed_dim <= 512, divisible by compress_ratio, embed_dim / squeeze_factor >= 1;
+ *                             1..FDSR_HAT_MAX_LAYERS layers of depth >= 1; upscale 2, 3, 4 or 8; img_range > 0.
+ *   fdsr_hat_load             a host fp32 tensor under the reference's state_dict name and shape.  The two
+ *                             relative_position_index_* buffers are functions of the geometry and are not taken.  The
+ *                             upsampler's one Conv2d is upsample.upsampling.0.*; the names .2.* and .4.* that the reference's
+ *                             state_dict repeats it under load the same tensor.  Any other name or shape: FDSR_E_KEY.
+ *                             Host-synchronous; drops every captured graph.
+ *   fdsr_hat_workspace_bytes  for a batch of height x width inputs.  FDSR_E_INVALID where the input cannot be reflect-padded to a
+ *                             multiple of 16 (F.pad's rule: the padding is smaller than the side).
+ *   fdsr_hat_forward          x_nchw [B][3][H][W] fp32 in [0, 1] -> out_nchw [B][3][Hp upscale][Wp upscale], Hp / Wp = H / W
+ *                             rounded up to a multiple of 16: the reference does not crop its output.  flags: FDSR_HAT_GRAPH
+ *                             replays the forward as one captured, linear hipGraph (hip_stream must be a created stream); one
+ *                             graph is kept per (B, H, W), captured anew when x, out or the workspace move.
+ *   fdsr_hat_debug_tensor     runs the forward up to a named tap and copies it out as NHWC [B][dims3[0]][dims3[1]][dims3[2]] at
+ *                             the padded size: SwinIR's taps plus layers.I.blocks.J.cab (the gated CAB output before
+ *                             conv_scale), layers.I.ocab.attn (after proj + shortcut) and layers.I.ocab.mlp.
+ * fdsr_swinir_to_u8 is save_img1 for this family too.  Errors as for fdsr_swinir. */
+#define FDSR_HAT_MAX_LAYERS 8
+#define FDSR_HAT_GRAPH 1
+typedef struct fdsr_hat_config {
+  int32_t embed_dim;
+  int32_t n_layers;                          /* len(depths) == len(num_heads), 1..FDSR_HAT_MAX_LAYERS */
+  int32_t depths[FDSR_HAT_MAX_LAYERS];
+  int32_t num_heads[FDSR_HAT_MAX_LAYERS];
+  int32_t window_size;
+  int32_t mlp_hidden;                        /* int(embed_dim * mlp_ratio), in the HABs and the OCAB */
+  int32_t upscale;
+  int32_t patch_norm;                        /* 0: no LayerNorm in patch_embed */
+  float img_range;
+  float mean[3];
+  int32_t compress_ratio;                    /* the CAB's hidden map has embed_dim / compress_ratio channels */
+  int32_t squeeze_factor;                    /* the gate's hidden layer has embed_dim / squeeze_factor channels */
+  float conv_scale;
+  int32_t overlap_win_size;                  /* int(window_size * overlap_ratio) + window_size */
+} fdsr_hat_config;
+typedef struct fdsr_hat_obj* fdsr_hat;
+int fdsr_hat_create(const fdsr_hat_config* cfg, fdsr_hat* out);
+int fdsr_hat_load(fdsr_hat s, const char* name, const float* host_f32, const int64_t* shape, int ndim);
+int fdsr_hat_workspace_bytes(fdsr_hat s, int batch, int height, int width, size_t* bytes);
+int fdsr_hat_forward(fdsr_hat s, const float* x_nchw, int batch, int height, int width, float* out_nchw, void* workspace,
+                     size_t workspace_bytes, void* hip_stream, int flags);
+int fdsr_hat_debug_tensor(fdsr_hat s, const char* name, const float* x_nchw, int batch, int height, int width, float* out_nhwc,
+                          size_t capacity_floats, int* dims3, void* workspace, size_t workspace_bytes, void* hip_stream);
+void fdsr_hat_destroy(fdsr_hat s);
+
 /* -- EDiffSR: ConditionalNAFNet noise predictor + IR-SDE reverse process (EDiffSR/codes: DenoisingNAFNet_arch.py,
  * module_util.py, utils/sde_utils.py) --------------------------------------------------------------------------------
  * An object of its own, independent of fdsr_handle.  fp32 activations (NHWC inside), every 1x1 / 2x2 / 3x3 convolution a GEMM
