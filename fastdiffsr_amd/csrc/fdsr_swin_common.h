@@ -1,4 +1,4 @@
-// What the window-transformer families (fdsr_swinir.hip, fdsr_hat.hip) share: the token GEMM with its 3x3 implicit-GEMM gather,
+// What the transformer families (fdsr_swinir.hip, fdsr_hat.hip, fdsr_transenet.hip) share: the token GEMM with its 3x3 implicit-GEMM gather,
 // LayerNorm over channels, the input kernel, the host packing of a Linear / Conv2d for the GEMM, and the small types of the
 // TABLE / SIZE / RUN walk.  Everything here sits in the anonymous namespace (internal linkage): each unit compiles the kernels
 // it launches.
@@ -24,12 +24,13 @@ constexpr int HD = 32;                // head_dim padded to the MFMA tile
 constexpr int NUM_FEAT = 64;          // channels of the reconstruction tail
 constexpr int LN_MAX_C = 512;         // swin_ln_kernel keeps a row in 8 registers per lane
 
-enum Gather { ROWS = 0, CONV3 = 1 };
+// PATCH8: row (b, ty, tx) is the 8 x 8 x Cin patch of an NHWC map, k = (p1 * 8 + p2) * Cin + c (fdsr_transenet.hip)
+enum Gather { ROWS = 0, CONV3 = 1, PATCH8 = 2 };
 // EPI_EXT and above: epilogues a translation unit adds by defining gemm_epilogue_ext for them
 enum Epi { EPI_NONE = 0, EPI_GELU = 1, EPI_LRELU = 2, EPI_RES = 3, EPI_SHUFFLE = 4, EPI_NCHW = 5, EPI_EXT = 6 };
 
 struct GemmArgs {
-  const float* x;      // ROWS: [M][K];  CONV3: NHWC [B][H][W][Cin]
+  const float* x;      // ROWS: [M][K];  CONV3, PATCH8: NHWC [B][H][W][Cin]
   const float* w;      // [Kpad][Npad];  CONV3: k = (ky * 3 + kx) * Cin + ci
   const float* bias;   // [Npad]
   const float* res;    // EPI_RES: [M][N], may be `out`
@@ -70,12 +71,25 @@ __global__ void __launch_bounds__(NT) swin_gemm_kernel(ARGS p) {
     oy = r / p.W;
     ox = r - oy * p.W;
   }
+  if constexpr (GATHER == PATCH8) {
+    if (mval) {
+      const int tw = p.W / 8, ntok = (p.H / 8) * tw;
+      n = gm / ntok;
+      const int r = gm - n * ntok;
+      oy = (r / tw) * 8;
+      ox = (r - (r / tw) * tw) * 8;
+    }
+  }
   const int bk = t >> 4, bn = (t & 15) * 4;
 
   // the address of element k of this thread's row, or null where it reads as zero
   auto src = [&](int k) -> const float* {
     if (!mval || k >= p.K) return nullptr;
     if (GATHER == ROWS) return p.x + (size_t)gm * p.K + k;
+    if constexpr (GATHER == PATCH8) {
+      const int pp = k / p.Cin, ci = k - pp * p.Cin;
+      return p.x + (((size_t)n * p.H + oy + (pp >> 3)) * p.W + ox + (pp & 7)) * p.Cin + ci;
+    }
     const int tap = k / p.Cin, ci = k - tap * p.Cin;
     const int ky = tap / 3, kx = tap - ky * 3;
     const int iy = oy + ky - 1, ix = ox + kx - 1;

@@ -182,6 +182,47 @@ def synth_hat(cfg, seed: int = 0) -> "OrderedDict[str, np.ndarray]":
     return out
 
 
+def synth_transenet(cfg, seed: int = 0) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights for TransENet, keyed and ordered as transenet.arch.state_schema(cfg), every tensor from its own key,
+    in the spirit of synth_hat.  The reference scales its logits by dim ** -0.5 = 512^-0.5 although a head has 32 dimensions:
+    q . k over 32 terms of variance s^2 each has a spread of sqrt(32) s^2, so the rows of to_qkv that make q and k, and to_q and
+    to_k, are N(0, 6 / 512) (s^2 = 6 on a LayerNorm's output): a logit spread of sqrt(32) 6 / sqrt(512) = 1.5 in every
+    attention, self and cross, at 8 keys and at 1024.  The v rows are N(0, 1 / 512).  LayerNorms are 1 + 0.2 N / 0.1 N.  to_out is
+    N(0, 0.5 / fan_in); net.0 and net.3 are N(0, 4 / fan_in) and N(0, 2 / fan_in) (pre-activations of about 2, where the erf and
+    tanh forms of GELU differ most).  sub_mean and add_mean are perturbed off what the reference initialises them to (the identity
+    and -/+ the mean): weight I + 0.15 N, bias -/+ mean + 0.05 N, so that a folded or skipped MeanShift shows.  The ResBlocks'
+    first convolution is N(0, 2 / fan_in), the second N(0, 0.5 / fan_in); the other convolutions and Linears N(0, g / fan_in), g
+    between 1 and 4; biases 0.05 N."""
+    from .transenet.arch import RGB_MEAN as TE_MEAN, INNER, state_schema as te_schema
+    out = OrderedDict()
+    for k, shape in te_schema(cfg).items():
+        x = _rng('transenet:' + k, seed).standard_normal(size=shape, dtype=np.float64)
+        fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else 1
+        mod = k.rsplit('.', 1)[0]
+        if mod in ('sub_mean', 'add_mean'):
+            sign = -1.0 if mod == 'sub_mean' else 1.0
+            x = (np.eye(3).reshape(3, 3, 1, 1) + 0.15 * x) if k.endswith('.weight') else (sign * np.asarray(TE_MEAN) + 0.05 * x)
+        elif mod.endswith('.norm'):
+            x = 1.0 + 0.2 * x if k.endswith('.weight') else 0.1 * x
+        elif k.endswith('.bias'):
+            x *= 0.05
+        elif mod.endswith('.to_qkv'):
+            x *= np.sqrt(np.r_[np.full(2 * INNER, 6.0), np.ones(INNER)] / fan_in)[:, None]
+        else:
+            parts = mod.split('.')
+            if mod.startswith('feat_extrat_stage'):
+                gain = 2.0 if parts[-1] == '0' else 0.5
+            elif mod.startswith('upsampler.'):
+                gain = 2.0
+            elif parts[-1] in ('to_q', 'to_k'):
+                gain = 6.0
+            else:
+                gain = {'to_out.0': 0.5, 'net.0': 4.0, 'net.3': 2.0, 'head.0': 4.0}.get('.'.join(parts[-2:]), 1.0)
+            x *= np.sqrt(gain / fan_in)
+        out[k] = x.astype(np.float32)
+    return out
+
+
 def synth_nafnet(seed: int = 0, width: int = 16, enc_blk_nums=(2, 1, 1, 1), middle_blk_num: int = 1, dec_blk_nums=(1, 1, 1, 1),
                  img_channel: int = 3) -> "OrderedDict[str, np.ndarray]":
     """Synthetic weights for EDiffSR's ConditionalNAFNet, keyed and ordered as ediffsr.arch.param_schema.  The reference

@@ -420,6 +420,50 @@ int fdsr_hat_debug_tensor(fdsr_hat s, const char* name, const float* x_nchw, int
                           size_t capacity_floats, int* dims3, void* workspace, size_t workspace_bytes, void* hip_stream);
 void fdsr_hat_destroy(fdsr_hat s);
 
+/* -- TransENet (MSI_SR_model/model/transenet.py: TransENet; model/transformer.py) inference ------------------------------------
+ * An object of its own, in the shape of fdsr_hat.  What the reference hard-codes is fixed here too: 8 x 8 patches, dim 512, 6
+ * heads of 32, mlp_dim 512, reduction 4 (channels = n_feats / 4), the tanh form of GELU, the logit scale 512^-0.5, no dropout.
+ * Exact fp32, NHWC inside, on the GEMM / LayerNorm kernels of the SwinIR family plus: dense attention over every token of the
+ * image (self-attention at (H / 8)(W / 8) and at scale^2 times as many tokens, cross-attention of the high tokens against the
+ * low ones), one workgroup per (image, head, 32 queries), k and v streamed in chunks of 128 keys whatever their number; the
+ * patch rearrange as a gather of the token GEMM and its inverse as embedding_to_patch's store; sub_mean and add_mean as general
+ * 3x3 matrices with bias.  Reruns are bitwise identical and an image's result depends neither on B nor on its position in the
+ * batch.
+ *   fdsr_transenet_create           validates the configuration without touching the device.  FDSR_E_INVALID outside the
+ *                                   envelope: n_colors 3; n_feats a multiple of 16, 16..256; scale 2, 3, 4 or 8; en_depth and
+ *                                   de_depth 1..FDSR_TRANSENET_MAX_DEPTH.
+ *   fdsr_transenet_load             a host fp32 tensor under the reference's state_dict name and shape (sub_mean.weight [3][3][1][1],
+ *                                   encoder_up.layers.3.0.fn.fn.to_qkv.weight [576][512], ...).  Any other name or shape:
+ *                                   FDSR_E_KEY.  Host-synchronous; drops every captured graph.
+ *   fdsr_transenet_workspace_bytes  for a batch of height x width inputs.  FDSR_E_INVALID unless both sides are multiples of 8.
+ *   fdsr_transenet_forward          x_nchw [B][3][H][W] fp32 -> out_nchw [B][3][H scale][W scale].  The geometry is the input's:
+ *                                   the reference's hr_patch_size binds the Python module, not the engine.  flags:
+ *                                   FDSR_TRANSENET_GRAPH replays the forward as one captured, linear hipGraph (hip_stream must be a
+ *                                   created stream); one graph is kept per (B, H, W), captured anew when x, out or the workspace move.
+ *   fdsr_transenet_debug_tensor     runs the forward up to a named tap and copies it out as NHWC [B][dims3[0]][dims3[1]][dims3[2]];
+ *                                   token tensors are [B][H / 8][W / 8][512] (times the scale for the high tokens).  Taps: head,
+ *                                   stageI, stageI.1x1, up, up.1x1, embed.lowI, embed.high, ENC.J.attn, ENC.J.ff, ENC (ENC =
+ *                                   encoder_stage1..3, encoder_up), decoderI.J.self / .cross / .ff, embedding_to_patch, span.
+ * fdsr_swinir_to_u8 is save_img1 for this family too.  Errors as for fdsr_swinir. */
+#define FDSR_TRANSENET_MAX_DEPTH 32
+#define FDSR_TRANSENET_GRAPH 1
+typedef struct fdsr_transenet_config {
+  int32_t n_feats;
+  int32_t scale;
+  int32_t n_colors;
+  int32_t en_depth;
+  int32_t de_depth;
+} fdsr_transenet_config;
+typedef struct fdsr_transenet_obj* fdsr_transenet;
+int fdsr_transenet_create(const fdsr_transenet_config* cfg, fdsr_transenet* out);
+int fdsr_transenet_load(fdsr_transenet s, const char* name, const float* host_f32, const int64_t* shape, int ndim);
+int fdsr_transenet_workspace_bytes(fdsr_transenet s, int batch, int height, int width, size_t* bytes);
+int fdsr_transenet_forward(fdsr_transenet s, const float* x_nchw, int batch, int height, int width, float* out_nchw, void* workspace,
+                           size_t workspace_bytes, void* hip_stream, int flags);
+int fdsr_transenet_debug_tensor(fdsr_transenet s, const char* name, const float* x_nchw, int batch, int height, int width, float* out_nhwc,
+                                size_t capacity_floats, int* dims3, void* workspace, size_t workspace_bytes, void* hip_stream);
+void fdsr_transenet_destroy(fdsr_transenet s);
+
 /* -- EDiffSR: ConditionalNAFNet noise predictor + IR-SDE reverse process (EDiffSR/codes: DenoisingNAFNet_arch.py,
  * module_util.py, utils/sde_utils.py) --------------------------------------------------------------------------------
  * An object of its own, independent of fdsr_handle.  fp32 activations (NHWC inside), every 1x1 / 2x2 / 3x3 convolution a GEMM
