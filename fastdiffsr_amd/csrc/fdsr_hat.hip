@@ -36,6 +36,7 @@
 
 #include "fdsr_engine_int.h"
 #include "fdsr_swin_common.h"
+#include "fdsr_swin_engine.h"
 
 using namespace fdsr_int;
 
@@ -46,7 +47,6 @@ constexpr int WSE = 24, WKT = WSE * WSE;   // the overlapping window (overlap_ra
 constexpr int QB = 32;                     // queries of one workgroup: a score row pitch of 32 keeps the two k rows of an MFMA operand read 32 banks apart
 constexpr int KC = 128;                    // keys per staged chunk
 constexpr int KP = KC + 32;                // pitch of the [d][key] chunk
-constexpr int NBUF = 10;
 
 enum HatEpi { EPI_COLSUM = EPI_EXT, EPI_HAB = EPI_EXT + 1 };
 
@@ -302,46 +302,73 @@ struct LayerDesc {
   }
 };
 
-struct Walker {
-  Mode mode;
-  fdsr_hat_config cfg{};
-  std::vector<LayerDesc>* table = nullptr;      // TABLE: appended to
-  std::vector<std::string>* taps = nullptr;     // TABLE: the tap names, appended to
-  size_t need[NBUF] = {};                       // SIZE: floats per image of each buffer
-  int N = 0, Hin = 0, Win = 0;
-  const float* img = nullptr;                   // RUN: the input, NCHW
-  float* dst = nullptr;                         // RUN: the output, NCHW (null: a debug walk, which ends at `stop`)
-  float* buf[NBUF] = {};
-  float* const* w = nullptr;
-  float* const* b = nullptr;
-  hipStream_t st = nullptr;
-  int li = 0;                                   // the next layer's index (load order)
-  int reuse = -1;                               // >= 0: the next gemm runs this layer again (the shared upsampling convolution)
-  const char* stop = nullptr;                   // RUN: the tap to end at
-  bool done = false;
-  T tapped{};
-  int err = FDSR_OK;
+struct Walker;
 
-  bool live() const { return mode == RUN && err == FDSR_OK && !done; }
-  bool stops_at(const std::string& name) const { return live() && stop && name == stop; }
-  void touch(const T& t) { need[t.buf] = std::max(need[t.buf], (size_t)t.H * t.W * t.C); }
-  void check(hipError_t e) {
-    if (e != hipSuccess && err == FDSR_OK) err = fail(nullptr, FDSR_E_HIP, "fdsr_hat: kernel launch failed: %s", hipGetErrorString(e));
+// what fdsr_swin_engine.h needs to know of this family
+struct Hat : FamilyDefaults {
+  using Config = fdsr_hat_config;
+  using Desc = LayerDesc;
+  using Walk = Walker;
+  using Obj = fdsr_hat_obj;
+  static constexpr const char *name = "fdsr_hat", *graph_flag_name = "FDSR_HAT_GRAPH";
+  static constexpr int NBUF = 10, SIDE = WS, graph_flag = FDSR_HAT_GRAPH;
+
+  // F.pad's rule for 'reflect': the padding must be smaller than the side it mirrors
+  static int check_shape(const char* fn, int B, int H, int W) {
+    if (B < 1 || H < 1 || W < 1) return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, B, H, W);
+    const int ph = round_up(H, WS) - H, pw = round_up(W, WS) - W;
+    if (ph >= H || pw >= W)
+      return fail(nullptr, FDSR_E_INVALID, "%s: a %dx%d image cannot be reflect-padded by (%d, %d) to a multiple of the window", fn, H, W, ph, pw);
+    return FDSR_OK;
   }
-  void tap(const std::string& name, const T& t) {
-    if (mode == TABLE) taps->push_back(name);
-    if (stops_at(name)) { done = true; tapped = t; }
+
+  // upsample.upsampling.{2,4}.* name the tensor of upsample.upsampling.0.* again (one Conv2d in every stage)
+  static std::string canonical_name(const fdsr_hat_config& cfg, const char* name) {
+    static const char prefix[] = "upsample.upsampling.";
+    std::string nm(name);
+    if (cfg.upscale == 3 || nm.compare(0, sizeof(prefix) - 1, prefix) != 0) return nm;
+    const size_t dot = nm.find('.', sizeof(prefix) - 1);
+    if (dot == std::string::npos) return nm;
+    const std::string idx = nm.substr(sizeof(prefix) - 1, dot - (sizeof(prefix) - 1));
+    for (int k = 1; (1 << k) < cfg.upscale; ++k)
+      if (idx == std::to_string(2 * k)) return prefix + std::string("0") + nm.substr(dot);
+    return nm;
   }
-  int layer(const std::string& name, Kind kind, int cin, int cout) {
-    if (reuse >= 0) {
-      const int idx = reuse;
-      reuse = -1;
-      return idx;
+
+  // device: LINEAR / CONV packed [Kpad][Npad] + bias [Npad]; LNORM gamma + beta; GATE as the checkpoint holds it; RPB_* biasT [heads][keys][256]
+  static void pack(const LayerDesc& L, int j, const float* host_f32, std::vector<float>& packed) {
+    if (L.kind == RPB_SA) {
+      // biasT[head][j][i] = table[(yi - yj + 15) * 31 + (xi - xj + 15)][head]: the gather of relative_position_index_SA, once
+      packed.resize((size_t)L.cout * WT * WT);
+      for (int hh = 0; hh < L.cout; ++hh)
+        for (int kj = 0; kj < WT; ++kj)
+          for (int qi = 0; qi < WT; ++qi) {
+            const int idx = ((qi >> 4) - (kj >> 4) + WS - 1) * (2 * WS - 1) + ((qi & 15) - (kj & 15) + WS - 1);
+            packed[((size_t)hh * WT + kj) * WT + qi] = host_f32[(size_t)idx * L.cout + hh];
+          }
+    } else if (L.kind == RPB_OCA) {
+      // relative_position_index_OCA is ((ky - qy) - 7) * 39 + ((kx - qx) - 7), -880 .. 640, and indexes a 1521-row table: the
+      // negative values count from its end
+      const int side = WS + WSE - 1, rows = side * side, off = WS - WSE + 1;
+      packed.resize((size_t)L.cout * WKT * WT);
+      for (int hh = 0; hh < L.cout; ++hh)
+        for (int kj = 0; kj < WKT; ++kj)
+          for (int qi = 0; qi < WT; ++qi) {
+            int idx = ((kj / WSE) - (qi >> 4) + off) * side + ((kj % WSE) - (qi & 15) + off);
+            if (idx < 0) idx += rows;
+            packed[((size_t)hh * WKT + kj) * WT + qi] = host_f32[(size_t)idx * L.cout + hh];
+          }
+    } else if (L.kind == LNORM) {
+      packed.assign(host_f32, host_f32 + L.cout);
+    } else if (L.kind == GATE) {
+      packed.assign(host_f32, host_f32 + (j == 1 ? (size_t)L.cout : (size_t)L.cout * L.cin));
+    } else {
+      pack_gemm_tensor(L.kind == CONV, j == 1, L.cin, L.cout, host_f32, packed);
     }
-    if (mode == TABLE) table->push_back(LayerDesc{name, kind, cin, cout});
-    return li++;
   }
+};
 
+struct Walker : WalkerBase<Hat> {
   template <int GATHER, int EPI>
   void launch_gemm(const HatGemmArgs& a, bool vec) {
     if constexpr (EPI >= EPI_EXT) check(launch_swin_gemm<GATHER, EPI>(a, vec, st));
@@ -357,20 +384,8 @@ struct Walker {
     if (mode == SIZE && epi != EPI_NCHW) touch(out);
     if (!live()) return out;
     HatGemmArgs a{};
-    a.x = buf[in.buf];
-    a.w = w[idx];
-    a.bias = b[idx];
-    a.res = res ? buf[res->buf] : nullptr;
+    gemm_args(a, idx, in, res, kind == CONV, in.C, cout, r);
     a.out = epi == EPI_NCHW ? dst : buf[ob];
-    a.M = N * in.H * in.W;
-    a.N = cout;
-    a.K = kind == CONV ? 9 * in.C : in.C;
-    a.Kpad = gemm_kpad(kind == CONV, in.C);
-    a.Npad = gemm_npad(cout);
-    a.H = in.H;
-    a.W = in.W;
-    a.Cin = in.C;
-    a.r = r;
     a.Hc = in.H;          // no crop: the reference returns the padded size
     a.Wc = in.W;
     a.slope = 0.01f;      // nn.LeakyReLU()'s default
@@ -398,16 +413,8 @@ struct Walker {
     return out;
   }
 
-  T norm(const std::string& name, const T& in, int ob) {
-    const int idx = layer(name, LNORM, in.C, in.C);
-    T out{ob, in.H, in.W, in.C};
-    if (mode == SIZE) touch(out);
-    if (!live()) return out;
-    const int M = N * in.H * in.W;
-    hipLaunchKernelGGL(swin_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, buf[in.buf], w[idx], b[idx], buf[ob], M, in.C);
-    check(hipGetLastError());
-    return out;
-  }
+  using WalkerBase::norm;
+  T norm(const std::string& name, const T& in, int ob) { return norm(layer(name, LNORM, in.C, in.C), in, ob); }
 
   // attention over the q | k | v rows of `qkv`, into `ob`
   T attention(const std::string& name, bool oca, const T& qkv, int heads, int shift, int ob) {
@@ -529,96 +536,9 @@ struct Walker {
   }
 };
 
-struct Plan { size_t off[NBUF]; size_t bytes; };
-
-struct Graph { int B, H, W; const void *x, *out, *ws; hipGraphExec_t exec; };
-
 }  // namespace
 
-struct fdsr_hat_obj {
-  fdsr_hat_config cfg{};
-  std::vector<LayerDesc> table;
-  std::vector<std::string> taps;
-  std::vector<unsigned char> have;   // [layer * 2 + j]
-  // device: LINEAR / CONV packed [Kpad][Npad] + bias [Npad]; LNORM gamma + beta; GATE as the checkpoint holds it; RPB_* biasT [heads][keys][256]
-  std::vector<float*> w, b;
-  std::vector<Graph> graphs;
-};
-
-namespace {
-
-Walker walker(fdsr_hat s, Mode mode, int B, int H, int W) {
-  Walker wk{mode};
-  wk.cfg = s->cfg;
-  wk.N = B;
-  wk.Hin = H;
-  wk.Win = W;
-  return wk;
-}
-
-Plan make_plan(fdsr_hat s, int B, int H, int W) {
-  Walker wk = walker(s, SIZE, B, H, W);
-  wk.walk();
-  Plan pl{};
-  size_t off = 0;
-  for (int i = 0; i < NBUF; ++i) {
-    pl.off[i] = off;
-    off = align_up(off + (size_t)B * wk.need[i] * sizeof(float), 256);
-  }
-  pl.bytes = off;
-  return pl;
-}
-
-void drop_graphs(fdsr_hat s) {
-  for (Graph& g : s->graphs)
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  s->graphs.clear();
-}
-
-// F.pad's rule for 'reflect': the padding must be smaller than the side it mirrors
-int check_shape(const char* fn, int B, int H, int W) {
-  if (B < 1 || H < 1 || W < 1) return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, B, H, W);
-  const int ph = round_up(H, WS) - H, pw = round_up(W, WS) - W;
-  if (ph >= H || pw >= W)
-    return fail(nullptr, FDSR_E_INVALID, "%s: a %dx%d image cannot be reflect-padded by (%d, %d) to a multiple of the window", fn, H, W, ph, pw);
-  return FDSR_OK;
-}
-
-// everything a forward or a debug walk checks, then the walker ready to run
-int prepare(fdsr_hat s, const char* fn, const float* x, int B, int H, int W, void* ws, size_t ws_bytes, void* stream, Walker* out) {
-  if (!s || !x || !ws) return fail(nullptr, FDSR_E_INVALID, "%s: null argument", fn);
-  int rc = check_shape(fn, B, H, W);
-  if (rc) return rc;
-  for (size_t L = 0; L < s->table.size(); ++L)
-    for (int j = 0; j < s->table[L].tensors(); ++j)
-      if (!s->have[L * 2 + j]) return fail(nullptr, FDSR_E_STATE, "%s: tensor '%s' is missing", fn, s->table[L].tensor_name(j).c_str());
-  const Plan pl = make_plan(s, B, H, W);
-  if (ws_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(ws) & 255))
-    return fail(nullptr, FDSR_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes) or not 256-byte aligned", fn, ws_bytes, pl.bytes);
-  Walker wk = walker(s, RUN, B, H, W);
-  wk.img = x;
-  for (int i = 0; i < NBUF; ++i) wk.buf[i] = reinterpret_cast<float*>(static_cast<char*>(ws) + pl.off[i]);
-  wk.w = s->w.data();
-  wk.b = s->b.data();
-  wk.st = reinterpret_cast<hipStream_t>(stream);
-  *out = wk;
-  return FDSR_OK;
-}
-
-// upsample.upsampling.{2,4}.* name the tensor of upsample.upsampling.0.* again (one Conv2d in every stage)
-std::string canonical_name(fdsr_hat s, const char* name) {
-  static const char prefix[] = "upsample.upsampling.";
-  std::string nm(name);
-  if (s->cfg.upscale == 3 || nm.compare(0, sizeof(prefix) - 1, prefix) != 0) return nm;
-  const size_t dot = nm.find('.', sizeof(prefix) - 1);
-  if (dot == std::string::npos) return nm;
-  const std::string idx = nm.substr(sizeof(prefix) - 1, dot - (sizeof(prefix) - 1));
-  for (int k = 1; (1 << k) < s->cfg.upscale; ++k)
-    if (idx == std::to_string(2 * k)) return prefix + std::string("0") + nm.substr(dot);
-  return nm;
-}
-
-}  // namespace
+struct fdsr_hat_obj : Engine<Hat> {};
 
 extern "C" {
 
@@ -647,139 +567,28 @@ int fdsr_hat_create(const fdsr_hat_config* cfg, fdsr_hat* out) {
   if (c.upscale != 2 && c.upscale != 3 && c.upscale != 4 && c.upscale != 8)
     return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: upscale %d is not supported (2, 3, 4, 8)", c.upscale);
   if (!(c.img_range > 0.f)) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: img_range must be positive");
-  fdsr_hat s = new (std::nothrow) fdsr_hat_obj();
-  if (!s) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: out of host memory");
-  s->cfg = c;
-  Walker wk = walker(s, TABLE, 1, WS, WS);
-  wk.table = &s->table;
-  wk.taps = &s->taps;
-  wk.walk();
-  s->have.assign(s->table.size() * 2, 0);
-  s->w.assign(s->table.size(), nullptr);
-  s->b.assign(s->table.size(), nullptr);
-  *out = s;
-  return FDSR_OK;
+  return engine_create<Hat>("fdsr_hat_create", c, out);
 }
 
-void fdsr_hat_destroy(fdsr_hat s) {
-  if (!s) return;
-  drop_graphs(s);
-  for (float* p : s->w)
-    if (p) (void)hipFree(p);
-  for (float* p : s->b)
-    if (p) (void)hipFree(p);
-  delete s;
-}
+void fdsr_hat_destroy(fdsr_hat s) { engine_destroy<Hat>(s); }
 
 int fdsr_hat_load(fdsr_hat s, const char* name, const float* host_f32, const int64_t* shape, int ndim) {
-  if (!s || !name || !host_f32 || (ndim > 0 && !shape) || ndim < 0) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_load: bad arguments");
-  const std::string nm = canonical_name(s, name);
-  int layer = -1, j = -1;
-  for (size_t L = 0; L < s->table.size() && layer < 0; ++L)
-    for (int q = 0; q < s->table[L].tensors(); ++q)
-      if (s->table[L].tensor_name(q) == nm) { layer = (int)L; j = q; break; }
-  if (layer < 0) return fail(nullptr, FDSR_E_KEY, "fdsr_hat_load: unknown tensor '%s'", name);
-  const LayerDesc& L = s->table[layer];
-  const std::vector<int64_t> want = L.shape(j);
-  if (ndim != (int)want.size() || !std::equal(want.begin(), want.end(), shape))
-    return fail(nullptr, FDSR_E_KEY, "fdsr_hat_load: '%s' has the wrong shape", name);
-  std::vector<float> packed;
-  if (L.kind == RPB_SA) {
-    // biasT[head][j][i] = table[(yi - yj + 15) * 31 + (xi - xj + 15)][head]: the gather of relative_position_index_SA, once
-    packed.resize((size_t)L.cout * WT * WT);
-    for (int hh = 0; hh < L.cout; ++hh)
-      for (int kj = 0; kj < WT; ++kj)
-        for (int qi = 0; qi < WT; ++qi) {
-          const int idx = ((qi >> 4) - (kj >> 4) + WS - 1) * (2 * WS - 1) + ((qi & 15) - (kj & 15) + WS - 1);
-          packed[((size_t)hh * WT + kj) * WT + qi] = host_f32[(size_t)idx * L.cout + hh];
-        }
-  } else if (L.kind == RPB_OCA) {
-    // relative_position_index_OCA is ((ky - qy) - 7) * 39 + ((kx - qx) - 7), -880 .. 640, and indexes a 1521-row table: the
-    // negative values count from its end
-    const int side = WS + WSE - 1, rows = side * side, off = WS - WSE + 1;
-    packed.resize((size_t)L.cout * WKT * WT);
-    for (int hh = 0; hh < L.cout; ++hh)
-      for (int kj = 0; kj < WKT; ++kj)
-        for (int qi = 0; qi < WT; ++qi) {
-          int idx = ((kj / WSE) - (qi >> 4) + off) * side + ((kj % WSE) - (qi & 15) + off);
-          if (idx < 0) idx += rows;
-          packed[((size_t)hh * WKT + kj) * WT + qi] = host_f32[(size_t)idx * L.cout + hh];
-        }
-  } else if (L.kind == LNORM) {
-    packed.assign(host_f32, host_f32 + L.cout);
-  } else if (L.kind == GATE) {
-    packed.assign(host_f32, host_f32 + (j == 1 ? (size_t)L.cout : (size_t)L.cout * L.cin));
-  } else {
-    pack_gemm_tensor(L.kind == CONV, j == 1, L.cin, L.cout, host_f32, packed);
-  }
-  float*& dst = j == 0 ? s->w[layer] : s->b[layer];
-  // a running forward may still read the old values: loading is host-synchronous, as in the sibling families
-  HIPCHK(nullptr, hipDeviceSynchronize());
-  drop_graphs(s);
-  if (!dst) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&dst), packed.size() * sizeof(float)));
-  HIPCHK(nullptr, hipMemcpy(dst, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-  s->have[(size_t)layer * 2 + j] = 1;
-  return FDSR_OK;
+  return engine_load<Hat>("fdsr_hat_load", s, name, host_f32, shape, ndim);
 }
 
 int fdsr_hat_workspace_bytes(fdsr_hat s, int batch, int height, int width, size_t* bytes) {
-  if (!s || !bytes) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_workspace_bytes: null argument");
-  const int rc = check_shape("fdsr_hat_workspace_bytes", batch, height, width);
-  if (rc) return rc;
-  *bytes = make_plan(s, batch, height, width).bytes;
-  return FDSR_OK;
+  return engine_workspace_bytes<Hat>("fdsr_hat_workspace_bytes", s, batch, height, width, bytes);
 }
 
 int fdsr_hat_forward(fdsr_hat s, const float* x_nchw, int batch, int height, int width, float* out_nchw, void* workspace, size_t workspace_bytes,
                      void* hip_stream, int flags) {
-  if (!out_nchw || (flags & ~FDSR_HAT_GRAPH)) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_forward: bad arguments");
-  if ((flags & FDSR_HAT_GRAPH) && !hip_stream) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_forward: FDSR_HAT_GRAPH needs a created stream");
-  Walker wk{RUN};
-  int rc = prepare(s, "fdsr_hat_forward", x_nchw, batch, height, width, workspace, workspace_bytes, hip_stream, &wk);
-  if (rc) return rc;
-  wk.dst = out_nchw;
-  if (!(flags & FDSR_HAT_GRAPH)) {
-    wk.walk();
-    return wk.err;
-  }
-  // one graph per (B, H, W); other pointers under the same shape capture anew
-  Graph* g = nullptr;
-  for (Graph& q : s->graphs)
-    if (q.B == batch && q.H == height && q.W == width) g = &q;
-  if (g && !(g->x == x_nchw && g->out == out_nchw && g->ws == workspace)) {
-    (void)hipGraphExecDestroy(g->exec);
-    s->graphs.erase(s->graphs.begin() + (g - s->graphs.data()));
-    g = nullptr;
-  }
-  if (!g) {
-    hipGraphExec_t exec = nullptr;
-    if ((rc = capture_exec(nullptr, wk.st, [&]() -> int { wk.walk(); return wk.err; }, &exec))) return rc;
-    s->graphs.push_back(Graph{batch, height, width, x_nchw, out_nchw, workspace, exec});
-    g = &s->graphs.back();
-  }
-  HIPCHK(nullptr, hipGraphLaunch(g->exec, wk.st));
-  return FDSR_OK;
+  return engine_forward<Hat>("fdsr_hat_forward", s, x_nchw, batch, height, width, out_nchw, workspace, workspace_bytes, hip_stream, flags);
 }
 
 int fdsr_hat_debug_tensor(fdsr_hat s, const char* name, const float* x_nchw, int batch, int height, int width, float* out_nhwc,
                           size_t capacity_floats, int* dims3, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (!name || !out_nhwc || !dims3) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_debug_tensor: null argument");
-  Walker wk{RUN};
-  const int rc = prepare(s, "fdsr_hat_debug_tensor", x_nchw, batch, height, width, workspace, workspace_bytes, hip_stream, &wk);
-  if (rc) return rc;
-  // the name is checked before anything runs: a walk that meets no tap would end in conv_last's store
-  const bool known = std::find(s->taps.begin(), s->taps.end(), std::string(name)) != s->taps.end();
-  if (!known) return fail(nullptr, FDSR_E_KEY, "fdsr_hat_debug_tensor: unknown tap '%s'", name);
-  wk.stop = name;
-  wk.walk();
-  if (wk.err) return wk.err;
-  if (!wk.done) return fail(nullptr, FDSR_E_KEY, "fdsr_hat_debug_tensor: tap '%s' was not reached", name);
-  const T& tp = wk.tapped;
-  const size_t count = (size_t)batch * tp.H * tp.W * tp.C;
-  if (count > capacity_floats) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_debug_tensor: '%s' needs %zu floats", name, count);
-  dims3[0] = tp.H; dims3[1] = tp.W; dims3[2] = tp.C;
-  HIPCHK(nullptr, hipMemcpyAsync(out_nhwc, wk.buf[tp.buf], count * sizeof(float), hipMemcpyDeviceToDevice, wk.st));
-  return FDSR_OK;
+  return engine_debug_tensor<Hat>("fdsr_hat_debug_tensor", s, name, x_nchw, batch, height, width, out_nhwc, capacity_floats, dims3, workspace,
+                                  workspace_bytes, hip_stream);
 }
 
 }  // extern "C"

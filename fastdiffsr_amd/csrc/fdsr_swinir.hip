@@ -34,7 +34,8 @@
 #include <vector>
 
 #include "fdsr_engine_int.h"
-#include "fdsr_swin_common.h"   // swin_gemm_kernel, swin_ln_kernel, swin_input_kernel, the weight packing: shared with fdsr_hat.hip
+#include "fdsr_swin_common.h"   // swin_gemm_kernel, swin_ln_kernel, swin_input_kernel, the weight packing
+#include "fdsr_swin_engine.h"   // the walk's bookkeeping, the engine object and the frames of the C functions
 
 using namespace fdsr_int;
 
@@ -42,7 +43,6 @@ namespace {
 
 constexpr int WS = 8, WT = WS * WS;   // the window and its tokens
 constexpr int TP = WT + 32;           // pitch of the [k][token] operand arrays of the attention kernel
-constexpr int NBUF = 6;
 
 // (Shifted-)window attention of one (image, window): a loop over the heads.  Token (ty, tx) of window (wy, wx) is the pixel
 // ((wy 8 + ty + shift) mod H, (wx 8 + tx + shift) mod W) -- torch.roll by -shift, then window_partition -- and the output goes
@@ -175,9 +175,6 @@ struct LayerDesc {
   std::string name;
   Kind kind;
   int cin, cout;   // LNORM: cout = C;  RPB: cout = heads
-  int K() const { return kind == CONV ? 9 * cin : cin; }
-  int Kpad() const { return round_up(K(), BK); }
-  int Npad() const { return round_up(cout, BN); }
   int tensors() const { return kind == RPB ? 1 : 2; }
   std::string tensor_name(int j) const { return kind == RPB ? name : name + (j == 0 ? ".weight" : ".bias"); }
   std::vector<int64_t> shape(int j) const {
@@ -188,39 +185,46 @@ struct LayerDesc {
   }
 };
 
-struct Walker {
-  Mode mode;
-  fdsr_swinir_config cfg{};
-  std::vector<LayerDesc>* table = nullptr;      // TABLE: appended to
-  std::vector<std::string>* taps = nullptr;     // TABLE: the tap names, appended to
-  size_t need[NBUF] = {};                       // SIZE: floats per image of each buffer
-  int N = 0, Hin = 0, Win = 0;
-  const float* img = nullptr;                   // RUN: the input, NCHW
-  float* dst = nullptr;                         // RUN: the output, NCHW (null: a debug walk, which ends at `stop`)
-  float* buf[NBUF] = {};
-  float* const* w = nullptr;
-  float* const* b = nullptr;
-  hipStream_t st = nullptr;
-  int li = 0;                                   // the next layer's index (load order)
-  const char* stop = nullptr;                   // RUN: the tap to end at
-  bool done = false;
-  T tapped{};
-  int err = FDSR_OK;
+struct Walker;
 
-  bool live() const { return mode == RUN && err == FDSR_OK && !done; }
-  void touch(const T& t) { need[t.buf] = std::max(need[t.buf], (size_t)t.H * t.W * t.C); }
-  void check(hipError_t e) {
-    if (e != hipSuccess && err == FDSR_OK) err = fail(nullptr, FDSR_E_HIP, "fdsr_swinir: kernel launch failed: %s", hipGetErrorString(e));
-  }
-  void tap(const std::string& name, const T& t) {
-    if (mode == TABLE) taps->push_back(name);
-    if (live() && stop && name == stop) { done = true; tapped = t; }
-  }
-  int layer(const std::string& name, Kind kind, int cin, int cout) {
-    if (mode == TABLE) table->push_back(LayerDesc{name, kind, cin, cout});
-    return li++;
+// what fdsr_swin_engine.h needs to know of this family
+struct Swinir : FamilyDefaults {
+  using Config = fdsr_swinir_config;
+  using Desc = LayerDesc;
+  using Walk = Walker;
+  using Obj = fdsr_swinir_obj;
+  static constexpr const char *name = "fdsr_swinir", *graph_flag_name = "FDSR_SWINIR_GRAPH";
+  static constexpr int NBUF = 6, SIDE = WS, graph_flag = FDSR_SWINIR_GRAPH;
+
+  // F.pad's rule for 'reflect': the padding must be smaller than the side it mirrors
+  static int check_shape(const char* fn, int B, int H, int W) {
+    if (B < 1 || H < 1 || W < 1) return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, B, H, W);
+    const int ph = round_up(H, WS) - H, pw = round_up(W, WS) - W;
+    if (ph >= H || pw >= W)
+      return fail(nullptr, FDSR_E_INVALID, "%s: a %dx%d image cannot be reflect-padded by (%d, %d) to a multiple of the window", fn, H, W, ph, pw);
+    return FDSR_OK;
   }
 
+  // device: LINEAR / CONV packed [Kpad][Npad] + bias [Npad]; LNORM gamma + beta; RPB biasT [heads][64][64]
+  static void pack(const LayerDesc& L, int j, const float* host_f32, std::vector<float>& packed) {
+    if (L.kind == RPB) {
+      // biasT[head][j][i] = table[(yi - yj + 7) * 15 + (xi - xj + 7)][head]: the gather of relative_position_index, once
+      packed.resize((size_t)L.cout * WT * WT);
+      for (int hh = 0; hh < L.cout; ++hh)
+        for (int kj = 0; kj < WT; ++kj)
+          for (int qi = 0; qi < WT; ++qi) {
+            const int idx = ((qi >> 3) - (kj >> 3) + WS - 1) * (2 * WS - 1) + ((qi & 7) - (kj & 7) + WS - 1);
+            packed[((size_t)hh * WT + kj) * WT + qi] = host_f32[(size_t)idx * L.cout + hh];
+          }
+    } else if (L.kind == LNORM) {
+      packed.assign(host_f32, host_f32 + L.cout);
+    } else {
+      pack_gemm_tensor(L.kind == CONV, j == 1, L.cin, L.cout, host_f32, packed);
+    }
+  }
+};
+
+struct Walker : WalkerBase<Swinir> {
   template <int GATHER, int EPI>
   void launch_gemm(const GemmArgs& a, bool vec) {
     check(launch_swin_gemm<GATHER, EPI>(a, vec, st));
@@ -232,22 +236,9 @@ struct Walker {
     T out{ob, in.H * r, in.W * r, cout / (r * r)};
     if (mode == SIZE && epi != EPI_NCHW) touch(out);
     if (!live()) return out;
-    const LayerDesc L{name, kind, in.C, cout};
     GemmArgs a{};
-    a.x = buf[in.buf];
-    a.w = w[idx];
-    a.bias = b[idx];
-    a.res = res ? buf[res->buf] : nullptr;
+    gemm_args(a, idx, in, res, kind == CONV, in.C, cout, r);
     a.out = epi == EPI_NCHW ? dst : buf[ob];
-    a.M = N * in.H * in.W;
-    a.N = cout;
-    a.K = L.K();
-    a.Kpad = L.Kpad();
-    a.Npad = L.Npad();
-    a.H = in.H;
-    a.W = in.W;
-    a.Cin = in.C;
-    a.r = r;
     a.Hc = Hin * cfg.upscale;
     a.Wc = Win * cfg.upscale;
     a.slope = 0.01f;   // nn.LeakyReLU()'s default
@@ -268,16 +259,8 @@ struct Walker {
     return out;
   }
 
-  T norm(const std::string& name, const T& in, int ob) {
-    const int idx = layer(name, LNORM, in.C, in.C);
-    T out{ob, in.H, in.W, in.C};
-    if (mode == SIZE) touch(out);
-    if (!live()) return out;
-    const int M = N * in.H * in.W;
-    hipLaunchKernelGGL(swin_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, buf[in.buf], w[idx], b[idx], buf[ob], M, in.C);
-    check(hipGetLastError());
-    return out;
-  }
+  using WalkerBase::norm;
+  T norm(const std::string& name, const T& in, int ob) { return norm(layer(name, LNORM, in.C, in.C), in, ob); }
 
   // attention over the q | k | v rows of `qkv`, into `ob`
   T attention(const std::string& name, const T& qkv, int heads, int shift, int ob) {
@@ -354,82 +337,9 @@ struct Walker {
   }
 };
 
-struct Plan { size_t off[NBUF]; size_t bytes; };
-
-struct Graph { int B, H, W; const void *x, *out, *ws; hipGraphExec_t exec; };
-
 }  // namespace
 
-struct fdsr_swinir_obj {
-  fdsr_swinir_config cfg{};
-  std::vector<LayerDesc> table;
-  std::vector<std::string> taps;
-  std::vector<unsigned char> have;   // [layer * 2 + j]
-  std::vector<float*> w, b;          // device: LINEAR / CONV packed [Kpad][Npad] + bias [Npad]; LNORM gamma + beta; RPB biasT [heads][64][64]
-  std::vector<Graph> graphs;
-};
-
-namespace {
-
-Walker walker(fdsr_swinir s, Mode mode, int B, int H, int W) {
-  Walker wk{mode};
-  wk.cfg = s->cfg;
-  wk.N = B;
-  wk.Hin = H;
-  wk.Win = W;
-  return wk;
-}
-
-Plan make_plan(fdsr_swinir s, int B, int H, int W) {
-  Walker wk = walker(s, SIZE, B, H, W);
-  wk.walk();
-  Plan pl{};
-  size_t off = 0;
-  for (int i = 0; i < NBUF; ++i) {
-    pl.off[i] = off;
-    off = align_up(off + (size_t)B * wk.need[i] * sizeof(float), 256);
-  }
-  pl.bytes = off;
-  return pl;
-}
-
-void drop_graphs(fdsr_swinir s) {
-  for (Graph& g : s->graphs)
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  s->graphs.clear();
-}
-
-// F.pad's rule for 'reflect': the padding must be smaller than the side it mirrors
-int check_shape(const char* fn, int B, int H, int W) {
-  if (B < 1 || H < 1 || W < 1) return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, B, H, W);
-  const int ph = round_up(H, WS) - H, pw = round_up(W, WS) - W;
-  if (ph >= H || pw >= W)
-    return fail(nullptr, FDSR_E_INVALID, "%s: a %dx%d image cannot be reflect-padded by (%d, %d) to a multiple of the window", fn, H, W, ph, pw);
-  return FDSR_OK;
-}
-
-// everything a forward or a debug walk checks, then the walker ready to run
-int prepare(fdsr_swinir s, const char* fn, const float* x, int B, int H, int W, void* ws, size_t ws_bytes, void* stream, Walker* out) {
-  if (!s || !x || !ws) return fail(nullptr, FDSR_E_INVALID, "%s: null argument", fn);
-  int rc = check_shape(fn, B, H, W);
-  if (rc) return rc;
-  for (size_t L = 0; L < s->table.size(); ++L)
-    for (int j = 0; j < s->table[L].tensors(); ++j)
-      if (!s->have[L * 2 + j]) return fail(nullptr, FDSR_E_STATE, "%s: tensor '%s' is missing", fn, s->table[L].tensor_name(j).c_str());
-  const Plan pl = make_plan(s, B, H, W);
-  if (ws_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(ws) & 255))
-    return fail(nullptr, FDSR_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes) or not 256-byte aligned", fn, ws_bytes, pl.bytes);
-  Walker wk = walker(s, RUN, B, H, W);
-  wk.img = x;
-  for (int i = 0; i < NBUF; ++i) wk.buf[i] = reinterpret_cast<float*>(static_cast<char*>(ws) + pl.off[i]);
-  wk.w = s->w.data();
-  wk.b = s->b.data();
-  wk.st = reinterpret_cast<hipStream_t>(stream);
-  *out = wk;
-  return FDSR_OK;
-}
-
-}  // namespace
+struct fdsr_swinir_obj : Engine<Swinir> {};
 
 extern "C" {
 
@@ -452,125 +362,28 @@ int fdsr_swinir_create(const fdsr_swinir_config* cfg, fdsr_swinir* out) {
   if (c.upscale != 2 && c.upscale != 3 && c.upscale != 4 && c.upscale != 8)
     return fail(nullptr, FDSR_E_INVALID, "fdsr_swinir_create: upscale %d is not supported (2, 3, 4, 8)", c.upscale);
   if (!(c.img_range > 0.f)) return fail(nullptr, FDSR_E_INVALID, "fdsr_swinir_create: img_range must be positive");
-  fdsr_swinir s = new (std::nothrow) fdsr_swinir_obj();
-  if (!s) return fail(nullptr, FDSR_E_INVALID, "fdsr_swinir_create: out of host memory");
-  s->cfg = c;
-  Walker wk = walker(s, TABLE, 1, WS, WS);
-  wk.table = &s->table;
-  wk.taps = &s->taps;
-  wk.walk();
-  s->have.assign(s->table.size() * 2, 0);
-  s->w.assign(s->table.size(), nullptr);
-  s->b.assign(s->table.size(), nullptr);
-  *out = s;
-  return FDSR_OK;
+  return engine_create<Swinir>("fdsr_swinir_create", c, out);
 }
 
-void fdsr_swinir_destroy(fdsr_swinir s) {
-  if (!s) return;
-  drop_graphs(s);
-  for (float* p : s->w)
-    if (p) (void)hipFree(p);
-  for (float* p : s->b)
-    if (p) (void)hipFree(p);
-  delete s;
-}
+void fdsr_swinir_destroy(fdsr_swinir s) { engine_destroy<Swinir>(s); }
 
 int fdsr_swinir_load(fdsr_swinir s, const char* name, const float* host_f32, const int64_t* shape, int ndim) {
-  if (!s || !name || !host_f32 || (ndim > 0 && !shape) || ndim < 0) return fail(nullptr, FDSR_E_INVALID, "fdsr_swinir_load: bad arguments");
-  int layer = -1, j = -1;
-  for (size_t L = 0; L < s->table.size() && layer < 0; ++L)
-    for (int q = 0; q < s->table[L].tensors(); ++q)
-      if (s->table[L].tensor_name(q) == name) { layer = (int)L; j = q; break; }
-  if (layer < 0) return fail(nullptr, FDSR_E_KEY, "fdsr_swinir_load: unknown tensor '%s'", name);
-  const LayerDesc& L = s->table[layer];
-  const std::vector<int64_t> want = L.shape(j);
-  if (ndim != (int)want.size() || !std::equal(want.begin(), want.end(), shape))
-    return fail(nullptr, FDSR_E_KEY, "fdsr_swinir_load: '%s' has the wrong shape", name);
-  std::vector<float> packed;
-  if (L.kind == RPB) {
-    // biasT[head][j][i] = table[(yi - yj + 7) * 15 + (xi - xj + 7)][head]: the gather of relative_position_index, once
-    packed.resize((size_t)L.cout * WT * WT);
-    for (int hh = 0; hh < L.cout; ++hh)
-      for (int kj = 0; kj < WT; ++kj)
-        for (int qi = 0; qi < WT; ++qi) {
-          const int idx = ((qi >> 3) - (kj >> 3) + WS - 1) * (2 * WS - 1) + ((qi & 7) - (kj & 7) + WS - 1);
-          packed[((size_t)hh * WT + kj) * WT + qi] = host_f32[(size_t)idx * L.cout + hh];
-        }
-  } else if (L.kind == LNORM) {
-    packed.assign(host_f32, host_f32 + L.cout);
-  } else {
-    pack_gemm_tensor(L.kind == CONV, j == 1, L.cin, L.cout, host_f32, packed);
-  }
-  float*& dst = j == 0 ? s->w[layer] : s->b[layer];
-  // a running forward may still read the old values: loading is host-synchronous, as in the sibling families
-  HIPCHK(nullptr, hipDeviceSynchronize());
-  drop_graphs(s);
-  if (!dst) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&dst), packed.size() * sizeof(float)));
-  HIPCHK(nullptr, hipMemcpy(dst, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-  s->have[(size_t)layer * 2 + j] = 1;
-  return FDSR_OK;
+  return engine_load<Swinir>("fdsr_swinir_load", s, name, host_f32, shape, ndim);
 }
 
 int fdsr_swinir_workspace_bytes(fdsr_swinir s, int batch, int height, int width, size_t* bytes) {
-  if (!s || !bytes) return fail(nullptr, FDSR_E_INVALID, "fdsr_swinir_workspace_bytes: null argument");
-  const int rc = check_shape("fdsr_swinir_workspace_bytes", batch, height, width);
-  if (rc) return rc;
-  *bytes = make_plan(s, batch, height, width).bytes;
-  return FDSR_OK;
+  return engine_workspace_bytes<Swinir>("fdsr_swinir_workspace_bytes", s, batch, height, width, bytes);
 }
 
 int fdsr_swinir_forward(fdsr_swinir s, const float* x_nchw, int batch, int height, int width, float* out_nchw, void* workspace,
                         size_t workspace_bytes, void* hip_stream, int flags) {
-  if (!out_nchw || (flags & ~FDSR_SWINIR_GRAPH)) return fail(nullptr, FDSR_E_INVALID, "fdsr_swinir_forward: bad arguments");
-  if ((flags & FDSR_SWINIR_GRAPH) && !hip_stream)
-    return fail(nullptr, FDSR_E_INVALID, "fdsr_swinir_forward: FDSR_SWINIR_GRAPH needs a created stream");
-  Walker wk{RUN};
-  int rc = prepare(s, "fdsr_swinir_forward", x_nchw, batch, height, width, workspace, workspace_bytes, hip_stream, &wk);
-  if (rc) return rc;
-  wk.dst = out_nchw;
-  if (!(flags & FDSR_SWINIR_GRAPH)) {
-    wk.walk();
-    return wk.err;
-  }
-  // one graph per (B, H, W); other pointers under the same shape capture anew
-  Graph* g = nullptr;
-  for (Graph& q : s->graphs)
-    if (q.B == batch && q.H == height && q.W == width) g = &q;
-  if (g && !(g->x == x_nchw && g->out == out_nchw && g->ws == workspace)) {
-    (void)hipGraphExecDestroy(g->exec);
-    s->graphs.erase(s->graphs.begin() + (g - s->graphs.data()));
-    g = nullptr;
-  }
-  if (!g) {
-    hipGraphExec_t exec = nullptr;
-    if ((rc = capture_exec(nullptr, wk.st, [&]() -> int { wk.walk(); return wk.err; }, &exec))) return rc;
-    s->graphs.push_back(Graph{batch, height, width, x_nchw, out_nchw, workspace, exec});
-    g = &s->graphs.back();
-  }
-  HIPCHK(nullptr, hipGraphLaunch(g->exec, wk.st));
-  return FDSR_OK;
+  return engine_forward<Swinir>("fdsr_swinir_forward", s, x_nchw, batch, height, width, out_nchw, workspace, workspace_bytes, hip_stream, flags);
 }
 
 int fdsr_swinir_debug_tensor(fdsr_swinir s, const char* name, const float* x_nchw, int batch, int height, int width, float* out_nhwc,
                              size_t capacity_floats, int* dims3, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (!name || !out_nhwc || !dims3) return fail(nullptr, FDSR_E_INVALID, "fdsr_swinir_debug_tensor: null argument");
-  Walker wk{RUN};
-  const int rc = prepare(s, "fdsr_swinir_debug_tensor", x_nchw, batch, height, width, workspace, workspace_bytes, hip_stream, &wk);
-  if (rc) return rc;
-  // the name is checked before anything runs: a walk that meets no tap would end in conv_last's store
-  const bool known = std::find(s->taps.begin(), s->taps.end(), std::string(name)) != s->taps.end();
-  if (!known) return fail(nullptr, FDSR_E_KEY, "fdsr_swinir_debug_tensor: unknown tap '%s'", name);
-  wk.stop = name;
-  wk.walk();
-  if (wk.err) return wk.err;
-  if (!wk.done) return fail(nullptr, FDSR_E_KEY, "fdsr_swinir_debug_tensor: tap '%s' was not reached", name);
-  const T& tp = wk.tapped;
-  const size_t count = (size_t)batch * tp.H * tp.W * tp.C;
-  if (count > capacity_floats) return fail(nullptr, FDSR_E_INVALID, "fdsr_swinir_debug_tensor: '%s' needs %zu floats", name, count);
-  dims3[0] = tp.H; dims3[1] = tp.W; dims3[2] = tp.C;
-  HIPCHK(nullptr, hipMemcpyAsync(out_nhwc, wk.buf[tp.buf], count * sizeof(float), hipMemcpyDeviceToDevice, wk.st));
-  return FDSR_OK;
+  return engine_debug_tensor<Swinir>("fdsr_swinir_debug_tensor", s, name, x_nchw, batch, height, width, out_nhwc, capacity_floats, dims3, workspace,
+                                     workspace_bytes, hip_stream);
 }
 
 int fdsr_swinir_to_u8(const float* src_nchw, uint8_t* dst_nhwc, int batch, int height, int width, void* hip_stream) {

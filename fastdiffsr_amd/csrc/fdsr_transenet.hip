@@ -32,6 +32,7 @@
 
 #include "fdsr_engine_int.h"
 #include "fdsr_swin_common.h"
+#include "fdsr_swin_engine.h"
 
 using namespace fdsr_int;
 
@@ -41,7 +42,6 @@ constexpr int DIM = 512, HEADS = 6, INNER = HEADS * HD, MLP = 512, PS = 8;   // 
 constexpr int QB = 32;                     // queries of one workgroup
 constexpr int KC = 128;                    // keys per staged chunk
 constexpr int KP = KC + 32;                // pitch of the [d][key] chunk
-constexpr int NBUF = 18;
 
 enum TransEpi { EPI_RELU = EPI_EXT, EPI_GELUT = EPI_EXT + 1, EPI_SCATTER = EPI_EXT + 2 };
 
@@ -233,39 +233,43 @@ struct LayerDesc {
   }
 };
 
-struct Walker {
-  Mode mode;
-  fdsr_transenet_config cfg{};
-  std::vector<LayerDesc>* table = nullptr;      // TABLE: appended to
-  std::vector<std::string>* taps = nullptr;     // TABLE: the tap names, appended to
-  size_t need[NBUF] = {};                       // SIZE: floats per image of each buffer
-  int N = 0, Hin = 0, Win = 0;
-  const float* img = nullptr;                   // RUN: the input, NCHW
-  float* dst = nullptr;                         // RUN: the output, NCHW (null: a debug walk, which ends at `stop`)
-  float* buf[NBUF] = {};
-  float* const* w = nullptr;
-  float* const* b = nullptr;
-  hipStream_t st = nullptr;
-  int li = 0;                                   // the next layer's index (load order)
-  const char* stop = nullptr;                   // RUN: the tap to end at
-  bool done = false;
-  T tapped{};
-  int err = FDSR_OK;
+struct Walker;
 
-  bool live() const { return mode == RUN && err == FDSR_OK && !done; }
-  void touch(const T& t) { need[t.buf] = std::max(need[t.buf], (size_t)t.H * t.W * t.C); }
-  void check(hipError_t e) {
-    if (e != hipSuccess && err == FDSR_OK) err = fail(nullptr, FDSR_E_HIP, "fdsr_transenet: kernel launch failed: %s", hipGetErrorString(e));
-  }
-  void tap(const std::string& name, const T& t) {
-    if (mode == TABLE) taps->push_back(name);
-    if (live() && stop && name == stop) { done = true; tapped = t; }
-  }
-  int layer(const std::string& name, Kind kind, int cin, int cout) {
-    if (mode == TABLE) table->push_back(LayerDesc{name, kind, cin, cout});
-    return li++;
+// what fdsr_swin_engine.h needs to know of this family
+struct Transenet : FamilyDefaults {
+  using Config = fdsr_transenet_config;
+  using Desc = LayerDesc;
+  using Walk = Walker;
+  using Obj = fdsr_transenet_obj;
+  static constexpr const char *name = "fdsr_transenet", *graph_flag_name = "FDSR_TRANSENET_GRAPH";
+  static constexpr int NBUF = 18, SIDE = PS, graph_flag = FDSR_TRANSENET_GRAPH;
+
+  static int check_shape(const char* fn, int B, int H, int W) {
+    if (B < 1 || H < 1 || W < 1) return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, B, H, W);
+    if (H % PS || W % PS) return fail(nullptr, FDSR_E_INVALID, "%s: a %dx%d image is not made of 8 x 8 patches (both sides must be multiples of 8)", fn, H, W);
+    if ((long long)B * H * W * 64 > (1ll << 30)) return fail(nullptr, FDSR_E_INVALID, "%s: %d images of %dx%d are too many pixels for one call", fn, B, H, W);
+    return FDSR_OK;
   }
 
+  // device: LINEAR / LINEAR_NB / CONV / CONV1 packed [Kpad][Npad] + bias [Npad] (LINEAR_NB: zeros); LNORM gamma + beta; MEAN as the checkpoint holds it
+  static void pack(const LayerDesc& L, int j, const float* host_f32, std::vector<float>& packed) {
+    if (L.kind == LNORM) packed.assign(host_f32, host_f32 + L.cout);
+    else if (L.kind == MEAN) packed.assign(host_f32, host_f32 + (j == 1 ? 3 : 9));
+    else pack_gemm_tensor(L.kind == CONV, j == 1, L.cin, L.cout, host_f32, packed);
+  }
+
+  // bias=False: the GEMM adds a row of zeros
+  static int after_load(Engine<Transenet>& s, int layer) {
+    const LayerDesc& L = s.table[layer];
+    if (L.kind != LINEAR_NB || s.b[layer]) return FDSR_OK;
+    const size_t bytes = (size_t)gemm_npad(L.cout) * sizeof(float);
+    HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&s.b[layer]), bytes));
+    HIPCHK(nullptr, hipMemset(s.b[layer], 0, bytes));
+    return FDSR_OK;
+  }
+};
+
+struct Walker : WalkerBase<Transenet> {
   // out = epilogue(gather(in) . W + bias).  res: the EPI_RES addend (may be the output).  r: the EPI_SHUFFLE factor.
   // patch: the rows are the 8 x 8 x C patches of `in`.
   T gemm(const std::string& name, Kind kind, int epi, const T& in, int cout, int ob, const T* res = nullptr, int r = 1, bool patch = false) {
@@ -277,20 +281,10 @@ struct Walker {
     if (mode == SIZE) touch(out);
     if (!live()) return out;
     GemmArgs a{};
-    a.x = buf[in.buf];
-    a.w = w[idx];
-    a.bias = b[idx];
-    a.res = res ? buf[res->buf] : nullptr;
+    gemm_args(a, idx, in, res, kind == CONV, cin, cout, r);
     a.out = buf[ob];
-    a.M = patch ? N * out.H * out.W : N * in.H * in.W;
-    a.N = cout;
-    a.K = kind == CONV ? 9 * cin : cin;
-    a.Kpad = gemm_kpad(kind == CONV, cin);
-    a.Npad = gemm_npad(cout);
-    a.H = epi == EPI_SCATTER ? out.H : in.H;
-    a.W = epi == EPI_SCATTER ? out.W : in.W;
-    a.Cin = epi == EPI_SCATTER ? out.C : in.C;
-    a.r = r;
+    if (patch) a.M = N * out.H * out.W;
+    if (epi == EPI_SCATTER) a.H = out.H, a.W = out.W, a.Cin = out.C;
     const bool vec = in.C % 4 == 0;
     if (patch) {
       check(launch_swin_gemm<PATCH8, EPI_NONE>(a, vec, st));
@@ -305,16 +299,6 @@ struct Walker {
       else if (epi == EPI_GELUT) check(launch_swin_gemm<ROWS, EPI_GELUT>(a, vec, st));
       else check(launch_swin_gemm<ROWS, EPI_SCATTER>(a, vec, st));
     }
-    return out;
-  }
-
-  T norm(int idx, const T& in, int ob) {
-    T out{ob, in.H, in.W, in.C};
-    if (mode == SIZE) touch(out);
-    if (!live()) return out;
-    const int M = N * in.H * in.W;
-    hipLaunchKernelGGL(swin_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, buf[in.buf], w[idx], b[idx], buf[ob], M, in.C);
-    check(hipGetLastError());
     return out;
   }
 
@@ -441,81 +425,9 @@ struct Walker {
   }
 };
 
-struct Plan { size_t off[NBUF]; size_t bytes; };
-
-struct Graph { int B, H, W; const void *x, *out, *ws; hipGraphExec_t exec; };
-
 }  // namespace
 
-struct fdsr_transenet_obj {
-  fdsr_transenet_config cfg{};
-  std::vector<LayerDesc> table;
-  std::vector<std::string> taps;
-  std::vector<unsigned char> have;   // [layer * 2 + j]
-  // device: LINEAR / LINEAR_NB / CONV / CONV1 packed [Kpad][Npad] + bias [Npad] (LINEAR_NB: zeros); LNORM gamma + beta; MEAN as the checkpoint holds it
-  std::vector<float*> w, b;
-  std::vector<Graph> graphs;
-};
-
-namespace {
-
-Walker walker(fdsr_transenet s, Mode mode, int B, int H, int W) {
-  Walker wk{mode};
-  wk.cfg = s->cfg;
-  wk.N = B;
-  wk.Hin = H;
-  wk.Win = W;
-  return wk;
-}
-
-Plan make_plan(fdsr_transenet s, int B, int H, int W) {
-  Walker wk = walker(s, SIZE, B, H, W);
-  wk.walk();
-  Plan pl{};
-  size_t off = 0;
-  for (int i = 0; i < NBUF; ++i) {
-    pl.off[i] = off;
-    off = align_up(off + (size_t)B * wk.need[i] * sizeof(float), 256);
-  }
-  pl.bytes = off;
-  return pl;
-}
-
-void drop_graphs(fdsr_transenet s) {
-  for (Graph& g : s->graphs)
-    if (g.exec) (void)hipGraphExecDestroy(g.exec);
-  s->graphs.clear();
-}
-
-int check_shape(const char* fn, int B, int H, int W) {
-  if (B < 1 || H < 1 || W < 1) return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, B, H, W);
-  if (H % PS || W % PS) return fail(nullptr, FDSR_E_INVALID, "%s: a %dx%d image is not made of 8 x 8 patches (both sides must be multiples of 8)", fn, H, W);
-  if ((long long)B * H * W * 64 > (1ll << 30)) return fail(nullptr, FDSR_E_INVALID, "%s: %d images of %dx%d are too many pixels for one call", fn, B, H, W);
-  return FDSR_OK;
-}
-
-// everything a forward or a debug walk checks, then the walker ready to run
-int prepare(fdsr_transenet s, const char* fn, const float* x, int B, int H, int W, void* ws, size_t ws_bytes, void* stream, Walker* out) {
-  if (!s || !x || !ws) return fail(nullptr, FDSR_E_INVALID, "%s: null argument", fn);
-  int rc = check_shape(fn, B, H, W);
-  if (rc) return rc;
-  for (size_t L = 0; L < s->table.size(); ++L)
-    for (int j = 0; j < s->table[L].tensors(); ++j)
-      if (!s->have[L * 2 + j]) return fail(nullptr, FDSR_E_STATE, "%s: tensor '%s' is missing", fn, s->table[L].tensor_name(j).c_str());
-  const Plan pl = make_plan(s, B, H, W);
-  if (ws_bytes < pl.bytes || (reinterpret_cast<uintptr_t>(ws) & 255))
-    return fail(nullptr, FDSR_E_WORKSPACE, "%s: workspace too small (%zu < %zu bytes) or not 256-byte aligned", fn, ws_bytes, pl.bytes);
-  Walker wk = walker(s, RUN, B, H, W);
-  wk.img = x;
-  for (int i = 0; i < NBUF; ++i) wk.buf[i] = reinterpret_cast<float*>(static_cast<char*>(ws) + pl.off[i]);
-  wk.w = s->w.data();
-  wk.b = s->b.data();
-  wk.st = reinterpret_cast<hipStream_t>(stream);
-  *out = wk;
-  return FDSR_OK;
-}
-
-}  // namespace
+struct fdsr_transenet_obj : Engine<Transenet> {};
 
 extern "C" {
 
@@ -531,121 +443,28 @@ int fdsr_transenet_create(const fdsr_transenet_config* cfg, fdsr_transenet* out)
     return fail(nullptr, FDSR_E_INVALID, "fdsr_transenet_create: en_depth %d (1..%d)", c.en_depth, FDSR_TRANSENET_MAX_DEPTH);
   if (c.de_depth < 1 || c.de_depth > FDSR_TRANSENET_MAX_DEPTH)
     return fail(nullptr, FDSR_E_INVALID, "fdsr_transenet_create: de_depth %d (1..%d)", c.de_depth, FDSR_TRANSENET_MAX_DEPTH);
-  fdsr_transenet s = new (std::nothrow) fdsr_transenet_obj();
-  if (!s) return fail(nullptr, FDSR_E_INVALID, "fdsr_transenet_create: out of host memory");
-  s->cfg = c;
-  Walker wk = walker(s, TABLE, 1, PS, PS);
-  wk.table = &s->table;
-  wk.taps = &s->taps;
-  wk.walk();
-  s->have.assign(s->table.size() * 2, 0);
-  s->w.assign(s->table.size(), nullptr);
-  s->b.assign(s->table.size(), nullptr);
-  *out = s;
-  return FDSR_OK;
+  return engine_create<Transenet>("fdsr_transenet_create", c, out);
 }
 
-void fdsr_transenet_destroy(fdsr_transenet s) {
-  if (!s) return;
-  drop_graphs(s);
-  for (float* p : s->w)
-    if (p) (void)hipFree(p);
-  for (float* p : s->b)
-    if (p) (void)hipFree(p);
-  delete s;
-}
+void fdsr_transenet_destroy(fdsr_transenet s) { engine_destroy<Transenet>(s); }
 
 int fdsr_transenet_load(fdsr_transenet s, const char* name, const float* host_f32, const int64_t* shape, int ndim) {
-  if (!s || !name || !host_f32 || (ndim > 0 && !shape) || ndim < 0) return fail(nullptr, FDSR_E_INVALID, "fdsr_transenet_load: bad arguments");
-  const std::string nm(name);
-  int layer = -1, j = -1;
-  for (size_t L = 0; L < s->table.size() && layer < 0; ++L)
-    for (int q = 0; q < s->table[L].tensors(); ++q)
-      if (s->table[L].tensor_name(q) == nm) { layer = (int)L; j = q; break; }
-  if (layer < 0) return fail(nullptr, FDSR_E_KEY, "fdsr_transenet_load: unknown tensor '%s'", name);
-  const LayerDesc& L = s->table[layer];
-  const std::vector<int64_t> want = L.shape(j);
-  if (ndim != (int)want.size() || !std::equal(want.begin(), want.end(), shape))
-    return fail(nullptr, FDSR_E_KEY, "fdsr_transenet_load: '%s' has the wrong shape", name);
-  std::vector<float> packed;
-  if (L.kind == LNORM) packed.assign(host_f32, host_f32 + L.cout);
-  else if (L.kind == MEAN) packed.assign(host_f32, host_f32 + (j == 1 ? 3 : 9));
-  else pack_gemm_tensor(L.kind == CONV, j == 1, L.cin, L.cout, host_f32, packed);
-  float*& dst = j == 0 ? s->w[layer] : s->b[layer];
-  // a running forward may still read the old values: loading is host-synchronous, as in the sibling families
-  HIPCHK(nullptr, hipDeviceSynchronize());
-  drop_graphs(s);
-  if (!dst) HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&dst), packed.size() * sizeof(float)));
-  HIPCHK(nullptr, hipMemcpy(dst, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (L.kind == LINEAR_NB && !s->b[layer]) {
-    // bias=False: the GEMM adds a row of zeros
-    const size_t bytes = (size_t)gemm_npad(L.cout) * sizeof(float);
-    HIPCHK(nullptr, hipMalloc(reinterpret_cast<void**>(&s->b[layer]), bytes));
-    HIPCHK(nullptr, hipMemset(s->b[layer], 0, bytes));
-  }
-  s->have[(size_t)layer * 2 + j] = 1;
-  return FDSR_OK;
+  return engine_load<Transenet>("fdsr_transenet_load", s, name, host_f32, shape, ndim);
 }
 
 int fdsr_transenet_workspace_bytes(fdsr_transenet s, int batch, int height, int width, size_t* bytes) {
-  if (!s || !bytes) return fail(nullptr, FDSR_E_INVALID, "fdsr_transenet_workspace_bytes: null argument");
-  const int rc = check_shape("fdsr_transenet_workspace_bytes", batch, height, width);
-  if (rc) return rc;
-  *bytes = make_plan(s, batch, height, width).bytes;
-  return FDSR_OK;
+  return engine_workspace_bytes<Transenet>("fdsr_transenet_workspace_bytes", s, batch, height, width, bytes);
 }
 
 int fdsr_transenet_forward(fdsr_transenet s, const float* x_nchw, int batch, int height, int width, float* out_nchw, void* workspace,
                            size_t workspace_bytes, void* hip_stream, int flags) {
-  if (!out_nchw || (flags & ~FDSR_TRANSENET_GRAPH)) return fail(nullptr, FDSR_E_INVALID, "fdsr_transenet_forward: bad arguments");
-  if ((flags & FDSR_TRANSENET_GRAPH) && !hip_stream)
-    return fail(nullptr, FDSR_E_INVALID, "fdsr_transenet_forward: FDSR_TRANSENET_GRAPH needs a created stream");
-  Walker wk{RUN};
-  int rc = prepare(s, "fdsr_transenet_forward", x_nchw, batch, height, width, workspace, workspace_bytes, hip_stream, &wk);
-  if (rc) return rc;
-  wk.dst = out_nchw;
-  if (!(flags & FDSR_TRANSENET_GRAPH)) {
-    wk.walk();
-    return wk.err;
-  }
-  // one graph per (B, H, W); other pointers under the same shape capture anew
-  Graph* g = nullptr;
-  for (Graph& q : s->graphs)
-    if (q.B == batch && q.H == height && q.W == width) g = &q;
-  if (g && !(g->x == x_nchw && g->out == out_nchw && g->ws == workspace)) {
-    (void)hipGraphExecDestroy(g->exec);
-    s->graphs.erase(s->graphs.begin() + (g - s->graphs.data()));
-    g = nullptr;
-  }
-  if (!g) {
-    hipGraphExec_t exec = nullptr;
-    if ((rc = capture_exec(nullptr, wk.st, [&]() -> int { wk.walk(); return wk.err; }, &exec))) return rc;
-    s->graphs.push_back(Graph{batch, height, width, x_nchw, out_nchw, workspace, exec});
-    g = &s->graphs.back();
-  }
-  HIPCHK(nullptr, hipGraphLaunch(g->exec, wk.st));
-  return FDSR_OK;
+  return engine_forward<Transenet>("fdsr_transenet_forward", s, x_nchw, batch, height, width, out_nchw, workspace, workspace_bytes, hip_stream, flags);
 }
 
 int fdsr_transenet_debug_tensor(fdsr_transenet s, const char* name, const float* x_nchw, int batch, int height, int width, float* out_nhwc,
                                 size_t capacity_floats, int* dims3, void* workspace, size_t workspace_bytes, void* hip_stream) {
-  if (!name || !out_nhwc || !dims3) return fail(nullptr, FDSR_E_INVALID, "fdsr_transenet_debug_tensor: null argument");
-  Walker wk{RUN};
-  const int rc = prepare(s, "fdsr_transenet_debug_tensor", x_nchw, batch, height, width, workspace, workspace_bytes, hip_stream, &wk);
-  if (rc) return rc;
-  // the name is checked before anything runs
-  const bool known = std::find(s->taps.begin(), s->taps.end(), std::string(name)) != s->taps.end();
-  if (!known) return fail(nullptr, FDSR_E_KEY, "fdsr_transenet_debug_tensor: unknown tap '%s'", name);
-  wk.stop = name;
-  wk.walk();
-  if (wk.err) return wk.err;
-  if (!wk.done) return fail(nullptr, FDSR_E_KEY, "fdsr_transenet_debug_tensor: tap '%s' was not reached", name);
-  const T& tp = wk.tapped;
-  const size_t count = (size_t)batch * tp.H * tp.W * tp.C;
-  if (count > capacity_floats) return fail(nullptr, FDSR_E_INVALID, "fdsr_transenet_debug_tensor: '%s' needs %zu floats", name, count);
-  dims3[0] = tp.H; dims3[1] = tp.W; dims3[2] = tp.C;
-  HIPCHK(nullptr, hipMemcpyAsync(out_nhwc, wk.buf[tp.buf], count * sizeof(float), hipMemcpyDeviceToDevice, wk.st));
-  return FDSR_OK;
+  return engine_debug_tensor<Transenet>("fdsr_transenet_debug_tensor", s, name, x_nchw, batch, height, width, out_nhwc, capacity_floats, dims3,
+                                        workspace, workspace_bytes, hip_stream);
 }
 
 }  // extern "C"

@@ -9,14 +9,13 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from .._engine_module import EngineModule, _ptr
 from .arch import RGB_MEAN, SwinIRConfig, buffer_value, is_buffer, state_schema, tap_names
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p()
+class SwinIR(EngineModule):
+    _family, _tap_names = 'swinir', staticmethod(tap_names)
 
-
-class SwinIR(nn.Module):
     def __init__(self, img_size=256, patch_size=1, in_chans=3, embed_dim=96, depths=(6, 6, 6, 6), num_heads=(6, 6, 6, 6), window_size=7,
                  mlp_ratio=4., qkv_bias=True, qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.1, norm_layer=nn.LayerNorm,
                  ape=False, patch_norm=True, use_checkpoint=False, upscale=4, img_range=1., upsampler='pixelshuffle',
@@ -46,106 +45,32 @@ class SwinIR(nn.Module):
                 self.register_buffer('p%d' % i, torch.from_numpy(buffer_value(self.cfg, k)))
             else:
                 self.register_parameter('p%d' % i, nn.Parameter(torch.zeros(shape), requires_grad=False))
-        self._h = None
-        self._uploaded = {}
-        self._ws = {}
-        self._static = {}
-        self._handle()     # refuses what the kernels do not cover (head_dim, embed_dim) with the library's message
+        self._init_engine()     # refuses what the kernels do not cover (head_dim, embed_dim) with the library's message
 
     # ---- the reference's keys ----
-    def _save_to_state_dict(self, destination, prefix, keep_vars):
-        for i, k in enumerate(self._names):
-            p = getattr(self, 'p%d' % i)
-            destination[prefix + k] = p if keep_vars else p.detach()
+    def _is_buffer(self, k):
+        return is_buffer(k)
 
-    def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
-        for i, k in enumerate(self._names):
-            key = prefix + k
-            if key not in state_dict:
-                if strict:
-                    missing_keys.append(key)
-                continue
-            src, p = state_dict[key], getattr(self, 'p%d' % i)
-            if is_buffer(k):
-                # a function of the geometry, never sent to the device: checked where the sizes match (an attn_mask of another
-                # img_size is the same function at another size)
-                if tuple(src.shape) == tuple(p.shape) and not torch.equal(src.to(p.device, p.dtype), p):
-                    error_msgs.append('buffer %s differs from what the window geometry gives' % key)
-                continue
-            if tuple(src.shape) != tuple(p.shape):
-                error_msgs.append('size mismatch for %s: copying a param with shape %s from checkpoint, the shape in current '
-                                  'model is %s.' % (key, tuple(src.shape), tuple(p.shape)))
-                continue
-            with torch.no_grad():
-                p.copy_(src)
-        if strict:
-            known = {prefix + k for k in self._names}
-            unexpected_keys += [k for k in state_dict if k.startswith(prefix) and k not in known]
+    def _buffer_differs(self, src, p):
+        # checked where the sizes match (an attn_mask of another img_size is the same function at another size)
+        return tuple(src.shape) == tuple(p.shape) and not torch.equal(src.to(p.device, p.dtype), p)
 
     def named_reference_parameters(self):
         return [(k, getattr(self, 'p%d' % i)) for i, k in enumerate(self._names) if not is_buffer(k)]
 
     # ---- the engine ----
-    def _handle(self):
-        if self._h is None:
-            cfg = self.cfg
-            if len(cfg.depths) > _lib.FDSR_SWINIR_MAX_LAYERS:
-                raise NotImplementedError('at most %d layers' % _lib.FDSR_SWINIR_MAX_LAYERS)
-            c = _lib.FdsrSwinirConfig()
-            c.embed_dim, c.n_layers, c.window_size, c.mlp_hidden = cfg.embed_dim, len(cfg.depths), cfg.window_size, cfg.mlp_hidden
-            c.upscale, c.patch_norm, c.img_range = cfg.upscale, int(cfg.patch_norm), cfg.img_range
-            for i, (d, h) in enumerate(zip(cfg.depths, cfg.num_heads)):
-                c.depths[i], c.num_heads[i] = d, h
-            for i in range(3):
-                c.mean[i] = RGB_MEAN[i]
-            h = C.c_void_p()
-            try:
-                _lib.check(None, _lib.load().fdsr_swinir_create(C.byref(c), C.byref(h)))
-            except _lib.FdsrError as e:
-                raise NotImplementedError(str(e)) from e
-            self._h = h
-        return self._h
-
-    def __del__(self):
-        h = getattr(self, '_h', None)
-        if h is not None and _lib._lib is not None:
-            _lib._lib.fdsr_swinir_destroy(h)
-            self._h = None
-
-    def __getstate__(self):
-        """copy.deepcopy and pickle carry the tensors and the configuration; a copy creates an engine of its own on first use."""
-        d = dict(self.__dict__)
-        d['_h'], d['_uploaded'], d['_ws'], d['_static'] = None, {}, {}, {}
-        return d
-
-    def sync_weights(self, device):
-        """Upload the parameters that changed since their last upload, by (_version, data_ptr)."""
-        lib, h = _lib.load(), self._handle()
-        if self._uploaded.get('device') != str(device):
-            self._uploaded = {'device': str(device)}
-        with torch.cuda.device(device):
-            for k, p in self.named_reference_parameters():
-                stamp = (p._version, p.data_ptr())
-                if self._uploaded.get(k) == stamp:
-                    continue
-                a = p.detach().to('cpu', torch.float32).contiguous()
-                shape = (C.c_int64 * a.dim())(*a.shape)
-                _lib.check(None, lib.fdsr_swinir_load(h, k.encode(), _ptr(a), shape, a.dim()))
-                self._uploaded[k] = stamp
-
-    def workspace_bytes(self, b, h, w):
-        need = C.c_size_t()
-        _lib.check(None, _lib.load().fdsr_swinir_workspace_bytes(self._handle(), b, h, w, C.byref(need)))
-        return need.value
-
-    def workspace(self, b, h, w, device=None):
-        device = device or next(self.parameters()).device
-        need = self.workspace_bytes(b, h, w)
-        key = (str(device), torch.cuda.current_stream(device).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=device)
-        return ws
+    def _fill_config(self):
+        cfg = self.cfg
+        if len(cfg.depths) > _lib.FDSR_SWINIR_MAX_LAYERS:
+            raise NotImplementedError('at most %d layers' % _lib.FDSR_SWINIR_MAX_LAYERS)
+        c = _lib.FdsrSwinirConfig()
+        c.embed_dim, c.n_layers, c.window_size, c.mlp_hidden = cfg.embed_dim, len(cfg.depths), cfg.window_size, cfg.mlp_hidden
+        c.upscale, c.patch_norm, c.img_range = cfg.upscale, int(cfg.patch_norm), cfg.img_range
+        for i, (d, h) in enumerate(zip(cfg.depths, cfg.num_heads)):
+            c.depths[i], c.num_heads[i] = d, h
+        for i in range(3):
+            c.mean[i] = RGB_MEAN[i]
+        return c
 
     @staticmethod
     def _check(x):
@@ -153,64 +78,14 @@ class SwinIR(nn.Module):
             raise ValueError('SwinIR takes a [B,3,H,W] tensor on the GPU (there is no CPU path)')
         return x.float().contiguous()
 
-    def forward(self, x, graph=False):
-        """[B,3,H,W] fp32 in [0, 1] on the GPU -> [B,3,H*scale,W*scale].  graph=True replays one captured graph per (B, H, W):
-        the call copies x into, and the result out of, buffers that the graph keeps."""
-        x = self._check(x)
-        b, _, h, w = x.shape
-        s = self.upscale
-        self.sync_weights(x.device)
-        lib, hd = _lib.load(), self._handle()
-        with torch.cuda.device(x.device):
-            if not graph:
-                out = torch.empty((b, 3, h * s, w * s), dtype=torch.float32, device=x.device)
-                ws = self.workspace(b, h, w, x.device)
-                st = torch.cuda.current_stream(x.device).cuda_stream
-                _lib.check(None, lib.fdsr_swinir_forward(hd, _ptr(x), b, h, w, _ptr(out), _ptr(ws), ws.numel(), C.c_void_p(st), 0))
-                return out
-            stream = torch.cuda.current_stream(x.device)
-            if stream.cuda_stream == 0:           # capture cannot run on the NULL stream
-                if not hasattr(self, '_graph_stream'):
-                    self._graph_stream = torch.cuda.Stream(x.device)
-                side = self._graph_stream
-                side.wait_stream(stream)
-                with torch.cuda.stream(side):
-                    out = self._graph_call(x, b, h, w, side)
-                stream.wait_stream(side)
-                return out
-            return self._graph_call(x, b, h, w, stream)
+    def output_shape(self, b, h, w):
+        """The reference crops to the input's size times the scale."""
+        return (b, 3, h * self.upscale, w * self.upscale)
 
-    def _graph_call(self, x, b, h, w, stream):
-        key = (str(x.device), stream.cuda_stream, b, h, w)
-        if key not in self._static:
-            s = self.upscale
-            self._static[key] = (torch.empty_like(x), torch.empty((b, 3, h * s, w * s), dtype=torch.float32, device=x.device),
-                                 torch.empty(self.workspace_bytes(b, h, w), dtype=torch.uint8, device=x.device))
-        xin, out, ws = self._static[key]
-        xin.copy_(x)
-        _lib.check(None, _lib.load().fdsr_swinir_forward(self._handle(), _ptr(xin), b, h, w, _ptr(out), _ptr(ws), ws.numel(),
-                                                         C.c_void_p(stream.cuda_stream), _lib.FDSR_SWINIR_GRAPH))
-        return out.clone()
-
-    def debug_tensor(self, name, x):
-        """The named tap of one forward (arch.tap_names), NCHW at the padded size."""
-        x = self._check(x)
-        b, _, h, w = x.shape
-        if name not in tap_names(self.cfg):
-            raise KeyError(name)
-        self.sync_weights(x.device)
+    def _debug_capacity(self, b, h, w):
         pad = self.window_size
         hp, wp = -(-h // pad) * pad, -(-w // pad) * pad
-        with torch.cuda.device(x.device):
-            cap = b * hp * wp * self.upscale ** 2 * max(self.cfg.embed_dim, 64)
-            out = torch.empty(cap, dtype=torch.float32, device=x.device)
-            dims = (C.c_int * 3)()
-            ws = self.workspace(b, h, w, x.device)
-            st = torch.cuda.current_stream(x.device).cuda_stream
-            _lib.check(None, _lib.load().fdsr_swinir_debug_tensor(self._handle(), name.encode(), _ptr(x), b, h, w, _ptr(out), cap, dims,
-                                                                  _ptr(ws), ws.numel(), C.c_void_p(st)))
-        th, tw, tc = dims[0], dims[1], dims[2]
-        return out[:b * th * tw * tc].view(b, th, tw, tc).permute(0, 3, 1, 2).contiguous()
+        return b * hp * wp * self.upscale ** 2 * max(self.cfg.embed_dim, 64)
 
 
 def to_u8(x):
