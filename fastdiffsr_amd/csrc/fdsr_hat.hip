@@ -11,7 +11,11 @@
 //   y    = pixel_shuffle(conv(y)) per factor of two, ONE convolution for every stage (one conv + PixelShuffle(3) at scale 3);
 //          out = conv_last(y) / img_range + mean at the PADDED size times the scale (the reference does not crop), NCHW
 //
-// The token GEMM, LayerNorm and the input kernel are fdsr_swin_common.h's.  New here:
+// The token GEMM, LayerNorm, the input kernel, the accumulator's row map and the attention kernel's chunk sizes (QB, KC, KP) are
+// fdsr_swin_common.h's.  The walk of the network, its GEMM dispatcher, the
+// common tensor kinds and the shape and configuration checks are fdsr_swin_walk.h's, shared with SwinIR; the host side here is
+// HAT's block bodies (Walker::group: the HABs with their CAB branch, the OCAB), its kinds RPB_OCA and GATE, its one shared
+// upsampling convolution, its traits and its extern "C" functions.  New here:
 //   hat_attn_kernel<OCA>  one workgroup per (image, window, head, block of 32 queries).  The block's full score rows stay in
 //                         LDS ([key][query], 256 or 576 keys): exact max / exp / sum / divide.  k, and after the softmax v, stream
 //                         through LDS in chunks of 128 keys.  The roll, the partition, the region ids, the -100 mask, the bias
@@ -37,6 +41,7 @@
 #include "fdsr_engine_int.h"
 #include "fdsr_swin_common.h"
 #include "fdsr_swin_engine.h"
+#include "fdsr_swin_walk.h"
 
 using namespace fdsr_int;
 
@@ -44,9 +49,6 @@ namespace {
 
 constexpr int WS = 16, WT = WS * WS;       // the window and its tokens
 constexpr int WSE = 24, WKT = WSE * WSE;   // the overlapping window (overlap_ratio 0.5) and its keys
-constexpr int QB = 32;                     // queries of one workgroup: a score row pitch of 32 keeps the two k rows of an MFMA operand read 32 banks apart
-constexpr int KC = 128;                    // keys per staged chunk
-constexpr int KP = KC + 32;                // pitch of the [d][key] chunk
 
 enum HatEpi { EPI_COLSUM = EPI_EXT, EPI_HAB = EPI_EXT + 1 };
 
@@ -57,10 +59,6 @@ struct HatGemmArgs : GemmArgs {
   float conv_scale;
 };
 
-}  // namespace
-
-namespace {
-
 template <int EPI, class ARGS>
 __device__ void gemm_epilogue_ext(const ARGS& p, const f32x16 (&acc)[2], int row0, int co, int h, float bias) {
   if constexpr (EPI == EPI_COLSUM) {
@@ -70,7 +68,7 @@ __device__ void gemm_epilogue_ext(const ARGS& p, const f32x16 (&acc)[2], int row
     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int om = row0 + mb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+        const int om = acc_row(row0 + mb * 32, i, h);
         const float v = acc[mb][i] + bias;
         p.out[(size_t)om * p.N + co] = v;
         s += v;
@@ -83,7 +81,7 @@ __device__ void gemm_epilogue_ext(const ARGS& p, const f32x16 (&acc)[2], int row
     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int om = row0 + mb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+        const int om = acc_row(row0 + mb * 32, i, h);
         if (om >= p.M) continue;
         const size_t o = (size_t)om * p.N + co;
         const float v = acc[mb][i] + bias;
@@ -156,24 +154,20 @@ __global__ void __launch_bounds__(256) hat_attn_kernel(const float* __restrict__
   const int win = bx % nwin, b = bx / nwin;
   const int wy = win / nwx, wx = win - wy * nwx;
 
-  auto region = [&](int ys, int xs) {
-    const int rh = ys < H - WS ? 0 : ys < H - shift ? 1 : 2, rw = xs < W - WS ? 0 : xs < W - shift ? 1 : 2;
-    return shift > 0 ? rh * 3 + rw : 0;
-  };
+  auto pixel = [&](int tok) { return window_pixel<WS>(wy, wx, tok, shift, H, W); };
+  auto region = [&](int tok) { return window_region<WS>(wy, wx, tok, shift, H, W); };
   for (int kk = t; kk < NK; kk += 256) {
     if (OCA) {
       const int ky = kk / WSE, py = wy * WS - (WSE - WS) / 2 + ky, px = wx * WS - (WSE - WS) / 2 + (kk - ky * WSE);
       sKPix[kk] = (py >= 0 && py < H && px >= 0 && px < W) ? py * W + px : -1;
     } else {
-      const int ys = wy * WS + (kk >> 4), xs = wx * WS + (kk & 15);
-      sKPix[kk] = ((ys + shift) % H) * W + (xs + shift) % W;
-      sKRid[kk] = region(ys, xs);
+      sKPix[kk] = pixel(kk);
+      sKRid[kk] = region(kk);
     }
   }
   if (t < QB) {
-    const int q = qb * QB + t, ys = wy * WS + (q >> 4), xs = wx * WS + (q & 15);
-    sQPix[t] = ((ys + shift) % H) * W + (xs + shift) % W;
-    sQRid[t] = region(ys, xs);
+    sQPix[t] = pixel(qb * QB + t);
+    sQRid[t] = region(qb * QB + t);
   }
   __syncthreads();
   const size_t img = (size_t)b * H * W;
@@ -206,7 +200,7 @@ __global__ void __launch_bounds__(256) hat_attn_kernel(const float* __restrict__
     __syncthreads();
     const int j0 = c0 + wave * 32;
     if (j0 < NK) {
-      f32x16 acc;
+      f32x16 acc;   // not score_tile: this kernel compiles to other code with it
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
@@ -217,7 +211,7 @@ __global__ void __launch_bounds__(256) hat_attn_kernel(const float* __restrict__
       const int ri = sQRid[r31], qg = qb * QB + r31;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int j = j0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int j = acc_row(j0, r, h);
         float v = acc[r] + bh[(size_t)j * WT + qg];
         if (!OCA && sKRid[j] != ri) v += -100.f;
         sSt[j * QB + r31] = v;
@@ -276,51 +270,39 @@ __global__ void __launch_bounds__(256) hat_attn_kernel(const float* __restrict__
   if (wave == 0 && r31 < hd) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int i = (r & 3) + 8 * (r >> 2) + 4 * h;   // acc_row(0, r, h), written out: the call changes this kernel's code
       out[(img + sQPix[i]) * C + head * hd + r31] = o[r];
     }
   }
 }
 
-enum Kind { LINEAR, CONV, LNORM, RPB_SA, RPB_OCA, GATE };
+// the kinds HAT adds: RPB_OCA owns the tensor `name` itself (RPB is the bias table of the HABs' self-attention), GATE a 1x1
+// Conv2d as the checkpoint holds it
+enum HatKind { RPB_OCA = KIND_EXT, GATE };
 
-// One named module of the checkpoint: LINEAR / CONV / LNORM / GATE own name.weight and name.bias, RPB_* own the tensor `name`
-struct LayerDesc {
-  std::string name;
-  Kind kind;
-  int cin, cout;   // LNORM: cout = C;  RPB_*: cout = heads
-  bool rpb() const { return kind == RPB_SA || kind == RPB_OCA; }
-  int tensors() const { return rpb() ? 1 : 2; }
-  std::string tensor_name(int j) const { return rpb() ? name : name + (j == 0 ? ".weight" : ".bias"); }
+struct LayerDesc : SwinLayerDesc<WS> {
+  int tensors() const { return kind == RPB_OCA ? 1 : SwinLayerDesc::tensors(); }
+  std::string tensor_name(int j) const { return kind == RPB_OCA ? name : SwinLayerDesc::tensor_name(j); }
   std::vector<int64_t> shape(int j) const {
-    if (kind == RPB_SA) return {(2 * WS - 1) * (2 * WS - 1), cout};
     if (kind == RPB_OCA) return {(WS + WSE - 1) * (WS + WSE - 1), cout};
-    if (j == 1 || kind == LNORM) return {cout};
-    if (kind == CONV) return {cout, cin, 3, 3};
-    if (kind == GATE) return {cout, cin, 1, 1};
-    return {cout, cin};
+    if (kind == GATE && j == 0) return {cout, cin, 1, 1};
+    return SwinLayerDesc::shape(j);
   }
 };
 
 struct Walker;
 
-// what fdsr_swin_engine.h needs to know of this family
-struct Hat : FamilyDefaults {
+// what fdsr_swin_engine.h and fdsr_swin_walk.h need to know of this family
+struct Hat : SwinFamily<WS> {
   using Config = fdsr_hat_config;
   using Desc = LayerDesc;
   using Walk = Walker;
   using Obj = fdsr_hat_obj;
+  using Args = HatGemmArgs;
   static constexpr const char *name = "fdsr_hat", *graph_flag_name = "FDSR_HAT_GRAPH";
-  static constexpr int NBUF = 10, SIDE = WS, graph_flag = FDSR_HAT_GRAPH;
-
-  // F.pad's rule for 'reflect': the padding must be smaller than the side it mirrors
-  static int check_shape(const char* fn, int B, int H, int W) {
-    if (B < 1 || H < 1 || W < 1) return fail(nullptr, FDSR_E_INVALID, "%s: bad arguments (B %d, %dx%d)", fn, B, H, W);
-    const int ph = round_up(H, WS) - H, pw = round_up(W, WS) - W;
-    if (ph >= H || pw >= W)
-      return fail(nullptr, FDSR_E_INVALID, "%s: a %dx%d image cannot be reflect-padded by (%d, %d) to a multiple of the window", fn, H, W, ph, pw);
-    return FDSR_OK;
-  }
+  static constexpr int NBUF = 10, graph_flag = FDSR_HAT_GRAPH;
+  // no crop: the reference returns the padded size times the scale
+  static int out_side(const Config&, int, int padded) { return padded; }
 
   // upsample.upsampling.{2,4}.* name the tensor of upsample.upsampling.0.* again (one Conv2d in every stage)
   static std::string canonical_name(const fdsr_hat_config& cfg, const char* name) {
@@ -335,18 +317,9 @@ struct Hat : FamilyDefaults {
     return nm;
   }
 
-  // device: LINEAR / CONV packed [Kpad][Npad] + bias [Npad]; LNORM gamma + beta; GATE as the checkpoint holds it; RPB_* biasT [heads][keys][256]
+  // device: the common kinds as SwinFamily packs them; GATE as the checkpoint holds it; RPB_OCA biasT [heads][576 keys][256 queries]
   static void pack(const LayerDesc& L, int j, const float* host_f32, std::vector<float>& packed) {
-    if (L.kind == RPB_SA) {
-      // biasT[head][j][i] = table[(yi - yj + 15) * 31 + (xi - xj + 15)][head]: the gather of relative_position_index_SA, once
-      packed.resize((size_t)L.cout * WT * WT);
-      for (int hh = 0; hh < L.cout; ++hh)
-        for (int kj = 0; kj < WT; ++kj)
-          for (int qi = 0; qi < WT; ++qi) {
-            const int idx = ((qi >> 4) - (kj >> 4) + WS - 1) * (2 * WS - 1) + ((qi & 15) - (kj & 15) + WS - 1);
-            packed[((size_t)hh * WT + kj) * WT + qi] = host_f32[(size_t)idx * L.cout + hh];
-          }
-    } else if (L.kind == RPB_OCA) {
+    if (L.kind == RPB_OCA) {
       // relative_position_index_OCA is ((ky - qy) - 7) * 39 + ((kx - qx) - 7), -880 .. 640, and indexes a 1521-row table: the
       // negative values count from its end
       const int side = WS + WSE - 1, rows = side * side, off = WS - WSE + 1;
@@ -358,78 +331,34 @@ struct Hat : FamilyDefaults {
             if (idx < 0) idx += rows;
             packed[((size_t)hh * WKT + kj) * WT + qi] = host_f32[(size_t)idx * L.cout + hh];
           }
-    } else if (L.kind == LNORM) {
-      packed.assign(host_f32, host_f32 + L.cout);
     } else if (L.kind == GATE) {
       packed.assign(host_f32, host_f32 + (j == 1 ? (size_t)L.cout : (size_t)L.cout * L.cin));
     } else {
-      pack_gemm_tensor(L.kind == CONV, j == 1, L.cin, L.cout, host_f32, packed);
+      SwinFamily::pack(L, j, host_f32, packed);
     }
   }
 };
 
-struct Walker : WalkerBase<Hat> {
-  template <int GATHER, int EPI>
-  void launch_gemm(const HatGemmArgs& a, bool vec) {
-    if constexpr (EPI >= EPI_EXT) check(launch_swin_gemm<GATHER, EPI>(a, vec, st));
-    else check(launch_swin_gemm<GATHER, EPI>(static_cast<const GemmArgs&>(a), vec, st));
+struct Walker : SwinWalker<Hat> {
+  int shared = -1;   // the layer of the upsampling convolution, once it has run
+
+  // the GEMM kernels HAT adds, then the common ones
+  void launch(int kind, int epi, const HatGemmArgs& a, bool vec) {
+    if (kind == LINEAR && epi == EPI_HAB) check(launch_swin_gemm<ROWS, EPI_HAB>(a, vec, st));
+    else if (kind == CONV && epi == EPI_GELU) check(launch_swin_gemm<CONV3, EPI_GELU>(static_cast<const GemmArgs&>(a), vec, st));
+    else if (kind == CONV && epi == EPI_COLSUM) check(launch_swin_gemm<CONV3, EPI_COLSUM>(a, vec, st));
+    else SwinWalker::launch(kind, epi, a, vec);
   }
 
-  // out = epilogue(gather(in) . W + bias).  res: the EPI_RES / EPI_HAB addend.  r: the EPI_SHUFFLE factor.  cab, aux: EPI_HAB's
-  // CAB output and gate, EPI_COLSUM's partial sums (aux).
-  T gemm(const std::string& name, Kind kind, int epi, const T& in, int cout, int ob, const T* res = nullptr, int r = 1, const T* cab = nullptr,
-         int aux = -1) {
-    const int idx = layer(name, kind, in.C, cout);
-    T out{ob, in.H * r, in.W * r, cout / (r * r)};
-    if (mode == SIZE && epi != EPI_NCHW) touch(out);
-    if (!live()) return out;
-    HatGemmArgs a{};
-    gemm_args(a, idx, in, res, kind == CONV, in.C, cout, r);
-    a.out = epi == EPI_NCHW ? dst : buf[ob];
-    a.Hc = in.H;          // no crop: the reference returns the padded size
-    a.Wc = in.W;
-    a.slope = 0.01f;      // nn.LeakyReLU()'s default
-    a.range = cfg.img_range;
-    for (int c = 0; c < 3; ++c) a.mean[c] = cfg.mean[c];
-    a.colsum = epi == EPI_COLSUM ? buf[aux] : nullptr;
-    a.gate = epi == EPI_HAB ? buf[aux] : nullptr;
-    a.cab = cab ? buf[cab->buf] : nullptr;
-    a.conv_scale = cfg.conv_scale;
-    const bool vec = in.C % 4 == 0;
-    if (kind == LINEAR) {
-      if (epi == EPI_NONE) launch_gemm<ROWS, EPI_NONE>(a, vec);
-      else if (epi == EPI_GELU) launch_gemm<ROWS, EPI_GELU>(a, vec);
-      else if (epi == EPI_RES) launch_gemm<ROWS, EPI_RES>(a, vec);
-      else launch_gemm<ROWS, EPI_HAB>(a, vec);
-    } else {
-      if (epi == EPI_NONE) launch_gemm<CONV3, EPI_NONE>(a, vec);
-      else if (epi == EPI_GELU) launch_gemm<CONV3, EPI_GELU>(a, vec);
-      else if (epi == EPI_COLSUM) launch_gemm<CONV3, EPI_COLSUM>(a, vec);
-      else if (epi == EPI_LRELU) launch_gemm<CONV3, EPI_LRELU>(a, vec);
-      else if (epi == EPI_RES) launch_gemm<CONV3, EPI_RES>(a, vec);
-      else if (epi == EPI_SHUFFLE) launch_gemm<CONV3, EPI_SHUFFLE>(a, vec);
-      else launch_gemm<CONV3, EPI_NCHW>(a, vec);
-    }
-    return out;
-  }
-
-  using WalkerBase::norm;
-  T norm(const std::string& name, const T& in, int ob) { return norm(layer(name, LNORM, in.C, in.C), in, ob); }
-
-  // attention over the q | k | v rows of `qkv`, into `ob`
-  T attention(const std::string& name, bool oca, const T& qkv, int heads, int shift, int ob) {
-    const int idx = layer(name, oca ? RPB_OCA : RPB_SA, 0, heads);
-    const int C = qkv.C / 3;
-    T out{ob, qkv.H, qkv.W, C};
-    if (mode == SIZE) touch(out);
-    if (!live()) return out;
-    const int hd = C / heads;
-    const unsigned blocks = (unsigned)(N * (qkv.H / WS) * (qkv.W / WS) * heads * (WT / QB));
-    const float scale = 1.f / sqrtf((float)hd);
-    if (oca) hipLaunchKernelGGL(hat_attn_kernel<true>, dim3(blocks), dim3(256), 0, st, buf[qkv.buf], w[idx], buf[ob], qkv.H, qkv.W, C, heads, hd, 0, scale);
-    else hipLaunchKernelGGL(hat_attn_kernel<false>, dim3(blocks), dim3(256), 0, st, buf[qkv.buf], w[idx], buf[ob], qkv.H, qkv.W, C, heads, hd, shift, scale);
-    check(hipGetLastError());
-    return out;
+  // attention over the q | k | v rows of `qkv`, into buffer 4
+  T attention(const std::string& name, bool oca, const T& qkv, int heads, int shift) {
+    return SwinWalker::attention(name, oca ? RPB_OCA : RPB, qkv, heads, 4, [&](const float* bias, int hd) {
+      const int C = qkv.C / 3;
+      const unsigned blocks = (unsigned)(N * (qkv.H / WS) * (qkv.W / WS) * heads * (WT / QB));
+      const float scale = 1.f / sqrtf((float)hd);
+      if (oca) hipLaunchKernelGGL(hat_attn_kernel<true>, dim3(blocks), dim3(256), 0, st, buf[qkv.buf], bias, buf[4], qkv.H, qkv.W, C, heads, hd, 0, scale);
+      else hipLaunchKernelGGL(hat_attn_kernel<false>, dim3(blocks), dim3(256), 0, st, buf[qkv.buf], bias, buf[4], qkv.H, qkv.W, C, heads, hd, shift, scale);
+    });
   }
 
   // the gate of `cab` [N][H][W][C] from its partial column sums (buffer 8), into buffer 9
@@ -446,93 +375,53 @@ struct Walker : WalkerBase<Hat> {
     check(hipGetLastError());
   }
 
-  T mlp(const std::string& p, const T& y) {
-    T n2 = norm(p + ".norm2", y, 4);
-    T hid = gemm(p + ".mlp.fc1", LINEAR, EPI_GELU, n2, cfg.mlp_hidden, 5);
-    return gemm(p + ".mlp.fc2", LINEAR, EPI_RES, hid, y.C, 3, &y);
+  // RHAG i: depth HABs (the odd ones on the shifted window), then one OCAB.  Buffers beyond the common ones: 6 / 7 the CAB's
+  // hidden map and output, 8 its partial column sums, 9 the gate.
+  T group(int i, const std::string& lp, T cur) {
+    const std::string gp = lp + ".residual_group";
+    const int C = cfg.embed_dim, heads = cfg.num_heads[i], Hp = cur.H, Wp = cur.W;
+    for (int j = 0; j < cfg.depths[i]; ++j) {
+      const std::string bp = gp + ".blocks." + std::to_string(j), tp = lp + ".blocks." + std::to_string(j);
+      T n1 = norm(bp + ".norm1", cur, 4);
+      T qkv = gemm(bp + ".attn.qkv", LINEAR, EPI_NONE, n1, 3 * C, 5);
+      T mid = gemm(bp + ".conv_block.cab.0", CONV, EPI_GELU, n1, C / cfg.compress_ratio, 6);
+      HatGemmArgs sums{}, hab{};
+      sums.colsum = buf[8];
+      T cab = gemm(bp + ".conv_block.cab.2", CONV, EPI_COLSUM, mid, C, 7, nullptr, 1, sums);
+      gate(bp + ".conv_block.cab.3.attention", cab);
+      if (stops_at(tp + ".cab")) {
+        const size_t total = (size_t)N * Hp * Wp * C;
+        hipLaunchKernelGGL(hat_gate_mul_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, buf[7], buf[9], buf[6], Hp * Wp, C, total);
+        check(hipGetLastError());
+      }
+      if (mode == SIZE) touch(T{6, Hp, Wp, C});
+      tap(tp + ".cab", T{6, Hp, Wp, C});
+      T o = attention(bp + ".attn.relative_position_bias_table", false, qkv, heads, j % 2 ? WS / 2 : 0);
+      hab.gate = buf[9];
+      hab.cab = buf[cab.buf];
+      hab.conv_scale = cfg.conv_scale;
+      T y = gemm(bp + ".attn.proj", LINEAR, EPI_HAB, o, C, 3, &cur, 1, hab);
+      tap(tp + ".attn", y);
+      cur = mlp(bp, y);
+      tap(tp + ".mlp", cur);
+    }
+    const std::string op = gp + ".overlap_attn";
+    T n1 = norm(op + ".norm1", cur, 4);
+    T qkv = gemm(op + ".qkv", LINEAR, EPI_NONE, n1, 3 * C, 5);
+    T o = attention(op + ".relative_position_bias_table", true, qkv, heads, 0);
+    T y = gemm(op + ".proj", LINEAR, EPI_RES, o, C, 3, &cur);
+    tap(lp + ".ocab.attn", y);
+    cur = mlp(op, y);
+    tap(lp + ".ocab.mlp", cur);
+    return cur;
   }
 
-  // The whole network.  Buffers: 0 the packed input, 1 conv_first's output (kept for conv_after_body), 2 / 3 the tokens (a
-  // RHAG's input stays in 2 while its blocks work in 3), 4 a LayerNorm's or an attention's output, 5 qkv / the MLP's hidden rows,
-  // 6 / 7 the CAB's hidden map and output, 8 its partial column sums, 9 the gate; the reconstruction tail alternates between 4
-  // and 5.
-  void walk() {
-    const int C = cfg.embed_dim;
-    const int Hp = round_up(std::max(Hin, 1), WS), Wp = round_up(std::max(Win, 1), WS);
-    T x{0, Hp, Wp, 3};
-    if (mode == SIZE) touch(x);
-    if (live()) {
-      const size_t total = (size_t)N * Hp * Wp * 3;
-      hipLaunchKernelGGL(swin_input_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, img, buf[0], Hin, Win, Hp, Wp, cfg.mean[0],
-                         cfg.mean[1], cfg.mean[2], cfg.img_range, total);
-      check(hipGetLastError());
-    }
-    const T f = gemm("conv_first", CONV, EPI_NONE, x, C, 1);
-    tap("conv_first", f);
-    T a{2, Hp, Wp, C};
-    if (cfg.patch_norm) {
-      a = norm("patch_embed.norm", f, 2);
-    } else {
-      if (mode == SIZE) touch(a);
-      if (live()) check(hipMemcpyAsync(buf[2], buf[1], (size_t)N * Hp * Wp * C * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-    tap("patch_embed.norm", a);
-    for (int i = 0; i < cfg.n_layers; ++i) {
-      const std::string lp = "layers." + std::to_string(i), gp = lp + ".residual_group";
-      const int heads = cfg.num_heads[i];
-      T cur = a;
-      for (int j = 0; j < cfg.depths[i]; ++j) {
-        const std::string bp = gp + ".blocks." + std::to_string(j), tp = lp + ".blocks." + std::to_string(j);
-        T n1 = norm(bp + ".norm1", cur, 4);
-        T qkv = gemm(bp + ".attn.qkv", LINEAR, EPI_NONE, n1, 3 * C, 5);
-        T mid = gemm(bp + ".conv_block.cab.0", CONV, EPI_GELU, n1, C / cfg.compress_ratio, 6);
-        T cab = gemm(bp + ".conv_block.cab.2", CONV, EPI_COLSUM, mid, C, 7, nullptr, 1, nullptr, 8);
-        gate(bp + ".conv_block.cab.3.attention", cab);
-        if (stops_at(tp + ".cab")) {
-          const size_t total = (size_t)N * Hp * Wp * C;
-          hipLaunchKernelGGL(hat_gate_mul_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, buf[7], buf[9], buf[6], Hp * Wp, C, total);
-          check(hipGetLastError());
-        }
-        if (mode == SIZE) touch(T{6, Hp, Wp, C});
-        tap(tp + ".cab", T{6, Hp, Wp, C});
-        T o = attention(bp + ".attn.relative_position_bias_table", false, qkv, heads, j % 2 ? WS / 2 : 0, 4);
-        T y = gemm(bp + ".attn.proj", LINEAR, EPI_HAB, o, C, 3, &cur, 1, &cab, 9);
-        tap(tp + ".attn", y);
-        cur = mlp(bp, y);
-        tap(tp + ".mlp", cur);
-      }
-      {
-        const std::string op = gp + ".overlap_attn";
-        T n1 = norm(op + ".norm1", cur, 4);
-        T qkv = gemm(op + ".qkv", LINEAR, EPI_NONE, n1, 3 * C, 5);
-        T o = attention(op + ".relative_position_bias_table", true, qkv, heads, 0, 4);
-        T y = gemm(op + ".proj", LINEAR, EPI_RES, o, C, 3, &cur);
-        tap(lp + ".ocab.attn", y);
-        cur = mlp(op, y);
-        tap(lp + ".ocab.mlp", cur);
-      }
-      a = gemm(lp + ".conv", CONV, EPI_RES, cur, C, 2, &a);
-      tap(lp, a);
-    }
-    T n = norm("norm", a, 4);
-    T y = gemm("conv_after_body", CONV, EPI_RES, n, C, 3, &f);
-    tap("conv_after_body", y);
-    y = gemm("conv_before_upsample.0", CONV, EPI_LRELU, y, NUM_FEAT, 4);
-    int ob = 5;
-    if (cfg.upscale == 3) {
-      y = gemm("upsample.upsampling.0", CONV, EPI_SHUFFLE, y, 9 * NUM_FEAT, ob, nullptr, 3);
-      tap("upsample.0", y);
-    } else {
-      // Upsample repeats ONE list of modules: the same Conv2d(64, 256) runs in every stage
-      int shared = -1;
-      for (int k = 0; (1 << k) < cfg.upscale; ++k, ob = 9 - ob) {
-        reuse = shared;
-        y = gemm("upsample.upsampling.0", CONV, EPI_SHUFFLE, y, 4 * NUM_FEAT, ob, nullptr, 2);
-        if (k == 0) shared = li - 1;
-        tap("upsample." + std::to_string(k), y);
-      }
-    }
-    gemm("conv_last", CONV, EPI_NCHW, y, 3, 0);
+  // Upsample repeats ONE list of modules: the same Conv2d(64, 256) runs in every stage
+  T upsample(int k, const T& y, int r, int ob) {
+    reuse = k ? shared : -1;
+    const T out = gemm("upsample.upsampling.0", CONV, EPI_SHUFFLE, y, r * r * NUM_FEAT, ob, nullptr, r);
+    if (k == 0) shared = li - 1;
+    return out;
   }
 };
 
@@ -545,29 +434,18 @@ extern "C" {
 int fdsr_hat_create(const fdsr_hat_config* cfg, fdsr_hat* out) {
   if (!cfg || !out) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: null argument");
   const fdsr_hat_config& c = *cfg;
-  if (c.window_size != WS) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: window_size %d is not supported (16 only)", c.window_size);
+  const char* fn = "fdsr_hat_create";
+  int rc;
+  if ((rc = check_window(fn, c, WS))) return rc;
   if (c.overlap_win_size != WSE)
     return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: overlap window %d is not supported (24 only: overlap_ratio 0.5)", c.overlap_win_size);
-  if (c.n_layers < 1 || c.n_layers > FDSR_HAT_MAX_LAYERS)
-    return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: %d layers (1..%d)", c.n_layers, FDSR_HAT_MAX_LAYERS);
-  if (c.embed_dim < 1 || c.embed_dim > LN_MAX_C || c.mlp_hidden < 1)
-    return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: embed_dim %d (1..%d), mlp hidden width %d", c.embed_dim, LN_MAX_C, c.mlp_hidden);
+  if ((rc = check_widths(fn, c, FDSR_HAT_MAX_LAYERS))) return rc;
   if (c.compress_ratio < 1 || c.embed_dim % c.compress_ratio)
     return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: embed_dim %d is not divisible by compress_ratio %d", c.embed_dim, c.compress_ratio);
   if (c.squeeze_factor < 1 || c.embed_dim / c.squeeze_factor < 1)
     return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: squeeze_factor %d leaves no channel of embed_dim %d", c.squeeze_factor, c.embed_dim);
-  for (int i = 0; i < c.n_layers; ++i) {
-    if (c.depths[i] < 1 || c.num_heads[i] < 1 || c.embed_dim % c.num_heads[i])
-      return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: layer %d: depth %d, embed_dim %d over %d heads", i, c.depths[i], c.embed_dim,
-                  c.num_heads[i]);
-    if (c.embed_dim / c.num_heads[i] > HD)
-      return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: layer %d: head_dim %d is not supported (at most %d)", i, c.embed_dim / c.num_heads[i],
-                  HD);
-  }
-  if (c.upscale != 2 && c.upscale != 3 && c.upscale != 4 && c.upscale != 8)
-    return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: upscale %d is not supported (2, 3, 4, 8)", c.upscale);
-  if (!(c.img_range > 0.f)) return fail(nullptr, FDSR_E_INVALID, "fdsr_hat_create: img_range must be positive");
-  return engine_create<Hat>("fdsr_hat_create", c, out);
+  if ((rc = check_layers_and_output(fn, c))) return rc;
+  return engine_create<Hat>(fn, c, out);
 }
 
 void fdsr_hat_destroy(fdsr_hat s) { engine_destroy<Hat>(s); }

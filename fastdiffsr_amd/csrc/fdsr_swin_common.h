@@ -1,7 +1,8 @@
 // What the transformer families (fdsr_swinir.hip, fdsr_hat.hip, fdsr_transenet.hip) share: the token GEMM with its 3x3 implicit-GEMM gather,
-// LayerNorm over channels, the input kernel, the host packing of a Linear / Conv2d for the GEMM, and the small types of the
-// TABLE / SIZE / RUN walk.  Everything here sits in the anonymous namespace (internal linkage): each unit compiles the kernels
-// it launches.
+// LayerNorm over channels, the input kernel, the pieces their attention kernels are written from (the 32x32 accumulator's row
+// map, the score tile, a window token's pixel and region, the chunk sizes), the host packing of a Linear / Conv2d for the GEMM,
+// and the small types of the TABLE / SIZE / RUN walk.  Everything here sits in the anonymous namespace (internal linkage): each
+// unit compiles the kernels it launches.  The attention kernels themselves stay in their units: they share source, not code.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +24,10 @@ constexpr int BP = BN + 32;
 constexpr int HD = 32;                // head_dim padded to the MFMA tile
 constexpr int NUM_FEAT = 64;          // channels of the reconstruction tail
 constexpr int LN_MAX_C = 512;         // swin_ln_kernel keeps a row in 8 registers per lane
+// the attention kernels that stream their keys (hat_attn_kernel, transenet_attn_kernel)
+constexpr int QB = 32;                // queries of one workgroup: a score row pitch of 32 keeps the two k rows of an MFMA operand read 32 banks apart
+constexpr int KC = 128;               // keys per staged chunk
+constexpr int KP = KC + 32;           // pitch of the [d][key] chunk
 
 // PATCH8: row (b, ty, tx) is the 8 x 8 x Cin patch of an NHWC map, k = (p1 * 8 + p2) * Cin + c (fdsr_transenet.hip)
 enum Gather { ROWS = 0, CONV3 = 1, PATCH8 = 2 };
@@ -43,8 +48,44 @@ struct GemmArgs {
   float range, mean[3];   // EPI_NCHW: out = acc / img_range + mean
 };
 
-// An added epilogue (EPI >= EPI_EXT): the wave's two 32 x 32 accumulators of column `co` (< N), rows row0 + mb 32 + (i & 3) +
-// 8 (i >> 2) + 4 h.  Declared here, defined by the unit that instantiates it.
+// C/D map of v_mfma_f32_32x32x2_f32: element i of lane (r31 = lane & 31, h = lane >> 5) is column r31 of row (i & 3) + 8 (i >> 2) +
+// 4 h of the tile; acc_row adds the tile's first row
+__device__ __forceinline__ int acc_row(int row0, int i, int h) { return row0 + (i & 3) + 8 * (i >> 2) + 4 * h; }
+
+// St[j][i] = sum_d k[j][d] q[i][d], one 32 x 32 tile: sK [d][key] and sQ [d][query] in LDS with their pitches, key0 / query0 the
+// tile's first key and query column, r31 this lane's column of both; rows of the result are keys, so that stores run along the
+// queries
+template <int NK, int NQ>
+__device__ __forceinline__ f32x16 score_tile(const float (&sK)[NK], int pitchK, int key0, const float (&sQ)[NQ], int pitchQ, int query0, int r31, int h) {
+  f32x16 acc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+  for (int s = 0; s < HD / 2; ++s) {
+    const int kr = 2 * s + h;
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sK[kr * pitchK + key0 + r31], sQ[kr * pitchQ + query0 + r31], acc, 0, 0, 0);
+  }
+  return acc;
+}
+
+// Token tok = ty WS + tx of window (wy, wx) of the image rolled by -shift (torch.roll, then window_partition): its pixel
+// ((wy WS + ty + shift) mod H, (wx WS + tx + shift) mod W), and its region of the rolled image (three slices per axis: [0, H - WS),
+// [H - WS, H - shift), [H - shift, H)) as calculate_mask numbers them; tokens of different regions do not attend to each other
+template <int WS>
+__device__ __forceinline__ int window_pixel(int wy, int wx, int tok, int shift, int H, int W) {
+  static_assert((WS & (WS - 1)) == 0, "the window side is a power of two");
+  const int ys = wy * WS + (tok >> __builtin_ctz(WS)), xs = wx * WS + (tok & (WS - 1));
+  return ((ys + shift) % H) * W + (xs + shift) % W;
+}
+template <int WS>
+__device__ __forceinline__ int window_region(int wy, int wx, int tok, int shift, int H, int W) {
+  const int ys = wy * WS + (tok >> __builtin_ctz(WS)), xs = wx * WS + (tok & (WS - 1));
+  const int rh = ys < H - WS ? 0 : ys < H - shift ? 1 : 2, rw = xs < W - WS ? 0 : xs < W - shift ? 1 : 2;
+  return shift > 0 ? rh * 3 + rw : 0;
+}
+
+// An added epilogue (EPI >= EPI_EXT): the wave's two 32 x 32 accumulators of column `co` (< N), rows acc_row(row0 + mb 32, i, h).
+// Declared here, defined by the unit that instantiates it.
 template <int EPI, class ARGS>
 __device__ void gemm_epilogue_ext(const ARGS& p, const f32x16 (&acc)[2], int row0, int co, int h, float bias);
 
@@ -147,7 +188,7 @@ __global__ void __launch_bounds__(NT) swin_gemm_kernel(ARGS p) {
     }
   }
 
-  // epilogue: C/D map col = lane & 31 (column), row = (i & 3) + 8 (i >> 2) + 4 (lane >> 5)
+  // epilogue: column lane & 31, rows acc_row(., i, lane >> 5)
   const int co = n0 + wn * 32 + r31;
   if (co >= p.N) return;
   const float bias = p.bias[co];
@@ -160,7 +201,7 @@ __global__ void __launch_bounds__(NT) swin_gemm_kernel(ARGS p) {
   for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int om = m0 + wm * 64 + mb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+      const int om = acc_row(m0 + wm * 64 + mb * 32, i, h);
       if (om >= p.M) continue;
       float v = acc[mb][i] + bias;
       if (EPI == EPI_NONE) {

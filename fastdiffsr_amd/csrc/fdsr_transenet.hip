@@ -10,7 +10,8 @@
 //           self-attention as above; t += to_out(attention(to_q(LN t), to_k(LN m), to_v(LN m))), ONE LayerNorm; feed-forward
 //   y     = embedding_to_patch(t) stored straight to its NHWC pixels (EPI_SCATTER); span_conv1x1; tail; add_mean, NHWC -> NCHW
 //
-// The token GEMM, its 3x3 gather, LayerNorm and the weight packing are fdsr_swin_common.h's.  New here:
+// The token GEMM, its 3x3 gather, LayerNorm, the weight packing and the attention kernel's score tile, row map and chunk sizes
+// (QB, KC, KP) are fdsr_swin_common.h's.  New here:
 //   transenet_attn_kernel  dense attention of 6 heads of 32 over every token: one workgroup per (image, head, 32 queries), k and v
 //                          streamed through LDS in chunks of 128 keys in order, LDS independent of Nk.  Two passes that both
 //                          form S^T on the MFMA: the first keeps the row maxima, the second writes exp(s - max) of a chunk to
@@ -39,9 +40,6 @@ using namespace fdsr_int;
 namespace {
 
 constexpr int DIM = 512, HEADS = 6, INNER = HEADS * HD, MLP = 512, PS = 8;   // hard-coded inside the reference's __init__
-constexpr int QB = 32;                     // queries of one workgroup
-constexpr int KC = 128;                    // keys per staged chunk
-constexpr int KP = KC + 32;                // pitch of the [d][key] chunk
 
 enum TransEpi { EPI_RELU = EPI_EXT, EPI_GELUT = EPI_EXT + 1, EPI_SCATTER = EPI_EXT + 2 };
 
@@ -51,7 +49,7 @@ __device__ void gemm_epilogue_ext(const ARGS& p, const f32x16 (&acc)[2], int row
   for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int om = row0 + mb * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+      const int om = acc_row(row0 + mb * 32, i, h);
       if (om >= p.M) continue;
       const float v = acc[mb][i] + bias;
       if constexpr (EPI == EPI_RELU) {
@@ -137,18 +135,8 @@ __global__ void __launch_bounds__(256) transenet_attn_kernel(const float* __rest
       for (int e = 0; e < 4; ++e) sK[(d0 + 4 * e4 + e) * KP + jj] = kv[e];
     }
   };
-  // St[j][i] of this wave's 32 keys of the chunk: row j = 32 wave + (r & 3) + 8 (r >> 2) + 4 h, column i = r31
-  auto scores = [&]() {
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-    for (int s = 0; s < HD / 2; ++s) {
-      const int kr = 2 * s + h;
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(sK[kr * KP + wave * 32 + r31], sQt[kr * QB + r31], acc, 0, 0, 0);
-    }
-    return acc;
-  };
+  // St[j][i] of this wave's 32 keys of the chunk: row j = acc_row(32 wave, r, h), column i = r31
+  auto scores = [&]() { return score_tile(sK, KP, wave * 32, sQt, QB, 0, r31, h); };
 
   // pass 1: the row maxima
   float m = -INFINITY;
@@ -159,7 +147,7 @@ __global__ void __launch_bounds__(256) transenet_attn_kernel(const float* __rest
     const f32x16 acc = scores();
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int j = c0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int j = acc_row(c0 + wave * 32, r, h);
       if (j < Nk) m = fmaxf(m, acc[r]);
     }
   }
@@ -189,7 +177,7 @@ __global__ void __launch_bounds__(256) transenet_attn_kernel(const float* __rest
     const f32x16 acc = scores();
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int jl = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+      const int jl = acc_row(wave * 32, r, h);
       const float e = c0 + jl < Nk ? expf(acc[r] - m) : 0.f;
       lsum += e;
       sSt[jl * QB + r31] = e;
