@@ -26,7 +26,13 @@ import argparse
 import itertools
 import logging
 import os
+import queue
+import sys
+import threading
 import time
+from collections import namedtuple
+from concurrent.futures import ThreadPoolExecutor
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -218,6 +224,183 @@ class _Loader:
         return {key: (v if key == 'Index' else self.ops.to_device(v)) for key, v in staged.items()}
 
 
+def _prepare(opt, cond_from_lr, max_images, rank, world, diffusion, precision, rng, graph, step, epoch, fid_cache):
+    """What a pass works on: the val set and this rank's shard of it, the model under the val schedule in the asked-for mode, the
+    step / epoch it reports under, and how much of the FID reference the caller's cache already holds."""
+    val_opt = opt['datasets']['val']
+    dataset = create_dataset(val_opt, 'val', cond_from_lr=cond_from_lr)
+    n_total = len(dataset) if max_images is None else min(len(dataset), max_images)
+    lo, hi = shard_range(n_total, rank, world)
+    rres = int(val_opt['r_resolution'])
+    if diffusion is None:
+        diffusion = create_model(opt)                                                 # sr_mfe.py:60
+    diffusion.netG.precision = precision
+    if rng is not None:
+        diffusion.netG.rng = rng
+    if graph is not None:
+        diffusion.netG.graph = graph
+    diffusion.set_new_noise_schedule(opt['model']['beta_schedule']['val'], schedule_phase='val')   # sr_mfe.py:66-67, :131-132
+    fid_ref = fid_cache if fid_cache is not None else {}
+    if fid_ref.get('images') not in (None, n_total):
+        fid_ref.clear()                # another val set: its statistics do not apply
+    return SimpleNamespace(dataset=dataset, n_total=n_total, lo=lo, hi=hi, rres=rres, scale=rres // int(val_opt['l_resolution']),
+                           diffusion=diffusion, step=diffusion.begin_step if step is None else step,
+                           epoch=diffusion.begin_epoch if epoch is None else epoch, fid_ref=fid_ref,
+                           fid_sets=1 if 'hr' in fid_ref else 3)    # (HR, INF, SR) or, with the reference statistics cached, SR only
+
+
+# The two sides scored against HR (the bicubic image, the sampled image) and the per-image fields of each.  A pass's columns are
+# sides x fields (LPIPS, when on, is a fifth field): its rows, sums, `res` keys and log lines are all laid out from that list.
+METRICS = (('bic', 'sr'), ('mse', 'psnr', 'ssim', 'ergas'))
+# One batch's results on their way to the host: the pinned landing buffers of one slot (None: not asked for), valid once `event`
+# has passed; the finisher sets `done` when it no longer reads them.
+_Landed = namedtuple('_Landed', 'event idxs sr done sums hr inf lpips fid', defaults=(None,) * 5)
+
+
+def _save(img, path):
+    from PIL import Image
+    Image.fromarray(img).save(path)
+
+
+class _Finisher:
+    """The thread behind the sampling loop: waits for a batch's copies, turns them into the reference's per-image numbers and hands
+    the images to the pool to be written.  It owns its queue, the ring of landing slots and what it fills: per_image (index -> one
+    number per column, zeros under infer), per_fid (index -> [fid_sets, D] fp32 features), saves (the write futures) and errors."""
+
+    def __init__(self, pool, columns, save_images, infer, host_metrics, scale, result_path, current_step, fid_sets):
+        self.pool, self.columns, self.save_images, self.infer, self.host_metrics = pool, columns, save_images, infer, host_metrics
+        self.scale, self.result_path, self.current_step, self.fid_sets = scale, result_path, current_step, fid_sets
+        self.per_image, self.per_fid, self.saves, self.errors, self.jobs = {}, {}, [], [], queue.Queue()
+        self.slot_done = [None] * 3       # as many slots as HipOps.land keeps buffers per ring
+        self.thread = threading.Thread(target=self._work, daemon=True)
+        self.thread.start()
+
+    def slot(self, k):
+        """Batch k's landing slot, once the finisher is done with its previous contents (the sampling thread asks BEFORE it lands)."""
+        slot = k % len(self.slot_done)
+        if self.slot_done[slot] is not None:
+            self.slot_done[slot].wait()
+        return slot
+
+    def put(self, slot, job):
+        self.slot_done[slot] = job.done
+        self.jobs.put(job)
+
+    def close(self):
+        self.jobs.put(None)
+        self.thread.join()
+
+    def _work(self):
+        for job in iter(self.jobs.get, None):       # None: close()'s sentinel
+            try:
+                job.event.synchronize()
+                sr_np = job.sr.numpy()
+                fd = None if job.fid is None else job.fid.numpy().reshape(self.fid_sets, len(job.idxs), -1)
+                for j, index in enumerate(job.idxs):
+                    if fd is not None:
+                        self.per_fid[index] = fd[:, j].copy()
+                    if self.save_images:                                             # sr_mfe.py:274 counts from 1
+                        name = '{}_{}_sr.{}'.format(self.current_step, index + 1, 'png' if self.infer else 'tif')
+                        self.saves.append(self.pool.submit(_save, sr_np[j].copy(), '{}/{}'.format(self.result_path, name)))
+                    self.per_image[index] = [0.0] * len(self.columns) if self.infer else self._row(job, j, sr_np[j])
+            except Exception as e:       # surfaced by run() after the drain
+                self.errors.append(e)
+            finally:
+                job.done.set()           # this slot's landing buffers may be refilled
+
+    def _row(self, job, j, sr):
+        """Image j of the batch as one number per column: from the device's sums, or (host_metrics) from the landed images."""
+        if self.host_metrics:
+            hr = job.hr.numpy()[j]
+            m = {side: {'mse': M.compare_mse(t, hr), 'psnr': M.compare_psnr(t, hr), 'ssim': M.compare_ssim(t, hr),
+                        'ergas': M.calculate_ergas(t, hr, scale=self.scale)}
+                 for side, t in zip(METRICS[0], (job.inf.numpy()[j], sr))}
+        else:
+            m = {side: M.metrics_from_sums(job.sums.numpy()[s, j], sr.shape, self.scale) for s, side in enumerate(METRICS[0])}
+        if job.lpips is not None:
+            for s, side in enumerate(METRICS[0]):
+                m[side]['lpips'] = float(job.lpips.numpy()[s, j, 0])                # sr_mfe.py:324, :345
+        return [m[side][f] for side, f in self.columns]
+
+
+def _score(ops, slot, hr_u8, inf_u8, sr_u8, host_metrics, lpips, fid, fid_sets):
+    """One batch's metric work in stream order: the sums (host_metrics: the images), LPIPS, FID features, each landed into `slot`."""
+    if host_metrics:
+        out = dict(hr=ops.land('hr', slot, hr_u8), inf=ops.land('inf', slot, inf_u8))
+    else:
+        sums = ops.new_sums(len(sr_u8))
+        ops.metric_sums(inf_u8, hr_u8, out=sums[0])
+        ops.metric_sums(sr_u8, hr_u8, out=sums[1])
+        out = dict(sums=ops.land('sums', slot, sums))
+    if lpips is not None:
+        out['lpips'] = ops.land('lpips', slot, ops.lpips(lpips, hr_u8, inf_u8, sr_u8))
+    if fid is not None:
+        out['fid'] = ops.land('fid', slot, ops.fid_features(fid, (hr_u8, inf_u8, sr_u8) if fid_sets == 3 else (sr_u8,)))
+    return out
+
+
+def _sample_batches(diffusion, loader, ops, finisher, clock, cond_from_lr, rres, infer, host_metrics, lpips, fid, fid_sets):
+    """The sampling thread's loop -> seconds inside the sampling calls; clock['stage'] / ['post'] take its host seconds around them."""
+    def stage(k):
+        """Batch k on the device as the model tensors: issued BEFORE the previous batch is sampled, so the bytes are
+        there when its loop ends (the copies and the two small kernels sit in front of that loop on the stream)."""
+        if k >= len(loader):
+            return None
+        ts = time.perf_counter()
+        raw = loader.get(k)
+        idxs = raw.pop('Index')
+        data = {key: ops.to_tensor(v) for key, v in raw.items()}
+        if cond_from_lr:
+            data['SR'] = ops.lr_to_sr(raw['LR'], rres, rres)
+        clock['stage'] += time.perf_counter() - ts
+        return idxs, data
+
+    t_sample = 0.0
+    loader.prefetch(1)
+    staged = stage(0)
+    for k in range(len(loader)):
+        idxs, data = staged
+        diffusion.feed_data(data)
+        staged = stage(k + 1)
+        loader.prefetch(k + 1 + loader.depth)
+        ops.sync()
+        t0 = time.time()
+        diffusion.test(continous=False)
+        ops.sync()
+        t_sample += time.time() - t0
+        logger.info('inference time (s): {:.4f} for {} image(s)'.format(time.time() - t0, len(idxs)))   # sr_mfe.py:279-284
+        tp = time.perf_counter()
+        sr_batch = diffusion.SR
+        if sr_batch.dim() == 3:       # the ddpm / tesr siblings return ret_img[-1]: one image (their own convention)
+            if len(idxs) != 1:
+                raise ValueError("which_model_G in ('ddpm', 'tesr') returns one image per call: use --batch 1")
+            sr_batch = sr_batch[None]
+        sr_u8 = ops.tensor2img_batch(sr_batch)                                    # Metrics.tensor2img, on the device
+        slot = finisher.slot(k)
+        sr_host = ops.land('sr', slot, sr_u8)
+        scores = {}
+        if not infer:
+            hr_u8 = ops.tensor2img_batch(diffusion.data['HR'])
+            inf_u8 = ops.tensor2img_batch(diffusion.data['SR'])                   # the bicubic image ('INF')
+            scores = _score(ops, slot, hr_u8, inf_u8, sr_u8, host_metrics, lpips, fid, fid_sets)
+        finisher.put(slot, _Landed(ops.mark(), idxs, sr_host, threading.Event(), **scores))
+        clock['post'] += time.perf_counter() - tp
+    return t_sample
+
+
+def _reduce(per_image, columns, world):
+    """-> (images, {column name: average}) over all ranks; summed in index order, so the averages do not depend on the batch size."""
+    sums = np.zeros(len(columns) + 1, dtype=np.float64)      # one sum per column, then the image count
+    for index in sorted(per_image):
+        sums += np.array(per_image[index] + [1.0])
+    if world > 1:
+        import torch.distributed as dist
+        t = torch.from_numpy(sums).cuda() if dist.get_backend() == 'nccl' else torch.from_numpy(sums)
+        dist.all_reduce(t)
+        sums = t.cpu().numpy()
+    return int(sums[-1]), {s + '_' + f: v for (s, f), v in zip(columns, sums[:-1] / max(sums[-1], 1.0))}
+
+
 def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_images=None, rank=0, world=1,
         save_images=True, log=print, infer=False, diffusion=None, step=None, epoch=None, workers=None, rng=None, graph=None,
         host_metrics=False, ops=None, lpips=None, fid=None, fid_cache=None):
@@ -239,217 +422,64 @@ def run(opt, batch=1, cond_from_lr=False, precision='f16x3', results=None, max_i
     HR), sr_fid = FID(SR, HR) are computed there in fp64 (FID.py's order: generated set first) and broadcast.
     fid_cache: a dict the caller keeps between passes over the same val set (the training loop): the HR / INF statistics and
     bic_fid are computed by the first pass and reused, later passes compute SR features only."""
-    import queue
-    import sys
-    import threading
-    from concurrent.futures import ThreadPoolExecutor
     t_run0 = time.perf_counter()
     clock = {'stage': 0.0, 'post': 0.0}      # host seconds of this thread outside the sampling calls (returned in res['host_seconds'])
-    val_opt = opt['datasets']['val']
-    dataset = create_dataset(val_opt, 'val', cond_from_lr=cond_from_lr)
-    n_total = len(dataset) if max_images is None else min(len(dataset), max_images)
-    lo, hi = shard_range(n_total, rank, world)
-    scale = int(val_opt['r_resolution']) // int(val_opt['l_resolution'])
-    if diffusion is None:
-        diffusion = create_model(opt)                                                 # sr_mfe.py:60
-    diffusion.netG.precision = precision
-    if rng is not None:
-        diffusion.netG.rng = rng
-    if graph is not None:
-        diffusion.netG.graph = graph
-    diffusion.set_new_noise_schedule(opt['model']['beta_schedule']['val'], schedule_phase='val')   # sr_mfe.py:66-67, :131-132
-    current_step = diffusion.begin_step if step is None else step
-    current_epoch = diffusion.begin_epoch if epoch is None else epoch
+    lpips, fid = (None, None) if infer else (lpips, fid)         # infer.py scores nothing
+    p = _prepare(opt, cond_from_lr, max_images, rank, world, diffusion, precision, rng, graph, step, epoch, fid_cache)
     result_path = results or (opt.get('path') or {}).get('results') or 'results'
     if save_images:
         os.makedirs(result_path, exist_ok=True)
     if ops is None:
-        ops = HipOps(diffusion.device)
-    rres = int(val_opt['r_resolution'])
-    use_lpips = lpips is not None and not infer
-    n_metric = 10 if use_lpips else 8
-    use_fid = fid is not None and not infer
-    fid_ref = fid_cache if fid_cache is not None else {}
-    if fid_ref.get('images') not in (None, n_total):
-        fid_ref.clear()                # another val set: its statistics do not apply
-    fid_sets = 1 if 'hr' in fid_ref else 3          # (HR, INF, SR) or, with the reference statistics cached, SR only
-    per_fid = {}                       # index -> [fid_sets, D] fp32 features
-    per_image = {}                     # index -> 8 numbers (bic mse/psnr/ssim/ergas, sr mse/psnr/ssim/ergas[, bic_lpips, sr_lpips]); summed in index order
-    t_sample = 0.0
+        ops = HipOps(p.diffusion.device)
+    columns = [(side, f) for side in METRICS[0] for f in METRICS[1] + (('lpips',) if lpips is not None else ())]
     # loader / writer threads of THIS rank: its share of the cores the job may use (affinity, cgroup quota, ranks on the host)
     n_workers = workers if workers else host_threads_per_rank(cap=8, floor=2)
     pool = ThreadPoolExecutor(max_workers=n_workers)
-    jobs = queue.Queue()
-    errors = []
-    saves = []
-
-    def _save(img, path):
-        from PIL import Image
-        Image.fromarray(img).save(path)
-
-    def _finish():
-        while True:
-            job = jobs.get()
-            if job is None:
-                return
-            try:
-                ev, idxs, sr_host, sums_host, hr_host, inf_host, lp_host, fd_host, _ = job
-                ev.synchronize()
-                sr_np = sr_host.numpy()
-                if fd_host is not None:
-                    fd = fd_host.numpy().reshape(fid_sets, len(idxs), -1)
-                    for j, index in enumerate(idxs):
-                        per_fid[index] = fd[:, j].copy()
-                for j, index in enumerate(idxs):
-                    idx = index + 1                                                   # sr_mfe.py:274 counts from 1
-                    if save_images:
-                        path = '{}/{}_{}_sr.{}'.format(result_path, current_step, idx, 'png' if infer else 'tif')
-                        saves.append(pool.submit(_save, sr_np[j].copy(), path))
-                    if infer:
-                        per_image[index] = None
-                    elif host_metrics:
-                        h_, f_, s_ = hr_host.numpy()[j], inf_host.numpy()[j], sr_np[j]
-                        per_image[index] = [M.compare_mse(f_, h_), M.compare_psnr(f_, h_), M.compare_ssim(f_, h_),
-                                            M.calculate_ergas(f_, h_, scale=scale),
-                                            M.compare_mse(s_, h_), M.compare_psnr(s_, h_), M.compare_ssim(s_, h_),
-                                            M.calculate_ergas(s_, h_, scale=scale)]
-                    else:
-                        sm = sums_host.numpy()
-                        b_ = M.metrics_from_sums(sm[0, j], sr_np[j].shape, scale)
-                        s_ = M.metrics_from_sums(sm[1, j], sr_np[j].shape, scale)
-                        per_image[index] = [b_['mse'], b_['psnr'], b_['ssim'], b_['ergas'], s_['mse'], s_['psnr'], s_['ssim'], s_['ergas']]
-                    if lp_host is not None:
-                        lp = lp_host.numpy()
-                        per_image[index] += [float(lp[0, j, 0]), float(lp[1, j, 0])]     # sr_mfe.py:324, :345
-            except Exception as e:       # surfaced by run() after the loop
-                errors.append(e)
-            finally:
-                job[-1].set()            # this slot's landing buffers may be refilled
-
-    finisher = threading.Thread(target=_finish, daemon=True)
-    finisher.start()
+    finisher = _Finisher(pool, columns, save_images, infer, host_metrics, p.scale, result_path, p.step, p.fid_sets)
     # the sampling thread hands the GIL over around every launch / synchronisation; with Python's default 5 ms switch interval each
     # hand-back can cost it up to 5 ms while a loader / writer thread is in a Python section: ask for 0.2 ms while the loop runs
     old_switch = sys.getswitchinterval()
     sys.setswitchinterval(2e-4)
     clock['setup'] = time.perf_counter() - t_run0
     loader = None
-    slot_free = [None] * 3
     try:
-        loader = _Loader(dataset, lo, hi, batch, pool, ops)
-
-        def stage(k):
-            """Batch k on the device as the model tensors: issued BEFORE the previous batch is sampled, so the bytes are
-            there when its loop ends (the copies and the two small kernels sit in front of that loop on the stream)."""
-            if k >= len(loader):
-                return None
-            ts = time.perf_counter()
-            raw = loader.get(k)
-            idxs = raw.pop('Index')
-            data = {key: ops.to_tensor(v) for key, v in raw.items()}
-            if cond_from_lr:
-                data['SR'] = ops.lr_to_sr(raw['LR'], rres, rres)
-            clock['stage'] += time.perf_counter() - ts
-            return idxs, data
-
-        loader.prefetch(1)
-        staged = stage(0)
-        for k in range(len(loader)):
-            idxs, data = staged
-            diffusion.feed_data(data)
-            staged = stage(k + 1)
-            loader.prefetch(k + 1 + loader.depth)
-            ops.sync()
-            t0 = time.time()
-            diffusion.test(continous=False)
-            ops.sync()
-            t_sample += time.time() - t0
-            logger.info('inference time (s): {:.4f} for {} image(s)'.format(time.time() - t0, len(idxs)))   # sr_mfe.py:279-284
-            tp = time.perf_counter()
-            sr_batch = diffusion.SR
-            if sr_batch.dim() == 3:       # the ddpm / tesr siblings return ret_img[-1]: one image (their own convention)
-                if len(idxs) != 1:
-                    raise ValueError("which_model_G in ('ddpm', 'tesr') returns one image per call: use --batch 1")
-                sr_batch = sr_batch[None]
-            b = len(idxs)
-            sr_u8 = ops.tensor2img_batch(sr_batch)                                    # Metrics.tensor2img, on the device
-            slot = k % 3
-            if slot_free[slot] is not None:
-                slot_free[slot].wait()           # the finisher is done with this slot's previous contents
-            sr_host = ops.land('sr', slot, sr_u8)
-            sums_host = hr_host = inf_host = lp_host = fd_host = None
-            if not infer:
-                hr_u8 = ops.tensor2img_batch(diffusion.data['HR'])
-                inf_u8 = ops.tensor2img_batch(diffusion.data['SR'])                   # the bicubic image ('INF')
-                if host_metrics:
-                    hr_host, inf_host = ops.land('hr', slot, hr_u8), ops.land('inf', slot, inf_u8)
-                else:
-                    sums = ops.new_sums(b)
-                    ops.metric_sums(inf_u8, hr_u8, out=sums[0])
-                    ops.metric_sums(sr_u8, hr_u8, out=sums[1])
-                    sums_host = ops.land('sums', slot, sums)
-                if use_lpips:
-                    lp_host = ops.land('lpips', slot, ops.lpips(lpips, hr_u8, inf_u8, sr_u8))
-                if use_fid:
-                    fd_host = ops.land('fid', slot, ops.fid_features(fid, (hr_u8, inf_u8, sr_u8) if fid_sets == 3 else (sr_u8,)))
-            done = threading.Event()
-            slot_free[slot] = done
-            jobs.put((ops.mark(), idxs, sr_host, sums_host, hr_host, inf_host, lp_host, fd_host, done))
-            clock['post'] += time.perf_counter() - tp
+        loader = _Loader(p.dataset, p.lo, p.hi, batch, pool, ops)
+        t_sample = _sample_batches(p.diffusion, loader, ops, finisher, clock, cond_from_lr, p.rres, infer, host_metrics,
+                                   lpips, fid, p.fid_sets)
     finally:
         tt = time.perf_counter()
-        jobs.put(None)
-        finisher.join()
+        finisher.close()               # the drain, also of an aborted pass: the finisher first (it still queues writes)
         if loader is not None:
             loader.close()
-        for f in saves:
+        for f in finisher.saves:
             f.result()
         pool.shutdown(wait=True)
         sys.setswitchinterval(old_switch)
         clock['tail'] = time.perf_counter() - tt
-    if errors:
-        raise errors[0]
-    sums = np.zeros(n_metric + 1, dtype=np.float64)    # bic mse/psnr/ssim/ergas, sr mse/psnr/ssim/ergas[, bic/sr lpips], count
-    for index in sorted(per_image):
-        if per_image[index] is not None:
-            sums[:n_metric] += np.array(per_image[index])
-        sums[n_metric] += 1.0
-    if world > 1:
-        import torch.distributed as dist
-        t = torch.from_numpy(sums).cuda() if dist.get_backend() == 'nccl' else torch.from_numpy(sums)
-        dist.all_reduce(t)
-        sums = t.cpu().numpy()
-    n = max(sums[n_metric], 1.0)
-    avg = sums[:n_metric] / n
-    res = dict(images=int(sums[n_metric]), bic_mse=avg[0], bic_psnr=avg[1], bic_ssim=avg[2], bic_ergas=avg[3],
-               sr_mse=avg[4], sr_psnr=avg[5], sr_ssim=avg[6], sr_ergas=avg[7],
-               sample_seconds_this_rank=t_sample, result_path=result_path,
+    if finisher.errors:
+        raise finisher.errors[0]
+    images, averages = _reduce(finisher.per_image, columns, world)
+    res = dict(images=images, **averages, sample_seconds_this_rank=t_sample, result_path=result_path,
                host_seconds=dict(clock, total=time.perf_counter() - t_run0, workers=n_workers))
-    if use_lpips:
-        res.update(bic_lpips=avg[8], sr_lpips=avg[9])
-    if use_fid:
+    if fid is not None:
         tf = time.perf_counter()
-        res.update(_fid_scores(per_fid, fid_ref, n_total, fid_sets, rank, world))
+        res.update(_fid_scores(finisher.per_fid, p.fid_ref, p.n_total, p.fid_sets, rank, world))
         res['host_seconds']['fid_statistics'] = time.perf_counter() - tf      # gather + fp64 statistics + sqrtm (rank 0)
-    tail_b = (', bic_lpips: {:.5e}'.format(avg[8]) if use_lpips else '') + (', bic_fid: {:.5e}'.format(res['bic_fid']) if use_fid else '')
-    tail_s = (', sr_lpips: {:.5e}'.format(avg[9]) if use_lpips else '') + (', sr_fid: {:.5e}'.format(res['sr_fid']) if use_fid else '')
     if rank == 0 and infer:
-        log('inference: {} images, {:.4f} s per image on this rank (batch {})'.format(int(sums[n_metric]), t_sample / max(hi - lo, 1), batch))
-    elif rank == 0:
-        # sr_mfe.py:375-378 (and :230-235): LPIPS last on each line, then FID (FID.py) when asked for
-        log('<epoch:{:3d}, iter:{:8,d}> bic_mse: {:.5e}, bic_psnr: {:.5e}, bic_ssim: {:.5e}, bic_ergas: {:.5e}'.format(
-            current_epoch, current_step, *avg[:4]) + tail_b)
-        log('<epoch:{:3d}, iter:{:8,d}> sr_mse: {:.5e}, sr_psnr: {:.5e}, sr_ssim: {:.5e}, sr_ergas: {:.5e}'.format(
-            current_epoch, current_step, *avg[4:8]) + tail_s)
+        log('inference: {} images, {:.4f} s per image on this rank (batch {})'.format(images, t_sample / max(p.hi - p.lo, 1), batch))
+    elif rank == 0:       # sr_mfe.py:375-378 (and :230-235): one line per side, LPIPS last on it, then FID (FID.py) when asked for
+        for side in METRICS[0]:
+            names = [s + '_' + f for s, f in columns if s == side] + ([side + '_fid'] if fid is not None else [])
+            log('<epoch:{:3d}, iter:{:8,d}> '.format(p.epoch, p.step) + ', '.join('{}: {:.5e}'.format(n, res[n]) for n in names))
     return res
 
 
 def _fid_scores(per_fid, fid_ref, n_total, fid_sets, rank, world):
     """bic_fid / sr_fid of one pass: this rank's per-image features are gathered to rank 0, put in index order (so the value does
     not depend on the rank count or the batch), turned into fp64 statistics there and the two distances broadcast."""
+    import torch.distributed as dist
     local = {i: per_fid[i] for i in sorted(per_fid)}
     if world > 1:
-        import torch.distributed as dist
         parts = [None] * world if rank == 0 else None
         dist.gather_object(local, parts, dst=0)
         if rank == 0:
@@ -465,7 +495,6 @@ def _fid_scores(per_fid, fid_ref, n_total, fid_sets, rank, world):
         sr = M.activation_statistics(feats[:, -1])
         out = [dict(bic_fid=fid_ref['bic_fid'], sr_fid=M.frechet_distance(*sr, *fid_ref['hr']))]
     if world > 1:
-        import torch.distributed as dist
         dist.broadcast_object_list(out, src=0)
         if rank != 0 and fid_sets == 3:
             fid_ref.update(images=n_total, hr=None, bic_fid=out[0]['bic_fid'])    # later passes: SR features only, as on rank 0
