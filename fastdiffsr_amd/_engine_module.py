@@ -1,4 +1,4 @@
-"""What the comparator modules (swinir.SwinIR, hat.HAT, transenet.TransENet) share: an nn.Module over one engine handle of
+"""What the comparator modules (swinir.SwinIR, hat.HAT, transenet.TransENet, hsenet.HSENet) share: an nn.Module over one engine handle of
 include/fdsr.h's fdsr_<family>_* functions.  The tensors live under p<i> (dotted names cannot be registered on an nn.Module)
 and state_dict / load_state_dict speak the reference's keys.
 

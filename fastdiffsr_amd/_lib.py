@@ -68,6 +68,13 @@ class FdsrTransenetConfig(C.Structure):
     _fields_ = [('n_feats', C.c_int32), ('scale', C.c_int32), ('n_colors', C.c_int32), ('en_depth', C.c_int32), ('de_depth', C.c_int32)]
 
 
+FDSR_HSENET_GRAPH = 1
+
+
+class FdsrHsenetConfig(C.Structure):
+    _fields_ = [('n_feats', C.c_int32), ('scale', C.c_int32), ('n_colors', C.c_int32), ('n_basic_modules', C.c_int32)]
+
+
 class FdsrError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f'libfdsr_hip error {code}: {msg}')
@@ -175,6 +182,14 @@ SYMBOLS = {
     'fdsr_transenet_debug_tensor': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                               C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_void_p]),
     'fdsr_transenet_destroy': (None, [C.c_void_p]),
+    'fdsr_hsenet_create': (C.c_int, [C.POINTER(FdsrHsenetConfig), C.POINTER(C.c_void_p)]),
+    'fdsr_hsenet_load': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int64), C.c_int]),
+    'fdsr_hsenet_workspace_bytes': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    'fdsr_hsenet_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                      C.c_int]),
+    'fdsr_hsenet_debug_tensor': (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                           C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'fdsr_hsenet_destroy': (None, [C.c_void_p]),
     'fdsr_nafnet_create': (C.c_int, [C.POINTER(FdsrNafnetConfig), C.POINTER(C.c_void_p)]),
     'fdsr_nafnet_num_weights': (C.c_int, [C.c_void_p]),
     'fdsr_nafnet_weight_info': (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int)]),

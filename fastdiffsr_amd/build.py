@@ -13,7 +13,7 @@ SOURCES = [('fdsr_kernels.hip', ['-O3']), ('fdsr_conv_h.hip', ['-O3', '-fno-slp-
            ('fdsr_conv_up2.hip', ['-O3', '-fno-slp-vectorize']),
            ('fdsr_conv_k32.hip', ['-O3', '-fno-slp-vectorize']), ('fdsr_conv_strip.hip', ['-O3', '-fno-slp-vectorize']),
            ('fdsr_conv_strip.hip', ['-O3', '-fno-slp-vectorize', '-DSTRIP_PART=2']), ('fdsr_conv_strip.hip', ['-O3', '-fno-slp-vectorize', '-DSTRIP_PART=3']), ('fdsr_conv_tail.hip', ['-O3', '-fno-slp-vectorize']),
-           ('fdsr_val.hip', ['-O3']), ('fdsr_scene.hip', ['-O3']), ('fdsr_lpips.hip', ['-O3']), ('fdsr_fid.hip', ['-O3']), ('fdsr_swinir.hip', ['-O3']), ('fdsr_hat.hip', ['-O3']), ('fdsr_transenet.hip', ['-O3']), ('fdsr_nafnet.hip', ['-O3']), ('fdsr_train.hip', ['-O3']), ('fdsr_wgrad.hip', ['-O3']), ('fdsr_engine.cpp', ['-O2']), ('fdsr_sample.cpp', ['-O2']), ('fdsr_plan.cpp', ['-O2']), ('fdsr_forms.cpp', ['-O2']), ('fdsr_train.cpp', ['-O2'])]
+           ('fdsr_val.hip', ['-O3']), ('fdsr_scene.hip', ['-O3']), ('fdsr_lpips.hip', ['-O3']), ('fdsr_fid.hip', ['-O3']), ('fdsr_swinir.hip', ['-O3']), ('fdsr_hat.hip', ['-O3']), ('fdsr_transenet.hip', ['-O3']), ('fdsr_hsenet.hip', ['-O3']), ('fdsr_nafnet.hip', ['-O3']), ('fdsr_train.hip', ['-O3']), ('fdsr_wgrad.hip', ['-O3']), ('fdsr_engine.cpp', ['-O2']), ('fdsr_sample.cpp', ['-O2']), ('fdsr_plan.cpp', ['-O2']), ('fdsr_forms.cpp', ['-O2']), ('fdsr_train.cpp', ['-O2'])]
 COMMON = ['--offload-arch=gfx950', '-std=c++17', '-fPIC', '-Wno-unused-result']
 
 

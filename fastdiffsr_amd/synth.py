@@ -223,6 +223,37 @@ def synth_transenet(cfg, seed: int = 0) -> "OrderedDict[str, np.ndarray]":
     return out
 
 
+HSENET_QK_GAIN = 2.0       # synth_hsenet's default (load_synthetic, the timing tool): softmax rows of the ten-module network neither flat nor one-hot
+
+
+def synth_hsenet(cfg, seed: int = 0, qk_gain: float = HSENET_QK_GAIN) -> "OrderedDict[str, np.ndarray]":
+    """Synthetic weights for HSENet, keyed and ordered as hsenet.arch.state_schema(cfg), every tensor from its own key.  The
+    3x3 convolutions are N(0, 1 / fan_in) (each is followed by a ReLU, and every module adds to a residual stream that grows
+    through the network), head.0 N(0, 4 / fan_in), g N(0, 1 / fan_in), AB.1 N(0, 4 / fan_in) (gate logits of a few units);
+    biases 0.05 N.  The reference initialises every W of a non-local block to ZERO, which makes the block the identity; here W
+    is N(0, 1 / fan_in).  The logits theta(x)^T phi(x) are unscaled: under plain fan-in weights the softmax over hundreds of
+    pixels is flat and the attention a mean, so theta and phi are N(0, 1 / fan_in) times qk_gain (the logits grow with its
+    square); tests fix a gain per configuration from a probe of the fp64 restatement (tests/hsenet_restatement.py).  sub_mean
+    and add_mean are the reference's constants: the identity and -/+ the UCMerced mean (std 1)."""
+    from .hsenet.arch import RGB_MEAN as HS_MEAN, state_schema as hs_schema
+    out = OrderedDict()
+    for k, shape in hs_schema(cfg).items():
+        x = _rng('hsenet:' + k, seed).standard_normal(size=shape, dtype=np.float64)
+        fan_in = int(np.prod(shape[1:])) if len(shape) > 1 else 1
+        mod = k.rsplit('.', 1)[0]
+        if mod in ('sub_mean', 'add_mean'):
+            sign = -1.0 if mod == 'sub_mean' else 1.0
+            x = np.eye(3).reshape(3, 3, 1, 1) if k.endswith('.weight') else sign * np.asarray(HS_MEAN)
+        elif k.endswith('.bias'):
+            x *= 0.05
+        else:
+            last = mod.split('.')[-1]
+            gain = 4.0 if mod == 'head.0' or mod.endswith('.AB.1') else 1.0
+            x *= np.sqrt(gain / fan_in) * (qk_gain if last in ('theta', 'phi') else 1.0)
+        out[k] = x.astype(np.float32)
+    return out
+
+
 def synth_nafnet(seed: int = 0, width: int = 16, enc_blk_nums=(2, 1, 1, 1), middle_blk_num: int = 1, dec_blk_nums=(1, 1, 1, 1),
                  img_channel: int = 3) -> "OrderedDict[str, np.ndarray]":
     """Synthetic weights for EDiffSR's ConditionalNAFNet, keyed and ordered as ediffsr.arch.param_schema.  The reference

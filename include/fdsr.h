@@ -464,6 +464,44 @@ int fdsr_transenet_debug_tensor(fdsr_transenet s, const char* name, const float*
                                 size_t capacity_floats, int* dims3, void* workspace, size_t workspace_bytes, void* hip_stream);
 void fdsr_transenet_destroy(fdsr_transenet s);
 
+/* -- HSENet (MSI_SR_model/model/hsenet.py: HSENET) inference ---------------------------------------------------------------------
+ * An object of its own, in the shape of fdsr_transenet.  Exact fp32, NHWC inside, on the GEMM kernels of the SwinIR family (every
+ * 3x3 of the body with its ReLU, the gate m * sigmoid(.) as an epilogue) plus: the non-local block as one attention kernel over
+ * every pixel of the image (one head of n_feats / 2 channels, unscaled logits, exact row maxima; self form and the cross form of
+ * AdjustedNonLocalBlock), one workgroup per (image, 32 queries), k and v streamed in chunks of 128 keys whatever their number, no
+ * N x N tensor in memory; the two bilinear resamplings of the HSEM (align_corners=False); sub_mean and add_mean as general 3x3
+ * matrices with bias.  Reruns are bitwise identical and an image's result depends neither on B nor on its position in the batch.
+ *   fdsr_hsenet_create           validates the configuration without touching the device.  FDSR_E_INVALID outside the envelope:
+ *                                n_colors 3; n_feats 16, 32 or 64; scale 2, 3, 4 or 8; n_basic_modules >= 1.
+ *   fdsr_hsenet_load             a host fp32 tensor under the reference's state_dict name and shape (sub_mean.weight [3][3][1][1],
+ *                                body_modulist.0.body.0.NonLocal_base.theta.weight [n_feats / 2][n_feats][1][1], ...).  Any other
+ *                                name or shape: FDSR_E_KEY.  Host-synchronous; drops every captured graph.
+ *   fdsr_hsenet_workspace_bytes  for a batch of height x width inputs.  FDSR_E_INVALID unless both sides are at least 2 (the
+ *                                half-scale branch needs a pixel).
+ *   fdsr_hsenet_forward          x_nchw [B][3][H][W] fp32 -> out_nchw [B][3][H scale][W scale].  flags: FDSR_HSENET_GRAPH replays
+ *                                the forward as one captured, linear hipGraph (hip_stream must be a created stream); one graph is
+ *                                kept per (B, H, W), captured anew when x, out or the workspace move.
+ *   fdsr_hsenet_debug_tensor     runs the forward up to a named tap and copies it out as NHWC [B][dims3[0]][dims3[1]][dims3[2]].
+ *                                Taps: head, mI.head, mI.base.nl / .gate, mI.base, mI.down.in, mI.down.nl / .gate, mI.down (half
+ *                                scale), mI.up, mI.cross, mI.hsem, mI (I = 0 .. n_basic_modules - 1), body, up.
+ * fdsr_swinir_to_u8 is save_img1 for this family too.  Errors as for fdsr_swinir. */
+#define FDSR_HSENET_GRAPH 1
+typedef struct fdsr_hsenet_config {
+  int32_t n_feats;
+  int32_t scale;
+  int32_t n_colors;
+  int32_t n_basic_modules;
+} fdsr_hsenet_config;
+typedef struct fdsr_hsenet_obj* fdsr_hsenet;
+int fdsr_hsenet_create(const fdsr_hsenet_config* cfg, fdsr_hsenet* out);
+int fdsr_hsenet_load(fdsr_hsenet s, const char* name, const float* host_f32, const int64_t* shape, int ndim);
+int fdsr_hsenet_workspace_bytes(fdsr_hsenet s, int batch, int height, int width, size_t* bytes);
+int fdsr_hsenet_forward(fdsr_hsenet s, const float* x_nchw, int batch, int height, int width, float* out_nchw, void* workspace,
+                        size_t workspace_bytes, void* hip_stream, int flags);
+int fdsr_hsenet_debug_tensor(fdsr_hsenet s, const char* name, const float* x_nchw, int batch, int height, int width, float* out_nhwc,
+                             size_t capacity_floats, int* dims3, void* workspace, size_t workspace_bytes, void* hip_stream);
+void fdsr_hsenet_destroy(fdsr_hsenet s);
+
 /* -- EDiffSR: ConditionalNAFNet noise predictor + IR-SDE reverse process (EDiffSR/codes: DenoisingNAFNet_arch.py,
  * module_util.py, utils/sde_utils.py) --------------------------------------------------------------------------------
  * An object of its own, independent of fdsr_handle.  fp32 activations (NHWC inside), every 1x1 / 2x2 / 3x3 convolution a GEMM
